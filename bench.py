@@ -1,14 +1,16 @@
 """Headline benchmark: CIFAR-10 32x32 EDM2 U-Net (35.6 M params) bf16 training images/sec on N MI355X,
 plus 32-step Heun sampler images/sec, roofline of the dominant kernel and a CPU baseline.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 A step = Diffuser -> Embedding -> Denoiser fwd -> sigma-weighted MSE -> backward -> bucketed gradient
 all-reduce over RCCL (overlapped with backward) -> fused Adam+EMA, on a synthetic device-resident batch
 (x = 0.5*randn(B,3,32,32), seed 42; conf/cifar10.yaml model, dropout 0.13, EMA 0.13, lr 0.02).
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  --dump-outputs DIR also writes what the timed paths computed, as DIR/<name>.npy
+(dump_sample): the loss of the last timed training step and the weights, EMA weights and Adam moments it left behind,
+and the images of each sampler leg's last timed solve -- seeded inputs, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -137,6 +139,33 @@ def vendor_gemm_tflops(device, M=131072, N=256, K=2304, iters=10):
         return None
 
 
+DUMP_MAX_ELEMS = 1 << 21       # per dumped array (8 MB of float32): the at most eight arrays stay under DUMP_MAX_BYTES
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_sample(t):
+    """`t` as a host float32 array (float64 stays float64): whole when it has at most DUMP_MAX_ELEMS elements, else its
+    elements at DUMP_MAX_ELEMS flat indices drawn with a fixed seed (the same indices in every run of the same sizes)"""
+    t = t.detach()
+    if t.dtype != torch.float64:
+        t = t.float()
+    if t.numel() > DUMP_MAX_ELEMS:
+        import numpy as np
+        idx = np.sort(np.random.default_rng(0).choice(t.numel(), DUMP_MAX_ELEMS, replace=False))
+        t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+    return t.cpu().numpy()
+
+
+def write_dumps(path, arrays):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES} byte limit"
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    note(f"wrote {len(arrays)} arrays ({total / 2**20:.1f} MB) to {path}")
+
+
 def build_model(device, conditional=False):
     import tinyedm
     from tinyedm.config import compose, instantiate
@@ -174,7 +203,7 @@ def timed_region(args, step, world, device, marks=None, last=None):
     return dt
 
 
-def train_bench(args, rank, world, device):
+def train_bench(args, rank, world, device, dumps=None):
     import tinyedm
     from tinyedm_amd import ops
     from tinyedm_amd.ddp import GradReducer
@@ -367,6 +396,11 @@ def train_bench(args, rank, world, device):
         # a diverged / corrupted run draws less power, clocks higher and "wins": never report it
         raise RuntimeError(f"bench: loss {final_loss}, |weights| {wnorm} after the timed region -- the step is broken")
     note(f"timed region done: {dt / args.steps * 1e3:.2f} ms/step")
+    if dumps is not None:
+        # the last timed step's loss and the state it left behind, taken before the instrumented steps below move it on
+        dumps.update({"train_loss": dump_sample(loss.reshape(1)), "train_weights": dump_sample(base.arena.theta),
+                      "train_ema_weights": dump_sample(opt.ema_arena), "train_adam_m": dump_sample(base.m),
+                      "train_adam_v": dump_sample(base.v)})
 
     # ---- roofline of the dominant kernel (3x3 implicit-GEMM conv): extra, instrumented EAGER steps AFTER the
     # timed region: HIP events around every launch on the launch stream; algorithmic FLOPs from the shapes.
@@ -406,7 +440,7 @@ def train_bench(args, rank, world, device):
 F32_MFMA_PEAK_TFLOPS = 157.3   # v_mfma_f32_32x32x2_f32, MI355X_MICROARCH.md chip table (= the fp32 vector rate)
 
 
-def sampler_bench(args, model, device, network_dtype="bf16"):
+def sampler_bench(args, model, device, network_dtype="bf16", dumps=None):
     """32-step Heun solve (63 network evaluations) of the CIFAR-10 net, hipGraph-captured.  network_dtype "bf16": the
     training path's kernels; "f32": the reference-precision evaluation (exact-fp32 kernels, csrc/eval_f32.hip) -- the
     reference itself samples in fp32 (generate.py:39-44)."""
@@ -433,6 +467,8 @@ def sampler_bench(args, model, device, network_dtype="bf16"):
     dt = (time.perf_counter() - t0) / iters
     if not bool(torch.isfinite(out).all()):
         raise RuntimeError("bench: the sampler produced non-finite images")
+    if dumps is not None:
+        dumps[f"sampler_{network_dtype}_images"] = dump_sample(out)
     model.denoiser.set_eval_dtype("bf16")
     peak = F32_MFMA_PEAK_TFLOPS if f32 else MFMA_PEAK_TFLOPS
     passes = 3 if split else 1      # split-bf16: every conv product is three bf16 MFMA passes (hi.w_hi + hi.w_lo + lo.w_hi)
@@ -516,7 +552,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-batch", type=int, default=8)
     ap.add_argument("--cpu-steps", type=int, default=20, help="timed CPU-oracle steps (~0.5 s each on 16 threads)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed paths computed (last timed step / solve) to DIR/<name>.npy, float32, at most 64 MB")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.no_graph:
         args.step_launch = "eager"
 
@@ -556,7 +596,8 @@ def main():
             os.close(saved_fd)
     assert world == args.gpus, f"--gpus {args.gpus} but WORLD_SIZE={world}"
 
-    model, ips, ms, final_loss, roof, launch_info = train_bench(args, rank, world, device)
+    dumps = {} if args.dump_outputs and rank == 0 else None
+    model, ips, ms, final_loss, roof, launch_info = train_bench(args, rank, world, device, dumps)
     out = None
     if rank == 0:
         # dominant kernel: k_conv3x3_v6<5,0,4> (3x3 implicit GEMM of the 32x32 layers: forward convs, with the modulation
@@ -629,18 +670,20 @@ def main():
         # sampler + CPU baseline ride on the single-GPU line only (the N>1 lines are the training scaling series;
         # hipGraph capture beside a live RCCL communicator is avoided)
         if not args.no_sampler and world == 1:
-            out["sampler"] = sampler_bench(args, model, device)
+            out["sampler"] = sampler_bench(args, model, device, dumps=dumps)
             if not args.no_sampler_fp32:
                 # the reference-faithful figure: the reference samples in fp32; priced against the f32-input MFMA peak
-                out["sampler_fp32"] = sampler_bench(args, model, device, "f32")
+                out["sampler_fp32"] = sampler_bench(args, model, device, "f32", dumps)
                 # the same precision class (2^-17 per operand; 32-step trajectory 2e-6 from the exact path) on the bf16 kernels:
                 # split-bf16, three MFMA passes per product (tinyedm_amd/networks.py _conv_f32)
-                out["sampler_fp32_split"] = sampler_bench(args, model, device, "f32x3")
+                out["sampler_fp32_split"] = sampler_bench(args, model, device, "f32x3", dumps)
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args)
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()
+    if dumps is not None:
+        write_dumps(args.dump_outputs, dumps)
     if rank == 0:
         print(json.dumps(out), flush=True)
 

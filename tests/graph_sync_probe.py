@@ -13,14 +13,17 @@ import torch  # noqa: E402
 
 import tinyedm  # noqa: E402
 from tinyedm.config import compose, instantiate  # noqa: E402
-from tinyedm_amd import ops  # noqa: E402
+from tinyedm_amd import networks, ops  # noqa: E402
 from tinyedm_amd.ema import EMAOptimizer  # noqa: E402
-from tinyedm_amd.graph import CapturedTrainStep  # noqa: E402
+from tinyedm_amd.graph import CapturedTrainStep, _backward  # noqa: E402
 
 N = 14
 
 
 class Probed(CapturedTrainStep):
+    """CapturedTrainStep._capture with the probes added: the same launch structure (one chain unless wgrad_fork, as in
+    the warm-up steps before it), the same backward hook"""
+
     def _capture(self, batch):
         x, y = batch
         sx, sy = x.clone(), None if y is None else y.clone()
@@ -30,10 +33,11 @@ class Probed(CapturedTrainStep):
         torch.cuda.synchronize()
         ops.capture_begin()
         graph = torch.cuda.CUDAGraph()
+        side, networks.WGRAD_STREAM = networks.WGRAD_STREAM, self.wgrad_fork
         try:
             with torch.cuda.graph(graph, stream=self.stream):
                 loss = self.model.training_step((sx, sy), 0)
-                loss.backward()
+                _backward(self.model, loss)
                 gb = (~torch.isfinite(self.base.arena.grad)).sum().float()
                 gn = self.base.arena.grad.float().norm()
                 self.base.step_dyn(self.params.dev, ema=self.ema.ema_arena)
@@ -44,6 +48,7 @@ class Probed(CapturedTrainStep):
                 self.hist.index_copy_(0, self.ctr, torch.stack([loss.float().reshape(()), gb, gn, wb, mb, eb])[None])
                 self.ctr += 1
         finally:
+            networks.WGRAD_STREAM = side
             token = ops.capture_end()
             self._restore(snap)
         return graph, sx, sy, loss, token
