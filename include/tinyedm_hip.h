@@ -398,6 +398,14 @@ int edm_heun_euler(const float* x, const float* D, float t0, float t1, float* dx
                    edm_stream_t stream);
 int edm_heun_correct(const float* x, const float* dx, const float* x1, const float* D1, float t0, float t1, float* out,
                      long n, unsigned* health, edm_stream_t stream);
+/* guided Heun updates: the two above on D = Dg + w*(Dm - Dg), mixed in registers (no temporary D).  w is a DEVICE
+ * pointer to one float, read at run time, so a captured solve follows later writes to it; w == 0 reproduces the
+ * unguided update fed Dg bit for bit.  Same health bit. */
+int edm_heun_euler_guided(const float* x, const float* Dm, const float* Dg, const float* w, float t0, float t1,
+                          float* dx, float* x1, long n, unsigned* health, edm_stream_t stream);
+int edm_heun_correct_guided(const float* x, const float* dx, const float* x1, const float* Dm1, const float* Dg1,
+                            const float* w, float t0, float t1, float* out, long n, unsigned* health,
+                            edm_stream_t stream);
 int edm_scale_f32(const float* x, float s, float* y, long n, edm_stream_t stream);
 
 /* ---------------------------------------------------------------- reference-precision evaluation (eval_f32.hip)

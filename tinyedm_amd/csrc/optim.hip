@@ -168,6 +168,83 @@ __global__ void k_heun_correct(const float* __restrict__ x, const float* __restr
   }
   if (health && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(health, 2u);
 }
+// Guided updates: D = Dg + w*(Dm - Dg) in registers, then the unguided kernels' expressions verbatim (w == 0 gives
+// exactly the unguided result on Dg: fmaf(0, d, Dg) == Dg).  w is read from device memory so that a captured solve
+// replays with whatever guidance the host wrote there.  vec: every pointer 16-byte aligned -> dwordx4 over the first
+// n/4*4 elements, the tail (and the whole range when !vec) element by element.
+__device__ __forceinline__ float heun_euler_guided_1(float x, float Dm, float Dg, float w, float t0, float t1,
+                                                     float& dx, bool& bad) {
+  const float D = fmaf(w, Dm - Dg, Dg);
+  const float d = (x - D) / t0;
+  dx = d;
+  const float o = x + (t1 - t0) * d;
+  bad |= !(fabsf(o) <= 3.0e38f);
+  return o;
+}
+__device__ __forceinline__ float heun_correct_guided_1(float x, float dx, float x1, float Dm1, float Dg1, float w,
+                                                       float t0, float t1, bool& bad) {
+  const float D1 = fmaf(w, Dm1 - Dg1, Dg1);
+  const float dp = (x1 - D1) / t1;
+  const float o = x + (t1 - t0) * (0.5f * dx + 0.5f * dp);
+  bad |= !(fabsf(o) <= 3.0e38f);
+  return o;
+}
+__global__ void k_heun_euler_guided(const float* __restrict__ x, const float* __restrict__ Dm,
+                                    const float* __restrict__ Dg, const float* __restrict__ w, float t0, float t1,
+                                    float* __restrict__ dx, float* __restrict__ x1, long n, bool vec,
+                                    unsigned* __restrict__ health) {
+  const float wv = *w;
+  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
+  bool bad = false;
+  long head = 0;
+  if (vec) {
+    head = n / 4 * 4;
+    for (long i = tid * 4; i < head; i += stride * 4) {
+      const f32x4 xv = *reinterpret_cast<const f32x4*>(x + i);
+      const f32x4 mv = *reinterpret_cast<const f32x4*>(Dm + i);
+      const f32x4 gv = *reinterpret_cast<const f32x4*>(Dg + i);
+      f32x4 dv, ov;
+      for (int j = 0; j < 4; ++j) {
+        float d;
+        ov[j] = heun_euler_guided_1(xv[j], mv[j], gv[j], wv, t0, t1, d, bad);
+        dv[j] = d;
+      }
+      *reinterpret_cast<f32x4*>(dx + i) = dv;
+      *reinterpret_cast<f32x4*>(x1 + i) = ov;
+    }
+  }
+  for (long i = head + tid; i < n; i += stride) {
+    float d;
+    x1[i] = heun_euler_guided_1(x[i], Dm[i], Dg[i], wv, t0, t1, d, bad);
+    dx[i] = d;
+  }
+  if (health && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(health, 2u);
+}
+__global__ void k_heun_correct_guided(const float* __restrict__ x, const float* __restrict__ dx,
+                                      const float* __restrict__ x1, const float* __restrict__ Dm1,
+                                      const float* __restrict__ Dg1, const float* __restrict__ w, float t0, float t1,
+                                      float* __restrict__ out, long n, bool vec, unsigned* __restrict__ health) {
+  const float wv = *w;
+  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
+  bool bad = false;
+  long head = 0;
+  if (vec) {
+    head = n / 4 * 4;
+    for (long i = tid * 4; i < head; i += stride * 4) {
+      const f32x4 xv = *reinterpret_cast<const f32x4*>(x + i);
+      const f32x4 dv = *reinterpret_cast<const f32x4*>(dx + i);
+      const f32x4 x1v = *reinterpret_cast<const f32x4*>(x1 + i);
+      const f32x4 mv = *reinterpret_cast<const f32x4*>(Dm1 + i);
+      const f32x4 gv = *reinterpret_cast<const f32x4*>(Dg1 + i);
+      f32x4 ov;
+      for (int j = 0; j < 4; ++j) ov[j] = heun_correct_guided_1(xv[j], dv[j], x1v[j], mv[j], gv[j], wv, t0, t1, bad);
+      *reinterpret_cast<f32x4*>(out + i) = ov;
+    }
+  }
+  for (long i = head + tid; i < n; i += stride)
+    out[i] = heun_correct_guided_1(x[i], dx[i], x1[i], Dm1[i], Dg1[i], wv, t0, t1, bad);
+  if (health && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(health, 2u);
+}
 __global__ void k_scale_f32(const float* __restrict__ x, float s, float* __restrict__ y, long n) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) y[i] = x[i] * s;
 }
@@ -246,6 +323,31 @@ extern "C" int edm_heun_correct(const float* x, const float* dx, const float* x1
   EDM_REQUIRE(x && dx && x1 && D1 && out && n > 0 && t1 != 0.f, "heun_correct: bad args");
   hipLaunchKernelGGL(k_heun_correct, dim3(grid_for(n, 256)), dim3(256), 0, st, x, dx, x1, D1, t0, t1, out, n, health);
   EDM_CHECK_LAUNCH("heun_correct");
+  return EDM_OK;
+}
+static bool aligned16(std::initializer_list<const void*> ps) {
+  for (const void* p : ps)
+    if (reinterpret_cast<uintptr_t>(p) & 15) return false;
+  return true;
+}
+// w: device pointer to the guidance weight (read by the kernel, so a captured graph follows later writes to it)
+extern "C" int edm_heun_euler_guided(const float* x, const float* Dm, const float* Dg, const float* w, float t0,
+                                     float t1, float* dx, float* x1, long n, unsigned* health, hipStream_t st) {
+  EDM_REQUIRE(x && Dm && Dg && w && dx && x1 && n > 0 && t0 != 0.f, "heun_euler_guided: bad args");
+  const bool vec = aligned16({x, Dm, Dg, dx, x1});
+  hipLaunchKernelGGL(k_heun_euler_guided, dim3(grid_for(vec ? (n + 3) / 4 : n, 256)), dim3(256), 0, st, x, Dm, Dg, w,
+                     t0, t1, dx, x1, n, vec, health);
+  EDM_CHECK_LAUNCH("heun_euler_guided");
+  return EDM_OK;
+}
+extern "C" int edm_heun_correct_guided(const float* x, const float* dx, const float* x1, const float* Dm1,
+                                       const float* Dg1, const float* w, float t0, float t1, float* out, long n,
+                                       unsigned* health, hipStream_t st) {
+  EDM_REQUIRE(x && dx && x1 && Dm1 && Dg1 && w && out && n > 0 && t1 != 0.f, "heun_correct_guided: bad args");
+  const bool vec = aligned16({x, dx, x1, Dm1, Dg1, out});
+  hipLaunchKernelGGL(k_heun_correct_guided, dim3(grid_for(vec ? (n + 3) / 4 : n, 256)), dim3(256), 0, st, x, dx, x1,
+                     Dm1, Dg1, w, t0, t1, out, n, vec, health);
+  EDM_CHECK_LAUNCH("heun_correct_guided");
   return EDM_OK;
 }
 extern "C" int edm_scale_f32(const float* x, float s, float* y, long n, hipStream_t st) {

@@ -15,6 +15,15 @@ Extensions (all optional): `--network_dtype`,
 `--in_channels` (the reference's noise dataset hard-codes 3; default = the checkpoint's
 denoiser.in_channels), `--mean/--std` (default: the reference's CIFAR-10 constants), `--seed`, `--no_graph`, and
 `--config_name` to sample from random-init weights of a config instead of a checkpoint (plumbing runs).
+Guided sampling (DeterministicSolver): `--guide_ckpt_path [--guide_load_ema]` (or `--guide_config_name`, random init) loads
+a guide network, evaluated at the same `--network_dtype`, and `--guidance W` samples with D = D_guide + W*(D_main - D_guide):
+classifier-free guidance with an unconditional guide, autoguidance with a smaller / less-trained conditional one.
+`--guidance_interval LO HI` guides only the evaluations with LO < sigma <= HI.  `--guidance 1` (the default) leaves the guide
+unused and the output byte-identical to a run without one.
+
+    python -m tinyedm.generate --ckpt_path cond.ckpt --load_ema --guide_ckpt_path uncond.ckpt --guide_load_ema \\
+        --guidance 2.0 --guidance_interval 0.28 5.42 --output_dir samples --num_samples 50000 --image_size 32 \\
+        --num_classes 10 --batch_size 512
 Multi-GPU = replicas only: under `python -m torch.distributed.run --nproc-per-node N` every rank samples
 its own contiguous index range with its own noise seed and writes `<global index>.png`; there is no collective.
 """
@@ -31,7 +40,8 @@ CIFAR_STD = (0.24703223, 0.24348513, 0.26158784)
 
 def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_classes, batch_size, num_workers=16,
              num_steps=32, *, in_channels=None, mean=None, std=None, seed=0, graph=True, model=None,
-             network_dtype="f32x3") -> None:
+             network_dtype="f32x3", guide=None, guide_ckpt_path=None, guide_load_ema=False, guidance=1.0,
+             guidance_interval=None) -> None:
     from .callbacks import PreditionWriter
     from .datamodules import RandomNoiseDataModule
     from .edm import EDM
@@ -45,7 +55,17 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
         model = EDM.load_from_checkpoint(ckpt_path, load_ema=load_ema)
     model = model.to(dev)
     model.denoiser.set_eval_dtype(network_dtype)
-    model.solver = DeterministicSolver(num_steps=num_steps)
+    if guide_ckpt_path is not None:
+        if guide is not None:
+            raise ValueError("generate: pass guide or guide_ckpt_path, not both")
+        guide = EDM.load_from_checkpoint(guide_ckpt_path, load_ema=guide_load_ema)
+    if guide is not None:
+        guide = guide.to(dev).eval()
+        guide.denoiser.set_eval_dtype(network_dtype)
+        if float(guidance) == 1.0:
+            print(f"[rank {rank}] guidance 1.0: the guide network is unused", flush=True)
+    model.solver = DeterministicSolver(num_steps=num_steps, guide=guide, guidance=guidance,
+                                       guidance_interval=guidance_interval)
     from . import _runtime_env
     if graph and _runtime_env.GRAPH_REPLAY_SAFE:      # otherwise the eager Heun loop: same values
         solve = model.solver.solve
@@ -88,21 +108,40 @@ def main(argv=None):
     parser.add_argument("--config_name", type=str, default=None,
                         help="sample from random-init weights of experiments/conf/<name>.yaml (no checkpoint)")
     parser.add_argument("--config_path", type=str, default=None)
+    # guided sampling
+    parser.add_argument("--guide_ckpt_path", type=str, default=None, help="checkpoint of the guide network")
+    parser.add_argument("--guide_load_ema", action="store_true", help="load the EMA weights of the guide")
+    parser.add_argument("--guide_config_name", type=str, default=None,
+                        help="random-init guide from experiments/conf/<name>.yaml (no checkpoint)")
+    parser.add_argument("--guidance", type=float, default=1.0,
+                        help="guidance weight w: D = D_guide + w*(D_main - D_guide) (default 1.0 = unguided)")
+    parser.add_argument("--guidance_interval", type=float, nargs=2, metavar=("LO", "HI"), default=None,
+                        help="guide only the evaluations with LO < sigma <= HI")
     args = parser.parse_args(argv)
+    if args.guide_ckpt_path is not None and args.guide_config_name is not None:
+        parser.error("--guide_ckpt_path and --guide_config_name are exclusive")
+    from . import networks
+    from .config import compose, instantiate
+    conf_dir = args.config_path or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                                "experiments", "conf")
+
+    def random_init(name):
+        cfg = compose(name, conf_dir)
+        networks.manual_seed(cfg.seed)
+        torch.manual_seed(cfg.seed)
+        return instantiate(cfg.model)
+    # the guide first: the main network's seeding is then the last, as without a guide
+    guide = None if args.guide_config_name is None else random_init(args.guide_config_name)
     model = None
     if args.ckpt_path is None:
         if args.config_name is None:
             parser.error("--ckpt_path is required (or --config_name for a random-init plumbing run)")
-        from . import networks
-        from .config import compose, instantiate
-        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-        cfg = compose(args.config_name, args.config_path or os.path.join(root, "experiments", "conf"))
-        networks.manual_seed(cfg.seed)
-        torch.manual_seed(cfg.seed)
-        model = instantiate(cfg.model)
+        model = random_init(args.config_name)
     generate(args.ckpt_path, args.load_ema, args.output_dir, args.num_samples, args.image_size, args.num_classes,
              args.batch_size, args.num_workers, args.num_steps, in_channels=args.in_channels, mean=args.mean,
-             std=args.std, seed=args.seed, graph=not args.no_graph, model=model, network_dtype=args.network_dtype)
+             std=args.std, seed=args.seed, graph=not args.no_graph, model=model, network_dtype=args.network_dtype,
+             guide=guide, guide_ckpt_path=args.guide_ckpt_path, guide_load_ema=args.guide_load_ema,
+             guidance=args.guidance, guidance_interval=args.guidance_interval)
 
 
 if __name__ == "__main__":

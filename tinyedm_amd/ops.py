@@ -1493,6 +1493,39 @@ def heun_correct(x, dx, x1, D1, t0, t1):
     return out
 
 
+def _guidance_weight(w_dev, x):
+    _chk(w_dev, f32, "w_dev")
+    if w_dev.numel() != 1 or w_dev.device != x.device:
+        raise ValueError(f"w_dev: expected a one-element fp32 tensor on {x.device}, got {tuple(w_dev.shape)} on "
+                         f"{w_dev.device}")
+
+
+def heun_euler_guided(x, Dm, Dg, w_dev, t0, t1):
+    """heun_euler on D = Dg + w*(Dm - Dg), w read on the device from the one-element tensor w_dev"""
+    _chk(x, f32, "x")
+    _chk(Dm, f32, "Dm", x.shape)
+    _chk(Dg, f32, "Dg", x.shape)
+    _guidance_weight(w_dev, x)
+    dx, x1 = torch.empty_like(x), torch.empty_like(x)
+    _lib.call("edm_heun_euler_guided", _p(x), _p(Dm), _p(Dg), _p(w_dev), float(t0), float(t1), _p(dx), _p(x1),
+              x.numel(), _p(health(x.device)), _stream())
+    return dx, x1
+
+
+def heun_correct_guided(x, dx, x1, Dm1, Dg1, w_dev, t0, t1):
+    """heun_correct on D1 = Dg1 + w*(Dm1 - Dg1), w read on the device from the one-element tensor w_dev"""
+    _chk(x, f32, "x")
+    _chk(dx, f32, "dx", x.shape)
+    _chk(x1, f32, "x1", x.shape)
+    _chk(Dm1, f32, "Dm1", x.shape)
+    _chk(Dg1, f32, "Dg1", x.shape)
+    _guidance_weight(w_dev, x)
+    out = torch.empty_like(x)
+    _lib.call("edm_heun_correct_guided", _p(x), _p(dx), _p(x1), _p(Dm1), _p(Dg1), _p(w_dev), float(t0), float(t1),
+              _p(out), x.numel(), _p(health(x.device)), _stream())
+    return out
+
+
 def scale_f32(x, s):
     _chk(x, f32, "x")
     y = torch.empty_like(x)

@@ -1,4 +1,5 @@
 """2nd-order Heun sampler (reference solvers.py:4-59) with the loop optionally captured in a hipGraph."""
+import math
 import weakref
 
 import torch
@@ -21,12 +22,24 @@ class DeterministicSolver:
     The sigma table is built with the reference's exact fp32 expression (bitwise-equal table,
     solvers.py:33-41) and uploaded to the device ONCE: the reference's per-step ``t0.to(device)``
     host->device copies (63 sync points for 32 steps) disappear, which is what makes the whole
-    solve capturable as one hipGraph (``solve(..., graph=True)``)."""
+    solve capturable as one hipGraph (``solve(..., graph=True)``).
+
+    Guided sampling (keyword-only ``guide``, ``guidance``, ``guidance_interval``): an evaluation at sigma uses
+
+        D(x; sigma, c) = D_guide(x; sigma, c) + guidance * (D_main(x; sigma, c) - D_guide(x; sigma, c))
+
+    classifier-free guidance with an unconditional ``guide`` (an unconditional EDM drops the labels itself),
+    autoguidance with a smaller / less-trained conditional one.  With ``guidance_interval=(lo, hi)`` only the
+    evaluations with lo < sigma <= hi (sigma = the fp32 table value) are guided; the others use D_main alone and do not
+    evaluate the guide.  ``guidance == 1`` guides nothing: the guide is never evaluated and the solve is the unguided
+    one.  ``guidance`` and ``guidance_interval`` are plain attributes, read at every solve; a captured solve reads the
+    guidance weight from device memory, so changing it replays the same graph."""
 
     MAX_GRAPHS = 4      # captured solves kept per model (shape / precision combinations; least recently used dropped)
 
     def __init__(self, num_steps: int = 18, sigma_min: float = 0.002, sigma_max: float = 80.0, rho: float = 7.0,
-                 dtype: str | None = None):
+                 dtype: str | None = None, *, guide=None, guidance: float = 1.0,
+                 guidance_interval: tuple[float, float] | None = None):
         self.num_steps = num_steps
         self.sigma_min = sigma_min
         self.sigma_max = sigma_max
@@ -38,39 +51,94 @@ class DeterministicSolver:
         i = torch.arange(num_steps, dtype=torch.float32)
         t = (sigma_max ** (1 / rho) + i / (num_steps - 1) * (sigma_min ** (1 / rho) - sigma_max ** (1 / rho))) ** rho
         self.t_steps = torch.cat([t, torch.zeros(1)])
-        self._graphs = weakref.WeakKeyDictionary()      # model -> {(shapes, device): captured solve}
+        self._graphs = weakref.WeakKeyDictionary()      # model -> {(shapes, device[, guide]): captured solve}
+        self.guide = guide
+        self.guidance = guidance
+        self.guidance_interval = guidance_interval
+        self.guided_evaluations()                       # (validates guidance and guidance_interval)
+
+    # ------------------------------------------------------------------ guidance
+    def guided_evaluations(self) -> tuple[bool, ...]:
+        """Which of the 2N-1 network evaluations are guided, in loop order: Euler at t_0, correction at t_1, Euler at
+        t_1, ..., Euler at t_{N-1}.  Host only; raises ValueError on an invalid guidance setting."""
+        w = float(self.guidance)
+        if not math.isfinite(w):
+            raise ValueError(f"DeterministicSolver: guidance must be finite, got {self.guidance}")
+        if w != 1.0 and self.guide is None:
+            raise ValueError(f"DeterministicSolver: guidance={w} needs a guide network (guide=None)")
+        if self.guidance_interval is not None:
+            lo, hi = (float(v) for v in self.guidance_interval)
+            if not 0.0 <= lo < hi:
+                raise ValueError(f"DeterministicSolver: guidance_interval (lo, hi) needs 0 <= lo < hi, got "
+                                 f"{tuple(self.guidance_interval)}")
+        ts = self.t_steps.tolist()          # the fp32 table values, exactly
+        sigmas = [ts[i // 2 + i % 2] for i in range(2 * self.num_steps - 1)]
+        if w == 1.0:
+            return (False,) * len(sigmas)
+        if self.guidance_interval is None:
+            return (True,) * len(sigmas)
+        return tuple(lo < s <= hi for s in sigmas)
+
+    def _check_guide(self, model, device):
+        """the checks that need the networks: run before any launch of a solve that evaluates the guide"""
+        from .edm import EDM
+        guide = getattr(self.guide, "__self__", self.guide)
+        if isinstance(guide, torch.nn.Module):
+            if guide.training:
+                raise ValueError("DeterministicSolver: the guide network is in training mode; call guide.eval()")
+            t = next(guide.parameters(), None)
+            if t is not None and t.device != device:
+                raise ValueError(f"DeterministicSolver: the guide network is on {t.device}, the solve on {device}")
+        owner = getattr(model, "__self__", model)
+        if isinstance(guide, EDM) and isinstance(owner, EDM):
+            g, m = guide.denoiser, owner.denoiser
+            if (g.in_channels, g.out_channels) != (m.in_channels, m.out_channels):
+                raise ValueError(f"DeterministicSolver: guide channels (in {g.in_channels}, out {g.out_channels}) differ "
+                                 f"from the model's (in {m.in_channels}, out {m.out_channels})")
 
     # ------------------------------------------------------------------ eager
-    def _loop(self, model, x0, class_labels, t_dev):
+    def _loop(self, model, x0, class_labels, t_dev, guided, w_dev):
         ts = self.t_steps.tolist()
         x1 = ops.scale_f32(x0, ts[0])
         for i in range(self.num_steps):
             t0, t1 = ts[i], ts[i + 1]
             x = x1
             D = model(x, t_dev[i], class_labels).float().contiguous()
-            dx, x1 = ops.heun_euler(x, D, t0, t1)
+            if guided[2 * i]:
+                Dg = self.guide(x, t_dev[i], class_labels).float().contiguous()
+                dx, x1 = ops.heun_euler_guided(x, D, Dg, w_dev, t0, t1)
+            else:
+                dx, x1 = ops.heun_euler(x, D, t0, t1)
             if i < self.num_steps - 1:
                 D1 = model(x1, t_dev[i + 1], class_labels).float().contiguous()
-                x1 = ops.heun_correct(x, dx, x1, D1, t0, t1)
+                if guided[2 * i + 1]:
+                    Dg1 = self.guide(x1, t_dev[i + 1], class_labels).float().contiguous()
+                    x1 = ops.heun_correct_guided(x, dx, x1, D1, Dg1, w_dev, t0, t1)
+                else:
+                    x1 = ops.heun_correct(x, dx, x1, D1, t0, t1)
         return x1
 
     @torch.no_grad()
     def solve(self, model, x0, class_labels=None, graph: bool = False):
         if not x0.is_cuda:
             raise RuntimeError("tinyedm_amd.DeterministicSolver: x0 must be a GPU tensor (there is no CPU path)")
+        guided = self.guided_evaluations()
+        if any(guided):
+            self._check_guide(model, x0.device)
         in_dtype = x0.dtype
         x0 = x0.float().contiguous()
         if not graph:
             t_dev = self.t_steps.to(x0.device)
-            return self._loop(model, x0, class_labels, t_dev).to(in_dtype)
-        out = self._solve_graphed(model, x0, class_labels).to(in_dtype)
+            w_dev = torch.full((1,), float(self.guidance), device=x0.device) if any(guided) else None
+            return self._loop(model, x0, class_labels, t_dev, guided, w_dev).to(in_dtype)
+        out = self._solve_graphed(model, x0, class_labels, guided).to(in_dtype)
         # the Heun kernels leave a bit in the device health word when the state went non-finite: a replay that ran
         # with corrupted arguments fails HERE, loudly (one host sync per solve of 2N-1 network evaluations)
         ops.check_health(x0.device, "DeterministicSolver.solve(graph=True)")
         return out
 
     # ------------------------------------------------------------------ hipGraph
-    def _solve_graphed(self, model, x0, class_labels):
+    def _solve_graphed(self, model, x0, class_labels, guided):
         # graphs are cached PER MODEL OBJECT (weakly: a new model allocated at a dead one's address must not replay the
         # dead one's graph, which id(model) as a key allowed)
         owner = getattr(model, "__self__", model)        # a bound method is a fresh object per access: key on its object
@@ -81,27 +149,36 @@ class DeterministicSolver:
             weakref.finalize(owner, _release_solves, per_model)
         # the evaluation precision of the denoiser(s) is part of the key: set_eval_dtype() between two solves must not
         # replay a graph captured with the other path's kernels
-        dtypes = ()
-        if isinstance(owner, torch.nn.Module):
-            dtypes = tuple(getattr(m, "eval_dtype", None) for m in owner.modules() if hasattr(m, "eval_dtype"))
-        key = (tuple(x0.shape), None if class_labels is None else tuple(class_labels.shape), x0.device.index, dtypes)
+        def eval_dtypes(net):
+            if not isinstance(net, torch.nn.Module):
+                return ()
+            return tuple(getattr(m, "eval_dtype", None) for m in net.modules() if hasattr(m, "eval_dtype"))
+        key = (tuple(x0.shape), None if class_labels is None else tuple(class_labels.shape), x0.device.index,
+               eval_dtypes(owner))
+        # a guided solve also keys on the guide (the entry holds it, so its id cannot be reused while the graph that
+        # reads its weights exists) and on which evaluations are guided; NOT on the guidance weight, which the graph
+        # reads from the entry's w_dev.  An unguided solve keeps the unguided key whatever guide is set.
+        guide = getattr(self.guide, "__self__", self.guide) if any(guided) else None
+        if guide is not None:
+            key += (id(guide), eval_dtypes(guide), guided)
         ent = per_model.get(key)
         if ent is None:
             _runtime_env.require_graph_replay_safe("DeterministicSolver.solve(graph=True)")
             t_dev = self.t_steps.to(x0.device)
+            w_dev = None if guide is None else torch.full((1,), float(self.guidance), device=x0.device)
             sx = x0.clone()
             sl = None if class_labels is None else class_labels.clone()
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):          # warm-up outside capture (weight packs, lazy inits)
-                self._loop(model, sx, sl, t_dev)
+                self._loop(model, sx, sl, t_dev, guided, w_dev)
             torch.cuda.current_stream().wait_stream(side)
             g = torch.cuda.CUDAGraph()
             ops.capture_begin()
             ok = False
             try:
                 with torch.cuda.graph(g):
-                    out = self._loop(model, sx, sl, t_dev)
+                    out = self._loop(model, sx, sl, t_dev, guided, w_dev)
                 ok = True
             finally:
                 token = ops.capture_end()
@@ -111,17 +188,20 @@ class DeterministicSolver:
                 old = per_model.pop(next(iter(per_model)))
                 torch.cuda.synchronize()
                 ops.release_capture(old[5])
-            ent = per_model[key] = (g, sx, sl, out, t_dev, token)
+            ent = per_model[key] = (g, sx, sl, out, t_dev, token, w_dev, guide)
         else:
             per_model[key] = per_model.pop(key)              # most recently used last
-        g, sx, sl, out, _, _ = ent
+        g, sx, sl, out, _, _, w_dev, _ = ent
         # the captured evaluations read the persistent eval-mode weight packs: refresh them (a no-op unless the
         # master weights changed since the last solve: optimizer steps, EMA swap, load_state_dict) before replaying
-        if isinstance(model, torch.nn.Module):
-            from .networks import Denoiser
-            for m in model.modules():
-                if isinstance(m, Denoiser) and not m.training:
-                    m._prep_all()
+        from .networks import Denoiser
+        for net in (model, guide):
+            if isinstance(net, torch.nn.Module):
+                for m in net.modules():
+                    if isinstance(m, Denoiser) and not m.training:
+                        m._prep_all()
+        if w_dev is not None:
+            w_dev.fill_(float(self.guidance))
         sx.copy_(x0)
         if sl is not None:
             sl.copy_(class_labels)
