@@ -406,6 +406,15 @@ int edm_heun_euler_guided(const float* x, const float* Dm, const float* Dg, cons
 int edm_heun_correct_guided(const float* x, const float* dx, const float* x1, const float* Dm1, const float* Dg1,
                             const float* w, float t0, float t1, float* out, long n, unsigned* health,
                             edm_stream_t stream);
+/* churn of the stochastic sampler (Karras et al. 2022, Algorithm 2): x_hat = x + c*n, n ~ N(0, 1) drawn in the kernel,
+ * x and x_hat contiguous [B, CHW] fp32.  Element j of sample b is normal j % 4 of one Philox4x32-10 call with counter
+ * (j / 4, b, 0x43480000 ^ step, solve_index) and key (seed_lo, seed_hi); the four normals are Box-Muller of words
+ * (0, 1) and (2, 3).  rec is a DEVICE pointer to four uint32 {seed_lo, seed_hi, solve_index, 0}, read at run time, so a
+ * captured solve draws new noise after the host rewrites it; step and c are by value.  The noise of a sample does not
+ * depend on B or on the memory path (dwordx4 when CHW % 4 == 0 and x, x_hat are 16-byte aligned).  Same health bit as
+ * the Heun updates. */
+int edm_heun_churn(const float* x, float c, const void* rec, int step, int B, long CHW, float* x_hat,
+                   unsigned* health, edm_stream_t stream);
 int edm_scale_f32(const float* x, float s, float* y, long n, edm_stream_t stream);
 
 /* ---------------------------------------------------------------- reference-precision evaluation (eval_f32.hip)

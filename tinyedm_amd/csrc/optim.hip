@@ -3,6 +3,7 @@
 // (edm.py:251-253, ema.py:137-140, 273), and the Heun updates of the sampler (solvers.py:49-57).
 #include "common.h"
 #include <math.h>
+#include <cmath>
 
 namespace {
 
@@ -245,6 +246,46 @@ __global__ void k_heun_correct_guided(const float* __restrict__ x, const float* 
     out[i] = heun_correct_guided_1(x[i], dx[i], x1[i], Dm1[i], Dg1[i], wv, t0, t1, bad);
   if (health && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(health, 2u);
 }
+// Churn of the stochastic sampler (Karras et al. 2022, Algorithm 2): x_hat = x + c*n, n ~ N(0, 1) drawn here.  One
+// thread per quad q of a sample b: element j = 4q + k of sample b takes normal k of
+//   philox4x32_10(ctr = (q, b, 0x43480000 ^ step, solve_index), key = (seed_lo, seed_hi))
+// (the four normals: box_muller(r.x, r.y), box_muller(r.z, r.w), as k_diffuse), so a sample's noise depends only on
+// (seed, solve_index, step, b, j): not on the batch size, the grid or the memory path.  seed and solve_index come from
+// the device record rec = {seed_lo, seed_hi, solve_index, 0}, so a captured solve draws new noise whenever the host
+// rewrites it.  vec: x and x_hat 16-byte aligned and CHW % 4 == 0 -> one dwordx4 load and store per quad; otherwise
+// the same quads element by element (the last quad of a sample may be partial).
+__global__ void k_heun_churn(const float* __restrict__ x, float c, const uint32_t* __restrict__ rec, uint32_t step,
+                             int B, long CHW, float* __restrict__ x_hat, bool vec, unsigned* __restrict__ health) {
+  const uint32_t seed_lo = rec[0], seed_hi = rec[1], solve_index = rec[2];
+  const long nq = (CHW + 3) / 4, total = (long)B * nq;
+  bool bad = false;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long b = i / nq, q = i - b * nq;
+    const Philox4 r = philox4x32_10((uint32_t)q, (uint32_t)b, 0x43480000u ^ step, solve_index, seed_lo, seed_hi);
+    float nn[4];
+    box_muller(r.x, r.y, nn[0], nn[1]);
+    box_muller(r.z, r.w, nn[2], nn[3]);
+    const long e = b * CHW + 4 * q;
+    if (vec) {
+      const f32x4 xv = *reinterpret_cast<const f32x4*>(x + e);
+      f32x4 ov;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        ov[k] = fmaf(c, nn[k], xv[k]);
+        bad |= !(fabsf(ov[k]) <= 3.0e38f);
+      }
+      *reinterpret_cast<f32x4*>(x_hat + e) = ov;
+    } else {
+      const int m = (int)(CHW - 4 * q < 4 ? CHW - 4 * q : 4);
+      for (int k = 0; k < m; ++k) {
+        const float o = fmaf(c, nn[k], x[e + k]);
+        bad |= !(fabsf(o) <= 3.0e38f);
+        x_hat[e + k] = o;
+      }
+    }
+  }
+  if (health && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(health, 2u);
+}
 __global__ void k_scale_f32(const float* __restrict__ x, float s, float* __restrict__ y, long n) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) y[i] = x[i] * s;
 }
@@ -348,6 +389,17 @@ extern "C" int edm_heun_correct_guided(const float* x, const float* dx, const fl
   hipLaunchKernelGGL(k_heun_correct_guided, dim3(grid_for(vec ? (n + 3) / 4 : n, 256)), dim3(256), 0, st, x, dx, x1,
                      Dm1, Dg1, w, t0, t1, out, n, vec, health);
   EDM_CHECK_LAUNCH("heun_correct_guided");
+  return EDM_OK;
+}
+// rec: device pointer to {seed_lo, seed_hi, solve_index, 0} (uint32), read by the kernel; step and c by value
+extern "C" int edm_heun_churn(const float* x, float c, const void* rec, int step, int B, long CHW, float* x_hat,
+                              unsigned* health, hipStream_t st) {
+  EDM_REQUIRE(x && rec && x_hat && B > 0 && CHW > 0 && step >= 0 && std::isfinite(c), "heun_churn: bad args");
+  EDM_REQUIRE((CHW + 3) / 4 <= 0xFFFFFFFFL, "heun_churn: CHW / 4 must fit the 32-bit Philox counter word");
+  const bool vec = CHW % 4 == 0 && aligned16({x, x_hat});
+  hipLaunchKernelGGL(k_heun_churn, dim3(grid_for((long)B * ((CHW + 3) / 4), 256)), dim3(256), 0, st, x, c,
+                     (const uint32_t*)rec, (uint32_t)step, B, CHW, x_hat, vec, health);
+  EDM_CHECK_LAUNCH("heun_churn");
   return EDM_OK;
 }
 extern "C" int edm_scale_f32(const float* x, float s, float* y, long n, hipStream_t st) {

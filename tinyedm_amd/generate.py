@@ -24,6 +24,14 @@ unused and the output byte-identical to a run without one.
     python -m tinyedm.generate --ckpt_path cond.ckpt --load_ema --guide_ckpt_path uncond.ckpt --guide_load_ema \\
         --guidance 2.0 --guidance_interval 0.28 5.42 --output_dir samples --num_samples 50000 --image_size 32 \\
         --num_classes 10 --batch_size 512
+Stochastic sampling (StochasticSolver, Algorithm 2 of Karras et al. 2022): `--S_churn`, `--S_min`, `--S_max`, `--S_noise`
+(EDM's names and defaults: 0, 0, inf, 1).  With `--S_churn` > 0 every step with S_min <= t_i <= S_max first adds fresh
+noise, lifting the state to t_hat_i = (1 + min(S_churn / N, sqrt(2) - 1)) t_i; the noise is drawn in the kernel from
+`--seed` (per rank, as the initial noise) and differs from batch to batch.  Guidance combines with it.  `--S_churn 0`
+(the default) samples with the deterministic solver, byte-identical to a run without these flags.
+
+    python -m tinyedm.generate --ckpt_path last.ckpt --load_ema --S_churn 40 --S_min 0.05 --S_max 50 --S_noise 1.003 \\
+        --output_dir samples --num_samples 50000 --image_size 64 --num_classes 1000 --batch_size 512
 Multi-GPU = replicas only: under `python -m torch.distributed.run --nproc-per-node N` every rank samples
 its own contiguous index range with its own noise seed and writes `<global index>.png`; there is no collective.
 """
@@ -41,11 +49,11 @@ CIFAR_STD = (0.24703223, 0.24348513, 0.26158784)
 def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_classes, batch_size, num_workers=16,
              num_steps=32, *, in_channels=None, mean=None, std=None, seed=0, graph=True, model=None,
              network_dtype="f32x3", guide=None, guide_ckpt_path=None, guide_load_ema=False, guidance=1.0,
-             guidance_interval=None) -> None:
+             guidance_interval=None, S_churn=0.0, S_min=0.0, S_max=float("inf"), S_noise=1.0) -> None:
     from .callbacks import PreditionWriter
     from .datamodules import RandomNoiseDataModule
     from .edm import EDM
-    from .solvers import DeterministicSolver
+    from .solvers import DeterministicSolver, StochasticSolver
     from .trainer import Trainer
 
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -64,8 +72,13 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
         guide.denoiser.set_eval_dtype(network_dtype)
         if float(guidance) == 1.0:
             print(f"[rank {rank}] guidance 1.0: the guide network is unused", flush=True)
-    model.solver = DeterministicSolver(num_steps=num_steps, guide=guide, guidance=guidance,
-                                       guidance_interval=guidance_interval)
+    if float(S_churn) != 0.0:       # (a negative or non-finite S_churn reaches the solver's validation)
+        model.solver = StochasticSolver(num_steps=num_steps, guide=guide, guidance=guidance,
+                                        guidance_interval=guidance_interval, S_churn=S_churn, S_min=S_min,
+                                        S_max=S_max, S_noise=S_noise, seed=seed + 1000003 * rank)
+    else:
+        model.solver = DeterministicSolver(num_steps=num_steps, guide=guide, guidance=guidance,
+                                           guidance_interval=guidance_interval)
     from . import _runtime_env
     if graph and _runtime_env.GRAPH_REPLAY_SAFE:      # otherwise the eager Heun loop: same values
         solve = model.solver.solve
@@ -117,6 +130,13 @@ def main(argv=None):
                         help="guidance weight w: D = D_guide + w*(D_main - D_guide) (default 1.0 = unguided)")
     parser.add_argument("--guidance_interval", type=float, nargs=2, metavar=("LO", "HI"), default=None,
                         help="guide only the evaluations with LO < sigma <= HI")
+    # stochastic sampling (EDM's churn)
+    parser.add_argument("--S_churn", type=float, default=0.0,
+                        help="stochasticity strength: gamma_i = min(S_churn / num_steps, sqrt(2) - 1) (default 0 = "
+                             "deterministic sampling)")
+    parser.add_argument("--S_min", type=float, default=0.0, help="churn only steps with S_min <= t_i (default 0)")
+    parser.add_argument("--S_max", type=float, default=float("inf"), help="churn only steps with t_i <= S_max (default inf)")
+    parser.add_argument("--S_noise", type=float, default=1.0, help="scale of the churn noise (default 1)")
     args = parser.parse_args(argv)
     if args.guide_ckpt_path is not None and args.guide_config_name is not None:
         parser.error("--guide_ckpt_path and --guide_config_name are exclusive")
@@ -141,7 +161,8 @@ def main(argv=None):
              args.batch_size, args.num_workers, args.num_steps, in_channels=args.in_channels, mean=args.mean,
              std=args.std, seed=args.seed, graph=not args.no_graph, model=model, network_dtype=args.network_dtype,
              guide=guide, guide_ckpt_path=args.guide_ckpt_path, guide_load_ema=args.guide_load_ema,
-             guidance=args.guidance, guidance_interval=args.guidance_interval)
+             guidance=args.guidance, guidance_interval=args.guidance_interval, S_churn=args.S_churn, S_min=args.S_min,
+             S_max=args.S_max, S_noise=args.S_noise)
 
 
 if __name__ == "__main__":

@@ -5,6 +5,7 @@ Layout conventions: activations are NHWC bf16 tensors of shape (B, H, W, C) (con
 "rows" means B*H*W.  Per-(sample,channel) quantities are fp32 (B, C).
 """
 import ctypes
+import math
 import os
 from typing import Optional
 
@@ -1524,6 +1525,50 @@ def heun_correct_guided(x, dx, x1, Dm1, Dg1, w_dev, t0, t1):
     _lib.call("edm_heun_correct_guided", _p(x), _p(dx), _p(x1), _p(Dm1), _p(Dg1), _p(w_dev), float(t0), float(t1),
               _p(out), x.numel(), _p(health(x.device)), _stream())
     return out
+
+
+def churn_record(seed: int, solve_index: int, device=None, out=None):
+    """The four-word device record edm_heun_churn reads its stream from: {seed_lo, seed_hi, solve_index, 0} as uint32,
+    held in an int32 tensor.  Writes into `out` when given (one host->device copy), else allocates on `device`."""
+    seed, solve_index = int(seed), int(solve_index)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"churn_record: seed must be in [0, 2**64), got {seed}")
+    if not 0 <= solve_index < 1 << 32:
+        raise ValueError(f"churn_record: solve_index must be in [0, 2**32), got {solve_index}")
+    words = (seed & 0xFFFFFFFF, seed >> 32, solve_index, 0)
+    host = torch.tensor([w - (1 << 32) if w >= 1 << 31 else w for w in words], dtype=torch.int32)   # (the uint32 bits)
+    if out is None:
+        return host.to(device)
+    _churn_rec(out, out)
+    out.copy_(host)
+    return out
+
+
+def _churn_rec(rec, x):
+    _chk(rec, torch.int32, "rec")
+    if rec.numel() != 4 or rec.device != x.device:
+        raise ValueError(f"rec: expected a four-element int32 tensor on {x.device} (ops.churn_record), got "
+                         f"{tuple(rec.shape)} on {rec.device}")
+
+
+def heun_churn(x, c, rec, step):
+    """x_hat = x + c*n with n ~ N(0, 1) drawn in the kernel (the churn of the stochastic sampler).  x: contiguous fp32
+    [B, ...]; rec: the device record of ops.churn_record (seed, solve index); step: the solver step, part of the
+    Philox counter.  The noise of sample b depends only on (seed, solve index, step, b, element)."""
+    _chk(x, f32, "x")
+    if x.dim() < 2 or x.numel() == 0:
+        raise ValueError(f"x: expected a non-empty [B, ...] tensor, got {tuple(x.shape)}")
+    _churn_rec(rec, x)
+    c, step = float(c), int(step)
+    if not math.isfinite(c):
+        raise ValueError(f"heun_churn: c must be finite, got {c}")
+    if not 0 <= step < 1 << 31:
+        raise ValueError(f"heun_churn: step must be in [0, 2**31), got {step}")
+    B = x.shape[0]
+    x_hat = torch.empty_like(x)
+    _lib.call("edm_heun_churn", _p(x), c, _p(rec), step, B, x.numel() // B, _p(x_hat), _p(health(x.device)),
+              _stream())
+    return x_hat
 
 
 def scale_f32(x, s):

@@ -1,6 +1,8 @@
-"""2nd-order Heun sampler (reference solvers.py:4-59) with the loop optionally captured in a hipGraph."""
+"""2nd-order Heun samplers with the loop optionally captured in a hipGraph: the deterministic one of the reference
+(solvers.py:4-59) and the stochastic one of Karras et al. 2022 (Algorithm 2)."""
 import math
 import weakref
+from typing import NamedTuple
 
 import torch
 
@@ -71,13 +73,33 @@ class DeterministicSolver:
             if not 0.0 <= lo < hi:
                 raise ValueError(f"DeterministicSolver: guidance_interval (lo, hi) needs 0 <= lo < hi, got "
                                  f"{tuple(self.guidance_interval)}")
-        ts = self.t_steps.tolist()          # the fp32 table values, exactly
-        sigmas = [ts[i // 2 + i % 2] for i in range(2 * self.num_steps - 1)]
+        sigmas = self._evaluation_sigmas()
         if w == 1.0:
             return (False,) * len(sigmas)
         if self.guidance_interval is None:
             return (True,) * len(sigmas)
         return tuple(lo < s <= hi for s in sigmas)
+
+    def _evaluation_sigmas(self) -> list[float]:
+        """the sigma of each of the 2N-1 evaluations, in loop order (the fp32 table values, exactly)"""
+        ts = self.t_steps.tolist()
+        return [ts[i // 2 + i % 2] for i in range(2 * self.num_steps - 1)]
+
+    # ------------------------------------------------------------------ subclass hooks (StochasticSolver)
+    def _graph_key_extra(self) -> tuple:
+        """what the subclass adds to the key of a captured solve"""
+        return ()
+
+    def _solve_state(self, device):
+        """per-solve device tensors the loop reads (a captured entry owns its own), written for this solve; or None"""
+        return None
+
+    def _write_solve_state(self, state) -> None:
+        """rewrite an entry's device tensors before a replay"""
+
+    def _step_start(self, x, i, ts, t_dev, state):
+        """the state, sigma and device sigma the step-i Euler evaluation starts from"""
+        return x, ts[i], t_dev[i]
 
     def _check_guide(self, model, device):
         """the checks that need the networks: run before any launch of a solve that evaluates the guide"""
@@ -97,15 +119,15 @@ class DeterministicSolver:
                                  f"from the model's (in {m.in_channels}, out {m.out_channels})")
 
     # ------------------------------------------------------------------ eager
-    def _loop(self, model, x0, class_labels, t_dev, guided, w_dev):
+    def _loop(self, model, x0, class_labels, t_dev, guided, w_dev, state=None):
         ts = self.t_steps.tolist()
         x1 = ops.scale_f32(x0, ts[0])
         for i in range(self.num_steps):
-            t0, t1 = ts[i], ts[i + 1]
-            x = x1
-            D = model(x, t_dev[i], class_labels).float().contiguous()
+            x, t0, s0 = self._step_start(x1, i, ts, t_dev, state)
+            t1 = ts[i + 1]
+            D = model(x, s0, class_labels).float().contiguous()
             if guided[2 * i]:
-                Dg = self.guide(x, t_dev[i], class_labels).float().contiguous()
+                Dg = self.guide(x, s0, class_labels).float().contiguous()
                 dx, x1 = ops.heun_euler_guided(x, D, Dg, w_dev, t0, t1)
             else:
                 dx, x1 = ops.heun_euler(x, D, t0, t1)
@@ -130,7 +152,8 @@ class DeterministicSolver:
         if not graph:
             t_dev = self.t_steps.to(x0.device)
             w_dev = torch.full((1,), float(self.guidance), device=x0.device) if any(guided) else None
-            return self._loop(model, x0, class_labels, t_dev, guided, w_dev).to(in_dtype)
+            state = self._solve_state(x0.device)
+            return self._loop(model, x0, class_labels, t_dev, guided, w_dev, state).to(in_dtype)
         out = self._solve_graphed(model, x0, class_labels, guided).to(in_dtype)
         # the Heun kernels leave a bit in the device health word when the state went non-finite: a replay that ran
         # with corrupted arguments fails HERE, loudly (one host sync per solve of 2N-1 network evaluations)
@@ -161,24 +184,26 @@ class DeterministicSolver:
         guide = getattr(self.guide, "__self__", self.guide) if any(guided) else None
         if guide is not None:
             key += (id(guide), eval_dtypes(guide), guided)
+        key += self._graph_key_extra()
         ent = per_model.get(key)
         if ent is None:
             _runtime_env.require_graph_replay_safe("DeterministicSolver.solve(graph=True)")
             t_dev = self.t_steps.to(x0.device)
             w_dev = None if guide is None else torch.full((1,), float(self.guidance), device=x0.device)
+            state = self._solve_state(x0.device)
             sx = x0.clone()
             sl = None if class_labels is None else class_labels.clone()
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):          # warm-up outside capture (weight packs, lazy inits)
-                self._loop(model, sx, sl, t_dev, guided, w_dev)
+                self._loop(model, sx, sl, t_dev, guided, w_dev, state)
             torch.cuda.current_stream().wait_stream(side)
             g = torch.cuda.CUDAGraph()
             ops.capture_begin()
             ok = False
             try:
                 with torch.cuda.graph(g):
-                    out = self._loop(model, sx, sl, t_dev, guided, w_dev)
+                    out = self._loop(model, sx, sl, t_dev, guided, w_dev, state)
                 ok = True
             finally:
                 token = ops.capture_end()
@@ -188,10 +213,11 @@ class DeterministicSolver:
                 old = per_model.pop(next(iter(per_model)))
                 torch.cuda.synchronize()
                 ops.release_capture(old[5])
-            ent = per_model[key] = (g, sx, sl, out, t_dev, token, w_dev, guide)
+            ent = per_model[key] = (g, sx, sl, out, t_dev, token, w_dev, guide, state)
         else:
             per_model[key] = per_model.pop(key)              # most recently used last
-        g, sx, sl, out, _, _, w_dev, _ = ent
+            self._write_solve_state(ent[8])
+        g, sx, sl, out, _, _, w_dev, _, _ = ent
         # the captured evaluations read the persistent eval-mode weight packs: refresh them (a no-op unless the
         # master weights changed since the last solve: optimizer steps, EMA swap, load_state_dict) before replaying
         from .networks import Denoiser
@@ -207,3 +233,112 @@ class DeterministicSolver:
             sl.copy_(class_labels)
         g.replay()
         return out.clone()
+
+
+class ChurnSchedule(NamedTuple):
+    """Per-step churn of a StochasticSolver, fp32 tensors of num_steps entries."""
+    gamma: torch.Tensor     # min(S_churn / N, sqrt(2) - 1) inside S_min <= t_i <= S_max, else 0
+    t_hat: torch.Tensor     # t_i + gamma_i * t_i: the sigma the step's Euler evaluation sees
+    c: torch.Tensor         # S_noise * sqrt(t_hat_i^2 - t_i^2): the scale of the fresh noise
+
+
+class _ChurnState(NamedTuple):
+    rec: torch.Tensor       # the device record of the noise stream (ops.churn_record)
+    t_hat: torch.Tensor     # device table of t_hat
+    steps: tuple            # per step: (churned, t_hat_i, c_i) as host floats
+
+
+def _check_uint(v, bits: int, name: str) -> None:
+    try:
+        ok = not isinstance(v, bool) and int(v) == v and 0 <= int(v) < 1 << bits
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError(f"StochasticSolver: {name} must be an integer in [0, 2**{bits}), got {v!r}")
+
+
+class StochasticSolver(DeterministicSolver):
+    """Algorithm 2 of Karras et al. 2022: the Heun solver with "churn".  Before step i, inside S_min <= t_i <= S_max,
+    the state is lifted to t_hat_i = t_i + gamma_i t_i by fresh noise,
+
+        x_hat = x_i + S_noise * sqrt(t_hat_i^2 - t_i^2) * n,   n ~ N(0, I),   gamma_i = min(S_churn / N, sqrt(2) - 1),
+
+    and the Heun step runs from (x_hat, t_hat_i) to t_{i+1}.  Same arguments as DeterministicSolver, guidance included,
+    plus keyword-only S_churn, S_min, S_max, S_noise (EDM's names and defaults) and ``seed``.
+
+    The noise is drawn in the kernel (ops.heun_churn) from Philox4x32-10 keyed by ``seed`` with the counter holding
+    (element, sample, step, solve index): it depends neither on the batch size nor on the launch geometry.  Every
+    ``solve()`` draws the noise of solve ``solve_index`` and then increments it, so consecutive batches differ and a run
+    is reproducible from ``seed``; setting ``solve_index`` back reproduces a solve.  A captured solve reads the seed
+    and the index from a device record written before every replay, so neither is part of the graph key; the churn
+    schedule is.  ``S_churn == 0`` is the DeterministicSolver solve: same kernels, same graph key, same result."""
+
+    def __init__(self, num_steps: int = 18, sigma_min: float = 0.002, sigma_max: float = 80.0, rho: float = 7.0,
+                 dtype: str | None = None, *, guide=None, guidance: float = 1.0,
+                 guidance_interval: tuple[float, float] | None = None, S_churn: float = 0.0, S_min: float = 0.0,
+                 S_max: float = math.inf, S_noise: float = 1.0, seed: int = 0):
+        self.S_churn = S_churn
+        self.S_min = S_min
+        self.S_max = S_max
+        self.S_noise = S_noise
+        self.seed = seed
+        self.solve_index = 0
+        super().__init__(num_steps, sigma_min, sigma_max, rho, dtype, guide=guide, guidance=guidance,
+                         guidance_interval=guidance_interval)     # (validates the churn settings too)
+
+    def churn_schedule(self) -> ChurnSchedule:
+        """gamma_i, t_hat_i and c_i of every step, computed in fp64 from the fp32 sigma table and rounded to fp32
+        (c_i from the rounded t_hat_i).  Host only; raises ValueError on an invalid churn setting or seed."""
+        S_churn, S_noise = float(self.S_churn), float(self.S_noise)
+        S_min, S_max = float(self.S_min), float(self.S_max)
+        if not (math.isfinite(S_churn) and S_churn >= 0.0):
+            raise ValueError(f"StochasticSolver: S_churn must be finite and >= 0, got {self.S_churn}")
+        if not (math.isfinite(S_noise) and S_noise >= 0.0):
+            raise ValueError(f"StochasticSolver: S_noise must be finite and >= 0, got {self.S_noise}")
+        if not 0.0 <= S_min <= S_max:
+            raise ValueError(f"StochasticSolver: needs 0 <= S_min <= S_max, got S_min={self.S_min}, S_max={self.S_max}")
+        _check_uint(self.seed, 64, "seed")
+        _check_uint(self.solve_index, 32, "solve_index")
+        t = self.t_steps[:-1].double()
+        g = min(S_churn / self.num_steps, math.sqrt(2.0) - 1.0)
+        gamma = ((t >= S_min) & (t <= S_max)).double() * g
+        t_hat = (t + gamma * t).float()
+        c = (S_noise * (t_hat.double() ** 2 - t ** 2).sqrt()).float()
+        return ChurnSchedule(gamma.float(), t_hat, c)
+
+    def _churn_steps(self) -> tuple:
+        s = self.churn_schedule()
+        return tuple((g > 0.0, th, c) for g, th, c in zip(s.gamma.tolist(), s.t_hat.tolist(), s.c.tolist()))
+
+    def _evaluation_sigmas(self) -> list[float]:
+        """the Euler evaluation of step i sees t_hat_i, its correction t_{i+1}"""
+        th = [s[1] for s in self._churn_steps()]
+        ts = self.t_steps.tolist()
+        return [th[i // 2] if i % 2 == 0 else ts[i // 2 + 1] for i in range(2 * self.num_steps - 1)]
+
+    def _graph_key_extra(self) -> tuple:
+        steps = self._churn_steps()
+        return (steps,) if any(s[0] for s in steps) else ()
+
+    def _solve_state(self, device):
+        steps = self._churn_steps()
+        if not any(s[0] for s in steps):
+            return None
+        return _ChurnState(ops.churn_record(self.seed, self.solve_index, device),
+                           torch.tensor([s[1] for s in steps], dtype=torch.float32, device=device), steps)
+
+    def _write_solve_state(self, state) -> None:
+        if state is not None:
+            ops.churn_record(self.seed, self.solve_index, out=state.rec)
+
+    def _step_start(self, x, i, ts, t_dev, state):
+        if state is None or not state.steps[i][0]:
+            return x, ts[i], t_dev[i]
+        _, t_hat, c = state.steps[i]
+        return ops.heun_churn(x, c, state.rec, i), t_hat, state.t_hat[i]
+
+    @torch.no_grad()
+    def solve(self, model, x0, class_labels=None, graph: bool = False):
+        out = super().solve(model, x0, class_labels, graph)
+        self.solve_index += 1
+        return out
