@@ -394,6 +394,17 @@ int edm_weighted_mse(const float* D, const float* clean, const float* sigma, con
 int edm_adam_ema(float* theta, float* grad, float* m, float* v, float* ema, long n, float lr, float b1, float b2,
                  float eps, int step, float ema_beta, float grad_scale, const void* dyn, int zero_grad,
                  unsigned* health, edm_stream_t stream);
+/* post-hoc EMA (Karras et al. 2024, Sec. 3): edm_adam_ema plus K = 1..4 profile arenas of n floats, updated from the new
+ * weights in the same pass, p_k = beta_k * p_k + (1 - beta_k) * theta_new.  theta / m / v / ema are bitwise those of
+ * edm_adam_ema.  profiles: HOST array of K device pointers (16-byte aligned); betas: DEVICE array of K floats read at
+ * run time, so a captured step follows the betas the host writes before each replay. */
+int edm_adam_ema_phema(float* theta, float* grad, float* m, float* v, float* ema, float* const* profiles, int K,
+                       const float* betas, long n, float lr, float b1, float b2, float eps, int step, float ema_beta,
+                       float grad_scale, const void* dyn, int zero_grad, unsigned* health, edm_stream_t stream);
+/* post-hoc EMA reconstruction: acc_l += w_l * snap for l < L <= 8.  acc: device fp64 [L][n], snap: device fp32 [n],
+ * w: HOST array of L doubles.  edm_phema_finish rounds n fp64 values to fp32. */
+int edm_phema_accumulate(double* acc, const float* snap, const double* w, int L, long n, edm_stream_t stream);
+int edm_phema_finish(const double* acc, float* out, long n, edm_stream_t stream);
 int edm_heun_euler(const float* x, const float* D, float t0, float t1, float* dx, float* x1, long n, unsigned* health,
                    edm_stream_t stream);
 int edm_heun_correct(const float* x, const float* dx, const float* x1, const float* D1, float t0, float t1, float* out,

@@ -99,6 +99,9 @@ SIGNATURES = {
     "edm_diffuse_given": [P, P, P, P, P, F, F, I, L, P],
     "edm_weighted_mse": [P, P, P, P, F, P, P, I, L, P, P, P],
     "edm_adam_ema": [P, P, P, P, P, L, F, F, F, F, I, F, F, P, I, P, P],
+    "edm_adam_ema_phema": [P, P, P, P, P, P, I, P, L, F, F, F, F, I, F, F, P, I, P, P],
+    "edm_phema_accumulate": [P, P, P, I, L, P],
+    "edm_phema_finish": [P, P, L, P],
     "edm_heun_euler": [P, P, F, F, P, P, L, P, P],
     "edm_heun_correct": [P, P, P, P, F, F, P, L, P, P],
     "edm_heun_euler_guided": [P, P, P, P, F, F, P, P, L, P, P],

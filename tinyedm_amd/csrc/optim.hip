@@ -143,6 +143,113 @@ __global__ void k_adam_ema(float* __restrict__ theta, float* __restrict__ grad, 
   if (health && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(health, 1u);
 }
 
+// Post-hoc EMA tracking (Karras et al. 2024, Sec. 3): k_adam_ema plus K power-function profile arenas updated from the
+// new weights in the same pass, p_k = beta_k * p_k + (1 - beta_k) * theta_new.  The theta / m / v / ema expressions are
+// k_adam_ema's verbatim: theta, m and v come out bitwise equal; the main EMA may differ in the last bit, because the
+// compiler fuses b*e + (1-b)*t into an FMA for some lanes and not others, differently in the two kernels.  The K betas are read from device memory so that the eager and the
+// captured step share one launch form and a replay picks up the betas the host wrote before it.
+struct PhemaArenas {
+  float* p[4];
+};
+template <int K>
+__global__ void k_adam_ema_phema(float* __restrict__ theta, float* __restrict__ grad, float* __restrict__ m,
+                                 float* __restrict__ v, float* __restrict__ ema, PhemaArenas prof,
+                                 const float* __restrict__ betas, long n4, long n, AdamArgs a,
+                                 const StepParams* __restrict__ dyn, int zero_grad, unsigned* __restrict__ health) {
+  if (dyn) { a.lr = dyn->lr; a.ema_beta = dyn->ema_beta; a.grad_scale = dyn->grad_scale; a.bc1 = dyn->bc1; a.bc2sqrt = dyn->bc2sqrt; }
+  float pb[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) pb[k] = betas[k];
+  const float step_size = a.lr / a.bc1;
+  bool bad = false;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+    if (i * 4 + 3 < n) {
+      f32x4 t = *reinterpret_cast<f32x4*>(theta + i * 4);
+      f32x4 g = *reinterpret_cast<const f32x4*>(grad + i * 4);
+      if (zero_grad) *reinterpret_cast<f32x4*>(grad + i * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
+      f32x4 mm = *reinterpret_cast<f32x4*>(m + i * 4);
+      f32x4 vv = *reinterpret_cast<f32x4*>(v + i * 4);
+      f32x4 ee;
+      if (ema) ee = *reinterpret_cast<f32x4*>(ema + i * 4);
+      f32x4 pp[K];
+#pragma unroll
+      for (int k = 0; k < K; ++k) pp[k] = *reinterpret_cast<f32x4*>(prof.p[k] + i * 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float gj = g[j] * a.grad_scale;
+        mm[j] = a.b1 * mm[j] + (1.f - a.b1) * gj;
+        vv[j] = a.b2 * vv[j] + (1.f - a.b2) * gj * gj;
+        t[j] -= step_size * mm[j] / (sqrtf(vv[j]) / a.bc2sqrt + a.eps);
+        if (ema) ee[j] = a.ema_beta * ee[j] + (1.f - a.ema_beta) * t[j];
+#pragma unroll
+        for (int k = 0; k < K; ++k) pp[k][j] = pb[k] * pp[k][j] + (1.f - pb[k]) * t[j];
+        bad |= !(fabsf(gj) <= 3.0e38f) || !(fabsf(t[j]) <= 3.0e38f);
+      }
+      *reinterpret_cast<f32x4*>(theta + i * 4) = t;
+      *reinterpret_cast<f32x4*>(m + i * 4) = mm;
+      *reinterpret_cast<f32x4*>(v + i * 4) = vv;
+      if (ema) *reinterpret_cast<f32x4*>(ema + i * 4) = ee;
+#pragma unroll
+      for (int k = 0; k < K; ++k) *reinterpret_cast<f32x4*>(prof.p[k] + i * 4) = pp[k];
+    } else {
+      for (long e = i * 4; e < n; ++e) {
+        const float gj = grad[e] * a.grad_scale;
+        const float mj = a.b1 * m[e] + (1.f - a.b1) * gj;
+        const float vj = a.b2 * v[e] + (1.f - a.b2) * gj * gj;
+        const float tj = theta[e] - step_size * mj / (sqrtf(vj) / a.bc2sqrt + a.eps);
+        m[e] = mj;
+        v[e] = vj;
+        theta[e] = tj;
+        if (zero_grad) grad[e] = 0.f;
+        if (ema) ema[e] = a.ema_beta * ema[e] + (1.f - a.ema_beta) * tj;
+#pragma unroll
+        for (int k = 0; k < K; ++k) prof.p[k][e] = pb[k] * prof.p[k][e] + (1.f - pb[k]) * tj;
+        bad |= !(fabsf(gj) <= 3.0e38f) || !(fabsf(tj) <= 3.0e38f);
+      }
+    }
+  }
+  if (health && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(health, 1u);
+}
+
+// Post-hoc EMA reconstruction: acc[l][i] += w[l] * snap[i] for L <= 8 target lengths in one pass over a snapshot.  The
+// accumulator is fp64, so hundreds of terms with |w| ~ 3 sum to the same result in any order.  vec: n % 4 == 0 and
+// snap / acc 16-byte aligned -> dwordx4 loads of snap, the rest element by element.
+struct PhemaWeights {
+  double w[8];
+};
+template <int L>
+__global__ void k_phema_accumulate(double* __restrict__ acc, const float* __restrict__ snap, PhemaWeights w, long n,
+                                   bool vec) {
+  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
+  long head = 0;
+  if (vec) {
+    head = n;
+    for (long i = tid * 4; i < n; i += stride * 4) {
+      const f32x4 s = *reinterpret_cast<const f32x4*>(snap + i);
+#pragma unroll
+      for (int l = 0; l < L; ++l) {
+        double2* d = reinterpret_cast<double2*>(acc + l * n + i);
+        double2 lo = d[0], hi = d[1];
+        lo.x = fma(w.w[l], (double)s[0], lo.x);
+        lo.y = fma(w.w[l], (double)s[1], lo.y);
+        hi.x = fma(w.w[l], (double)s[2], hi.x);
+        hi.y = fma(w.w[l], (double)s[3], hi.y);
+        d[0] = lo;
+        d[1] = hi;
+      }
+    }
+  }
+  for (long i = head + tid; i < n; i += stride) {
+    const double s = (double)snap[i];
+#pragma unroll
+    for (int l = 0; l < L; ++l) acc[l * n + i] = fma(w.w[l], s, acc[l * n + i]);
+  }
+}
+__global__ void k_f64_to_f32(const double* __restrict__ a, float* __restrict__ out, long n) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+    out[i] = (float)a[i];
+}
+
 // dx = (x-D)/t0 ; x1 = x + (t1-t0)*dx
 __global__ void k_heun_euler(const float* __restrict__ x, const float* __restrict__ Dn, float t0, float t1,
                              float* __restrict__ dx, float* __restrict__ x1, long n, unsigned* __restrict__ health) {
@@ -349,6 +456,63 @@ extern "C" int edm_adam_ema(float* theta, float* grad, float* m, float* v, float
   hipLaunchKernelGGL(k_adam_ema, dim3(grid_for(n4, 256)), dim3(256), 0, st, theta, grad, m, v, ema, n4, n, a,
                      (const StepParams*)dyn, zero_grad, health);
   EDM_CHECK_LAUNCH("adam_ema");
+  return EDM_OK;
+}
+// edm_adam_ema plus K (1..4) post-hoc EMA profile arenas of n floats each: profiles is a HOST array of K device pointers
+// (taken by value, so the arenas are fixed for a captured launch), betas a DEVICE array of K floats read at run time.
+extern "C" int edm_adam_ema_phema(float* theta, float* grad, float* m, float* v, float* ema, float* const* profiles,
+                                  int K, const float* betas, long n, float lr, float b1, float b2, float eps, int step,
+                                  float ema_beta, float grad_scale, const void* dyn, int zero_grad, unsigned* health,
+                                  hipStream_t st) {
+  EDM_REQUIRE(theta && grad && m && v && n > 0 && step >= 1, "adam_ema_phema: bad args");
+  EDM_REQUIRE(profiles && betas && K >= 1 && K <= 4, "adam_ema_phema: 1 <= K <= 4 profiles and a beta array required");
+  PhemaArenas prof = {{nullptr, nullptr, nullptr, nullptr}};
+  for (int k = 0; k < K; ++k) {
+    EDM_REQUIRE(profiles[k] && (uintptr_t)profiles[k] % 16 == 0, "adam_ema_phema: profile arenas must be 16-byte aligned");
+    prof.p[k] = profiles[k];
+  }
+  EDM_REQUIRE(((uintptr_t)theta % 16 == 0) && ((uintptr_t)grad % 16 == 0) && ((uintptr_t)m % 16 == 0) &&
+                  ((uintptr_t)v % 16 == 0) && (!ema || (uintptr_t)ema % 16 == 0),
+              "adam_ema_phema: arenas must be 16-byte aligned");
+  AdamArgs a;
+  a.lr = lr; a.b1 = b1; a.b2 = b2; a.eps = eps;
+  a.bc1 = (float)(1.0 - pow((double)b1, (double)step));
+  a.bc2sqrt = (float)sqrt(1.0 - pow((double)b2, (double)step));
+  a.ema_beta = ema_beta;
+  a.grad_scale = grad_scale;
+  const long n4 = (n + 3) / 4;
+  const dim3 grid(grid_for(n4, 256)), block(256);
+  const StepParams* d = (const StepParams*)dyn;
+  switch (K) {
+    case 1: hipLaunchKernelGGL(k_adam_ema_phema<1>, grid, block, 0, st, theta, grad, m, v, ema, prof, betas, n4, n, a, d, zero_grad, health); break;
+    case 2: hipLaunchKernelGGL(k_adam_ema_phema<2>, grid, block, 0, st, theta, grad, m, v, ema, prof, betas, n4, n, a, d, zero_grad, health); break;
+    case 3: hipLaunchKernelGGL(k_adam_ema_phema<3>, grid, block, 0, st, theta, grad, m, v, ema, prof, betas, n4, n, a, d, zero_grad, health); break;
+    default: hipLaunchKernelGGL(k_adam_ema_phema<4>, grid, block, 0, st, theta, grad, m, v, ema, prof, betas, n4, n, a, d, zero_grad, health); break;
+  }
+  EDM_CHECK_LAUNCH("adam_ema_phema");
+  return EDM_OK;
+}
+// acc: DEVICE fp64 [L][n] (row l at acc + l*n), snap: DEVICE fp32 [n], w: HOST array of L doubles; acc_l += w_l * snap
+extern "C" int edm_phema_accumulate(double* acc, const float* snap, const double* w, int L, long n, hipStream_t st) {
+  EDM_REQUIRE(acc && snap && w && L >= 1 && L <= 8 && n > 0, "phema_accumulate: bad args (1 <= L <= 8)");
+  PhemaWeights pw = {};
+  for (int l = 0; l < L; ++l) pw.w[l] = w[l];
+  const bool vec = n % 4 == 0 && (uintptr_t)acc % 16 == 0 && (uintptr_t)snap % 16 == 0;
+  const dim3 grid(grid_for(vec ? n / 4 : n, 256)), block(256);
+  switch (L) {
+#define EDM_PHEMA_ACC(LL) case LL: hipLaunchKernelGGL(k_phema_accumulate<LL>, grid, block, 0, st, acc, snap, pw, n, vec); break;
+    EDM_PHEMA_ACC(1) EDM_PHEMA_ACC(2) EDM_PHEMA_ACC(3) EDM_PHEMA_ACC(4)
+    EDM_PHEMA_ACC(5) EDM_PHEMA_ACC(6) EDM_PHEMA_ACC(7) EDM_PHEMA_ACC(8)
+#undef EDM_PHEMA_ACC
+  }
+  EDM_CHECK_LAUNCH("phema_accumulate");
+  return EDM_OK;
+}
+// out = (float)acc, n elements (round to nearest): the last step of a reconstruction
+extern "C" int edm_phema_finish(const double* acc, float* out, long n, hipStream_t st) {
+  EDM_REQUIRE(acc && out && n > 0, "phema_finish: bad args");
+  hipLaunchKernelGGL(k_f64_to_f32, dim3(grid_for(n, 256)), dim3(256), 0, st, acc, out, n);
+  EDM_CHECK_LAUNCH("phema_finish");
   return EDM_OK;
 }
 // health (nullable device word): bit 1 is OR-ed in when the new state holds a non-finite value

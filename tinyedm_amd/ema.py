@@ -113,6 +113,43 @@ class FlatArena:
         self.rebind_grads()
 
 
+class PowerProfiles:
+    """The post-hoc EMA profiles of a FusedAdam (Karras et al. 2024, Sec. 3; tinyedm_amd/posthoc_ema.py): K fp32 arenas
+    laid out like the parameter arena, each updated in the optimizer's pass with beta = (1 - 1/t)^(gamma_k + 1), t the
+    1-based count of profile updates.  The K betas live in a device array that `upload(t)` rewrites from a ring of
+    pinned host rows (fp64 on the host, rounded to fp32), so the eager and the captured step share one launch form."""
+
+    SLOTS = 16
+
+    def __init__(self, theta: torch.Tensor, gammas):
+        self.gammas = tuple(float(g) for g in gammas)
+        K = len(self.gammas)
+        if not 1 <= K <= ops.PHEMA_MAX_PROFILES:
+            raise ValueError(f"post-hoc EMA: 1 to {ops.PHEMA_MAX_PROFILES} profiles, got {K}")
+        self.arenas = theta.detach().clone().unsqueeze(0).repeat(K, 1)       # (K, numel): row k is profile k
+        self.count = 0
+        self.betas = torch.zeros(K, device=theta.device, dtype=torch.float32)
+        self._host = torch.zeros(self.SLOTS, K, dtype=torch.float32).pin_memory()
+        self._events = [None] * self.SLOTS
+        self._i = 0
+
+    def beta_values(self, t: int):
+        """host betas of the t-th update (fp64 -> fp32)"""
+        return np.array([(1.0 - 1.0 / t) ** (g + 1.0) for g in self.gammas], dtype=np.float32)
+
+    def upload(self, t: int):
+        """write the betas of update t into the device array (stream-ordered before the next optimizer launch)"""
+        k = self._i % self.SLOTS
+        self._i += 1
+        if self._events[k] is not None:
+            self._events[k].synchronize()
+        self._host[k].numpy()[:] = self.beta_values(t)
+        self.betas.copy_(self._host[k], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self._events[k] = ev
+
+
 class FusedAdam(torch.optim.Optimizer):
     """Adam (no weight decay / amsgrad) with torch.optim.Adam semantics, one launch over the arena."""
 
@@ -130,6 +167,19 @@ class FusedAdam(torch.optim.Optimizer):
     # off by default because torch optimizers leave .grad intact after step()).
     fuse_zero_grad = False
     _cleared = False
+    # post-hoc EMA profiles (PowerProfiles), attached by posthoc_ema.PostHocEMA; None: the step is the plain adam_ema
+    phema: Optional[PowerProfiles] = None
+
+    def attach_profiles(self, gammas) -> PowerProfiles:
+        """start tracking post-hoc EMA profiles with these gammas: every later step() / step_dyn() updates them"""
+        self.phema = PowerProfiles(self.arena.theta, gammas)
+        return self.phema
+
+    def _adam_phema(self, ema, step, ema_beta, grad_scale, dyn, zero_grad):
+        g = self.param_groups[0]
+        ops.adam_ema_phema(self.arena.theta, self.arena.grad, self.m, self.v, ema, self.phema.arenas.unbind(0),
+                           self.phema.betas, g["lr"], g["betas"][0], g["betas"][1], g["eps"], step, ema_beta,
+                           grad_scale, dyn=dyn, zero_grad=zero_grad)
 
     def zero_grad(self, set_to_none: bool = False):
         # step() cleared the arena itself (fuse_zero_grad) and nothing has been written into it since: free.  "Since"
@@ -148,8 +198,13 @@ class FusedAdam(torch.optim.Optimizer):
         g = self.param_groups[0]
         self.arena.rebind_grads()
         self.step_count += 1
-        ops.adam_ema(self.arena.theta, self.arena.grad, self.m, self.v, ema, g["lr"], g["betas"][0], g["betas"][1],
-                     g["eps"], self.step_count, ema_beta, self.grad_scale, zero_grad=self.fuse_zero_grad)
+        if self.phema is None:
+            ops.adam_ema(self.arena.theta, self.arena.grad, self.m, self.v, ema, g["lr"], g["betas"][0], g["betas"][1],
+                         g["eps"], self.step_count, ema_beta, self.grad_scale, zero_grad=self.fuse_zero_grad)
+        else:
+            self.phema.upload(self.phema.count + 1)
+            self._adam_phema(ema, self.step_count, ema_beta, self.grad_scale, None, self.fuse_zero_grad)
+            self.phema.count += 1
         self._cleared = bool(self.fuse_zero_grad)
         from . import networks
         self._fwd_epoch_at_clear = networks.FORWARD_EPOCH
@@ -163,6 +218,9 @@ class FusedAdam(torch.optim.Optimizer):
         (graph.CapturedTrainStep owns the host-side counters)."""
         g = self.param_groups[0]
         self.arena.rebind_grads()
+        if self.phema is not None:      # (the profile betas: uploaded by the caller, PowerProfiles.upload)
+            self._adam_phema(ema, max(1, self.step_count), 0.0, 1.0, dyn, True)
+            return
         ops.adam_ema(self.arena.theta, self.arena.grad, self.m, self.v, ema, g["lr"], g["betas"][0], g["betas"][1],
                      g["eps"], max(1, self.step_count), 0.0, 1.0, dyn=dyn, zero_grad=True)
 
@@ -172,7 +230,9 @@ class FusedAdam(torch.optim.Optimizer):
         # (Parameter re-created, deepcopy, user re-init) from the one that wrote it
         return {"m": self.m, "v": self.v, "step": self.step_count, "layout": FlatArena.LAYOUT,
                 "offsets": list(self.arena.offsets), "numels": [p.numel() for p in self.arena.params],
-                "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]}
+                "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups],
+                **({} if self.phema is None else {"phema": {"profiles": self.phema.arenas, "count": self.phema.count,
+                                                             "gammas": list(self.phema.gammas)}})}
 
     def load_state_dict(self, sd):
         """Accepts this class's own layout ({m, v, step}: flat arenas) or torch.optim.Adam's
@@ -199,7 +259,11 @@ class FusedAdam(torch.optim.Optimizer):
                     self.m[o_new:o_new + n].copy_(sd["m"][o_old:o_old + n])
                     self.v[o_new:o_new + n].copy_(sd["v"][o_old:o_old + n])
             self.step_count = int(sd["step"])
+            if self.phema is not None:
+                self._load_profiles(sd, old)
         elif "state" in sd:
+            if self.phema is not None:
+                self._load_profiles(sd, None)
             a = self.arena
             if len(sd["state"]) not in (0, len(a.params)):
                 raise ValueError(f"optimizer state has {len(sd['state'])} entries, the model {len(a.params)} parameters")
@@ -218,6 +282,29 @@ class FusedAdam(torch.optim.Optimizer):
             raise KeyError("optimizer state dict has neither this build's {m, v, step} nor torch Adam's {state, param_groups}")
         for g, s in zip(self.param_groups, sd["param_groups"]):
             g.update({k: v for k, v in s.items() if k != "params"})
+
+
+    def _load_profiles(self, sd, old_offsets):
+        """the post-hoc EMA profiles of `sd` (same slices as m / v) into the attached PowerProfiles"""
+        ph = sd.get("phema")
+        if ph is None:
+            raise ValueError("optimizer state: post-hoc EMA tracking is on, but the checkpoint holds no profile state -- "
+                             "the profiles cannot be recreated mid-run (resume without the PostHocEMA callback, or "
+                             "start tracking from step 0)")
+        if [float(g) for g in ph["gammas"]] != list(self.phema.gammas):
+            raise ValueError(f"optimizer state: the checkpoint tracks post-hoc EMA gammas {list(ph['gammas'])}, the run "
+                             f"{list(self.phema.gammas)}")
+        src, dst, a = ph["profiles"], self.phema.arenas, self.arena
+        if tuple(src.shape) != (dst.shape[0], sd["m"].numel()):
+            raise ValueError(f"optimizer state: post-hoc EMA profiles of shape {tuple(src.shape)}, expected "
+                             f"({dst.shape[0]}, {sd['m'].numel()})")
+        if old_offsets == list(a.offsets) and src.shape == dst.shape:
+            dst.copy_(src)
+        else:
+            for p, o_new, o_old in zip(a.params, a.offsets, old_offsets):
+                n = p.numel()
+                dst[:, o_new:o_new + n].copy_(src[:, o_old:o_old + n])
+        self.phema.count = int(ph["count"])
 
 
 def _grads_written_since_clear(opt: "FusedAdam") -> bool:

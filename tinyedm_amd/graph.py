@@ -123,21 +123,28 @@ class CapturedTrainStep:
             beta = (1 - 1 / (self.ema.current_step + 1)) ** (self.ema.gamma + 1)
         self.params.upload(step=networks.rng.step, seed=networks.rng.seed, lr=float(g["lr"]), ema_beta=float(beta),
                            grad_scale=float(self.grad_scale), bc1=1.0 - b1 ** t, bc2sqrt=math.sqrt(1.0 - b2 ** t))
+        if self.base.phema is not None:     # post-hoc EMA profiles: their betas ride in a device array of their own
+            self.base.phema.upload(self.base.phema.count + 1)
 
     def _advance(self):
         self.base.step_count += 1
         if self.ema is not None:
             self.ema.current_step += 1
         networks.rng.step += 1
+        if self.base.phema is not None:
+            self.base.phema.count += 1
         networks.bump_weight_epoch()
 
     def _snapshot(self):
-        return (self.base.step_count, self.ema.current_step if self.ema is not None else 0, networks.rng.step)
+        return (self.base.step_count, self.ema.current_step if self.ema is not None else 0, networks.rng.step,
+                self.base.phema.count if self.base.phema is not None else 0)
 
     def _restore(self, snap):
-        self.base.step_count, cs, networks.rng.step = snap
+        self.base.step_count, cs, networks.rng.step, pc = snap
         if self.ema is not None:
             self.ema.current_step = cs
+        if self.base.phema is not None:
+            self.base.phema.count = pc
 
     def _eager(self, batch):
         """one step through the ordinary Python path, driven by the same device parameter record"""

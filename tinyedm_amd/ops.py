@@ -1477,6 +1477,64 @@ def adam_ema(theta, grad, m, v, ema, lr, b1, b2, eps, step, ema_beta, grad_scale
               _p(health(theta.device)), _stream())
 
 
+PHEMA_MAX_PROFILES = 4          # edm_adam_ema_phema: K
+PHEMA_MAX_LENGTHS = 8           # edm_phema_accumulate: L
+
+
+def adam_ema_phema(theta, grad, m, v, ema, profiles, betas, lr, b1, b2, eps, step, ema_beta, grad_scale=1.0, dyn=None,
+                   zero_grad=False):
+    """adam_ema plus the post-hoc EMA profiles: every tensor of `profiles` (1..4 fp32 arenas of theta's size) gets
+    p = beta_k * p + (1 - beta_k) * theta_new in the same pass, beta_k read on the device from `betas` (K fp32)."""
+    for t, nme in ((theta, "theta"), (grad, "grad"), (m, "m"), (v, "v")):
+        _chk(t, f32, nme)
+        if t.numel() != theta.numel():
+            raise ValueError("adam_ema_phema: arena size mismatch")
+    if ema is not None:
+        _chk(ema, f32, "ema")
+        if ema.numel() != theta.numel():
+            raise ValueError("adam_ema_phema: arena size mismatch")
+    profiles = list(profiles)
+    K = len(profiles)
+    if not 1 <= K <= PHEMA_MAX_PROFILES:
+        raise ValueError(f"adam_ema_phema: 1 to {PHEMA_MAX_PROFILES} profiles, got {K}")
+    for k, p in enumerate(profiles):
+        _chk(p, f32, f"profiles[{k}]")
+        if p.numel() != theta.numel() or p.device != theta.device:
+            raise ValueError(f"adam_ema_phema: profiles[{k}] must be an arena of {theta.numel()} floats on {theta.device}")
+    _chk(betas, f32, "betas", (K,))
+    if betas.device != theta.device:
+        raise ValueError(f"adam_ema_phema: betas must live on {theta.device}")
+    ptrs = (ctypes.c_void_p * K)(*[p.data_ptr() for p in profiles])
+    _lib.call("edm_adam_ema_phema", _p(theta), _p(grad), _p(m), _p(v), _p(ema), ptrs, K, _p(betas), theta.numel(),
+              float(lr), float(b1), float(b2), float(eps), int(step), float(ema_beta), float(grad_scale), _dyn(dyn),
+              int(bool(zero_grad)), _p(health(theta.device)), _stream())
+
+
+def phema_accumulate(acc, snap, weights):
+    """acc[l] += weights[l] * snap for every row l of the fp64 accumulator acc [L, n] (L <= 8); snap: fp32, n elements"""
+    _chk(acc, torch.float64, "acc")
+    _chk(snap, f32, "snap")
+    if acc.dim() != 2 or snap.numel() != acc.shape[1] or snap.device != acc.device:
+        raise ValueError(f"phema_accumulate: acc [L, n] and snap [n] on one device, got {tuple(acc.shape)} and "
+                         f"{tuple(snap.shape)}")
+    L = acc.shape[0]
+    w = [float(x) for x in weights]
+    if len(w) != L or not 1 <= L <= PHEMA_MAX_LENGTHS:
+        raise ValueError(f"phema_accumulate: 1 to {PHEMA_MAX_LENGTHS} weights, one per row of acc, got {len(w)} for {L} rows")
+    if not all(math.isfinite(x) for x in w):
+        raise ValueError("phema_accumulate: weights must be finite")
+    _lib.call("edm_phema_accumulate", _p(acc), _p(snap), (ctypes.c_double * L)(*w), L, acc.shape[1], _stream())
+
+
+def phema_finish(acc):
+    """fp64 accumulator -> fp32 (round to nearest), same shape"""
+    _chk(acc, torch.float64, "acc")
+    out = torch.empty(acc.shape, device=acc.device, dtype=f32)
+    if acc.numel():
+        _lib.call("edm_phema_finish", _p(acc), _p(out), acc.numel(), _stream())
+    return out
+
+
 def heun_euler(x, D, t0, t1):
     _chk(x, f32, "x")
     _chk(D, f32, "D", x.shape)

@@ -262,6 +262,8 @@ class Trainer:
                     if self.global_rank == 0 and self.global_step % self.log_every_n_steps == 0:
                         print(f"[fit] epoch {epoch} step {self.global_step} loss {float(loss.detach()):.4f} "
                               f"{imgs / (time.time() - t0):.1f} img/s", flush=True)
+                    # Lightning's hook, here once per completed optimizer step (posthoc_ema.PostHocEMA writes its snapshots)
+                    self._call("on_train_batch_end", model, loss, batch, bi)
                     if 0 < self.max_steps <= self.global_step:
                         done = True
                         break
