@@ -426,6 +426,15 @@ int edm_heun_correct_guided(const float* x, const float* dx, const float* x1, co
  * the Heun updates. */
 int edm_heun_churn(const float* x, float c, const void* rec, int step, int B, long CHW, float* x_hat,
                    unsigned* health, edm_stream_t stream);
+/* DPM-Solver++ multistep update (data prediction, sigma(t) = t): m = Dg + w*(Dm - Dg) when guided (Dg and w both
+ * non-null; w a DEVICE pointer, as above), else m = Dm; x_out = a*x + c0*m + c1*m1 + c2*m2, with m1 / m2 the
+ * previous steps' m (nullable: a null term is absent; m2 needs m1).  m is also written to m_out (nullable), the
+ * solver-owned history.  The row (a, c0, c1, c2) = (0, 1, 0, 0) returns m bit for bit.  All operands fp32, n elements,
+ * x_out / m_out alias none of them; dwordx4 when every operand is 16-byte aligned.  Same health bit as the Heun
+ * updates. */
+int edm_dpm_multistep(const float* x, const float* Dm, const float* Dg, const float* w, const float* m1,
+                      const float* m2, float a, float c0, float c1, float c2, float* x_out, float* m_out, long n,
+                      unsigned* health, edm_stream_t stream);
 int edm_scale_f32(const float* x, float s, float* y, long n, edm_stream_t stream);
 
 /* ---------------------------------------------------------------- reference-precision evaluation (eval_f32.hip)

@@ -393,6 +393,59 @@ __global__ void k_heun_churn(const float* __restrict__ x, float c, const uint32_
   }
   if (health && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(health, 2u);
 }
+// DPM-Solver++ multistep update in data-prediction form (sigma(t) = t, s(t) = 1):
+//   m = Dg + w*(Dm - Dg)  (G; else m = Dm),   x_out = a*x + c0*m + c1*m1 + c2*m2   (H = number of history terms)
+// evaluated as fmaf(a, x, fmaf(c2, m2, fmaf(c1, m1, c0*m))), so the row (0, 1, 0, 0) of the final step returns m
+// itself.  m is also written to m_out (nullable): the solver's history buffer, read back as m1 / m2 by the next steps.
+// w is read from device memory (a captured solve follows later writes to it); w == 0 mixes to exactly Dg.  vec: every
+// operand 16-byte aligned -> dwordx4 over the first n/4*4 elements, the tail (and the whole range when !vec) scalar.
+template <bool G, int H>
+__device__ __forceinline__ float dpm_multistep_1(float x, float Dm, float Dg, float w, float m1, float m2, float a,
+                                                 float c0, float c1, float c2, float& m, bool& bad) {
+  m = G ? fmaf(w, Dm - Dg, Dg) : Dm;
+  float o = c0 * m;
+  if (H >= 1) o = fmaf(c1, m1, o);
+  if (H >= 2) o = fmaf(c2, m2, o);
+  o = fmaf(a, x, o);
+  bad |= !(fabsf(o) <= 3.0e38f);
+  return o;
+}
+template <bool G, int H>
+__global__ void k_dpm_multistep(const float* __restrict__ x, const float* __restrict__ Dm,
+                                const float* __restrict__ Dg, const float* __restrict__ w,
+                                const float* __restrict__ m1, const float* __restrict__ m2, float a, float c0, float c1,
+                                float c2, float* __restrict__ x_out, float* __restrict__ m_out, long n, bool vec,
+                                unsigned* __restrict__ health) {
+  const float wv = G ? *w : 0.f;
+  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
+  bool bad = false;
+  long head = 0;
+  if (vec) {
+    head = n / 4 * 4;
+    for (long i = tid * 4; i < head; i += stride * 4) {
+      const f32x4 xv = *reinterpret_cast<const f32x4*>(x + i);
+      const f32x4 dv = *reinterpret_cast<const f32x4*>(Dm + i);
+      f32x4 gv{}, h1{}, h2{}, ov, mv;
+      if (G) gv = *reinterpret_cast<const f32x4*>(Dg + i);
+      if (H >= 1) h1 = *reinterpret_cast<const f32x4*>(m1 + i);
+      if (H >= 2) h2 = *reinterpret_cast<const f32x4*>(m2 + i);
+      for (int j = 0; j < 4; ++j) {
+        float m;
+        ov[j] = dpm_multistep_1<G, H>(xv[j], dv[j], gv[j], wv, h1[j], h2[j], a, c0, c1, c2, m, bad);
+        mv[j] = m;
+      }
+      *reinterpret_cast<f32x4*>(x_out + i) = ov;
+      if (m_out) *reinterpret_cast<f32x4*>(m_out + i) = mv;
+    }
+  }
+  for (long i = head + tid; i < n; i += stride) {
+    float m;
+    x_out[i] = dpm_multistep_1<G, H>(x[i], Dm[i], G ? Dg[i] : 0.f, wv, H >= 1 ? m1[i] : 0.f, H >= 2 ? m2[i] : 0.f,
+                                     a, c0, c1, c2, m, bad);
+    if (m_out) m_out[i] = m;
+  }
+  if (health && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(health, 2u);
+}
 __global__ void k_scale_f32(const float* __restrict__ x, float s, float* __restrict__ y, long n) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) y[i] = x[i] * s;
 }
@@ -564,6 +617,28 @@ extern "C" int edm_heun_churn(const float* x, float c, const void* rec, int step
   hipLaunchKernelGGL(k_heun_churn, dim3(grid_for((long)B * ((CHW + 3) / 4), 256)), dim3(256), 0, st, x, c,
                      (const uint32_t*)rec, (uint32_t)step, B, CHW, x_hat, vec, health);
   EDM_CHECK_LAUNCH("heun_churn");
+  return EDM_OK;
+}
+// Dg and w both given (guided) or both null; m2 needs m1; m_out nullable.  x_out and m_out alias no operand.
+extern "C" int edm_dpm_multistep(const float* x, const float* Dm, const float* Dg, const float* w, const float* m1,
+                                 const float* m2, float a, float c0, float c1, float c2, float* x_out, float* m_out,
+                                 long n, unsigned* health, hipStream_t st) {
+  EDM_REQUIRE(x && Dm && x_out && n > 0 && (Dg == nullptr) == (w == nullptr) && (m1 != nullptr || m2 == nullptr) &&
+              std::isfinite(a) && std::isfinite(c0) && std::isfinite(c1) && std::isfinite(c2),
+              "dpm_multistep: bad args");
+  const bool vec = aligned16({x, Dm, Dg, m1, m2, x_out, m_out});       // (a null pointer counts as aligned)
+  const dim3 grid(grid_for(vec ? (n + 3) / 4 : n, 256)), block(256);
+  const int H = m2 ? 2 : m1 ? 1 : 0;
+#define EDM_DPM_LAUNCH(G_, H_)                                                                                     \
+  hipLaunchKernelGGL((k_dpm_multistep<G_, H_>), grid, block, 0, st, x, Dm, Dg, w, m1, m2, a, c0, c1, c2, x_out, \
+                     m_out, n, vec, health)
+  if (Dg) {
+    if (H == 0) EDM_DPM_LAUNCH(true, 0); else if (H == 1) EDM_DPM_LAUNCH(true, 1); else EDM_DPM_LAUNCH(true, 2);
+  } else {
+    if (H == 0) EDM_DPM_LAUNCH(false, 0); else if (H == 1) EDM_DPM_LAUNCH(false, 1); else EDM_DPM_LAUNCH(false, 2);
+  }
+#undef EDM_DPM_LAUNCH
+  EDM_CHECK_LAUNCH("dpm_multistep");
   return EDM_OK;
 }
 extern "C" int edm_scale_f32(const float* x, float s, float* y, long n, hipStream_t st) {

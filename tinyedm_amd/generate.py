@@ -32,6 +32,13 @@ noise, lifting the state to t_hat_i = (1 + min(S_churn / N, sqrt(2) - 1)) t_i; t
 
     python -m tinyedm.generate --ckpt_path last.ckpt --load_ema --S_churn 40 --S_min 0.05 --S_max 50 --S_noise 1.003 \\
         --output_dir samples --num_samples 50000 --image_size 64 --num_classes 1000 --batch_size 512
+Multistep sampling (MultistepSolver, DPM-Solver++ of Lu et al. 2022): `--solver dpmpp` with `--solver_order` 1, 2 (the
+default, DPM-Solver++(2M)) or 3 spends one network evaluation per step, N in all against Heun's 2N - 1.  It combines
+with every guidance flag; a nonzero `--S_churn` with it is an error.  `--solver heun` (the default) is the Heun solver,
+byte-identical to a run without these flags.
+
+    python -m tinyedm.generate --ckpt_path last.ckpt --load_ema --solver dpmpp --solver_order 2 --num_steps 32 \\
+        --output_dir samples --num_samples 50000 --image_size 32 --num_classes 10 --batch_size 512
 Multi-GPU = replicas only: under `python -m torch.distributed.run --nproc-per-node N` every rank samples
 its own contiguous index range with its own noise seed and writes `<global index>.png`; there is no collective.
 """
@@ -46,15 +53,27 @@ CIFAR_MEAN = (0.49139968, 0.48215841, 0.44653091)      # generate.py:31-34 ("nee
 CIFAR_STD = (0.24703223, 0.24348513, 0.26158784)
 
 
+def _check_solver(solver, S_churn) -> None:
+    """the sampler choices that need nothing loaded: checked before any checkpoint or network is"""
+    if solver not in ("heun", "dpmpp"):
+        raise ValueError(f"generate: solver must be 'heun' or 'dpmpp', got {solver!r}")
+    if solver == "dpmpp" and float(S_churn) != 0.0:
+        raise ValueError(f"generate: --solver dpmpp is deterministic; --S_churn must be 0, got {S_churn} (stochastic "
+                         "sampling is --solver heun)")
+
+
 def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_classes, batch_size, num_workers=16,
              num_steps=32, *, in_channels=None, mean=None, std=None, seed=0, graph=True, model=None,
              network_dtype="f32x3", guide=None, guide_ckpt_path=None, guide_load_ema=False, guidance=1.0,
-             guidance_interval=None, S_churn=0.0, S_min=0.0, S_max=float("inf"), S_noise=1.0) -> None:
+             guidance_interval=None, S_churn=0.0, S_min=0.0, S_max=float("inf"), S_noise=1.0, solver="heun",
+             solver_order=2) -> None:
     from .callbacks import PreditionWriter
     from .datamodules import RandomNoiseDataModule
     from .edm import EDM
-    from .solvers import DeterministicSolver, StochasticSolver
+    from .solvers import DeterministicSolver, MultistepSolver, StochasticSolver
     from .trainer import Trainer
+
+    _check_solver(solver, S_churn)
 
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
@@ -72,7 +91,10 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
         guide.denoiser.set_eval_dtype(network_dtype)
         if float(guidance) == 1.0:
             print(f"[rank {rank}] guidance 1.0: the guide network is unused", flush=True)
-    if float(S_churn) != 0.0:       # (a negative or non-finite S_churn reaches the solver's validation)
+    if solver == "dpmpp":
+        model.solver = MultistepSolver(num_steps=num_steps, order=solver_order, guide=guide, guidance=guidance,
+                                       guidance_interval=guidance_interval)
+    elif float(S_churn) != 0.0:     # (a negative or non-finite S_churn reaches the solver's validation)
         model.solver = StochasticSolver(num_steps=num_steps, guide=guide, guidance=guidance,
                                         guidance_interval=guidance_interval, S_churn=S_churn, S_min=S_min,
                                         S_max=S_max, S_noise=S_noise, seed=seed + 1000003 * rank)
@@ -137,7 +159,14 @@ def main(argv=None):
     parser.add_argument("--S_min", type=float, default=0.0, help="churn only steps with S_min <= t_i (default 0)")
     parser.add_argument("--S_max", type=float, default=float("inf"), help="churn only steps with t_i <= S_max (default inf)")
     parser.add_argument("--S_noise", type=float, default=1.0, help="scale of the churn noise (default 1)")
+    # multistep sampling
+    parser.add_argument("--solver", choices=["heun", "dpmpp"], default="heun",
+                        help="heun (default): EDM's 2nd-order Heun, 2N-1 network evaluations; dpmpp: DPM-Solver++ "
+                             "multistep, N evaluations")
+    parser.add_argument("--solver_order", type=int, choices=[1, 2, 3], default=2,
+                        help="order of --solver dpmpp (default 2: DPM-Solver++(2M))")
     args = parser.parse_args(argv)
+    _check_solver(args.solver, args.S_churn)
     if args.guide_ckpt_path is not None and args.guide_config_name is not None:
         parser.error("--guide_ckpt_path and --guide_config_name are exclusive")
     from . import networks
@@ -162,7 +191,7 @@ def main(argv=None):
              std=args.std, seed=args.seed, graph=not args.no_graph, model=model, network_dtype=args.network_dtype,
              guide=guide, guide_ckpt_path=args.guide_ckpt_path, guide_load_ema=args.guide_load_ema,
              guidance=args.guidance, guidance_interval=args.guidance_interval, S_churn=args.S_churn, S_min=args.S_min,
-             S_max=args.S_max, S_noise=args.S_noise)
+             S_max=args.S_max, S_noise=args.S_noise, solver=args.solver, solver_order=args.solver_order)
 
 
 if __name__ == "__main__":

@@ -1629,6 +1629,41 @@ def heun_churn(x, c, rec, step):
     return x_hat
 
 
+def dpm_multistep(x, Dm, a, c0, c1=0.0, c2=0.0, Dg=None, w_dev=None, m1=None, m2=None, m_out=None):
+    """One DPM-Solver++ multistep update: m = Dg + w*(Dm - Dg) (w read on the device from the one-element tensor
+    w_dev) when Dg is given, else m = Dm; returns x_out = a*x + c0*m + c1*m1 + c2*m2 and writes m to m_out when given.
+    m1 / m2: the previous steps' m (None drops the term, so its coefficient must be 0).  Every tensor fp32, contiguous,
+    x's shape and device; m_out aliases no operand."""
+    _chk(x, f32, "x")
+    if x.numel() == 0:
+        raise ValueError("x: expected a non-empty tensor")
+    _chk(Dm, f32, "Dm", x.shape)
+    if (Dg is None) != (w_dev is None):
+        raise ValueError("dpm_multistep: Dg and w_dev go together (guided) or are both None")
+    if Dg is not None:
+        _chk(Dg, f32, "Dg", x.shape)
+        _guidance_weight(w_dev, x)
+    a, c0, c1, c2 = float(a), float(c0), float(c1), float(c2)
+    if not all(math.isfinite(v) for v in (a, c0, c1, c2)):
+        raise ValueError(f"dpm_multistep: coefficients must be finite, got {(a, c0, c1, c2)}")
+    if m1 is None and m2 is not None:
+        raise ValueError("dpm_multistep: m2 needs m1")
+    for t, c, nme in ((m1, c1, "m1"), (m2, c2, "m2")):
+        if t is None and c != 0.0:
+            raise ValueError(f"dpm_multistep: {nme} is None but its coefficient is {c}")
+    ins = [(t, nme) for t, nme in ((x, "x"), (Dm, "Dm"), (Dg, "Dg"), (m1, "m1"), (m2, "m2")) if t is not None]
+    for t, nme in ins[1:] + ([(m_out, "m_out")] if m_out is not None else []):
+        _chk(t, f32, nme, x.shape)
+        if t.device != x.device:
+            raise ValueError(f"{nme}: expected a tensor on {x.device}, got {t.device}")
+    if m_out is not None and any(t.data_ptr() == m_out.data_ptr() for t, _ in ins):
+        raise ValueError("m_out: must not alias an operand")
+    x_out = torch.empty_like(x)
+    _lib.call("edm_dpm_multistep", _p(x), _p(Dm), _p(Dg), _p(w_dev), _p(m1), _p(m2), a, c0, c1, c2, _p(x_out),
+              _p(m_out), x.numel(), _p(health(x.device)), _stream())
+    return x_out
+
+
 def scale_f32(x, s):
     _chk(x, f32, "x")
     y = torch.empty_like(x)

@@ -1,5 +1,6 @@
-"""2nd-order Heun samplers with the loop optionally captured in a hipGraph: the deterministic one of the reference
-(solvers.py:4-59) and the stochastic one of Karras et al. 2022 (Algorithm 2)."""
+"""ODE / SDE samplers with the loop optionally captured in a hipGraph: the 2nd-order Heun ones, deterministic as in the
+reference (solvers.py:4-59) and stochastic as Algorithm 2 of Karras et al. 2022, and the DPM-Solver++ multistep one
+(Lu et al. 2022) that spends one network evaluation per step."""
 import math
 import weakref
 from typing import NamedTuple
@@ -90,8 +91,9 @@ class DeterministicSolver:
         """what the subclass adds to the key of a captured solve"""
         return ()
 
-    def _solve_state(self, device):
-        """per-solve device tensors the loop reads (a captured entry owns its own), written for this solve; or None"""
+    def _solve_state(self, x0):
+        """per-solve device tensors the loop reads (a captured entry owns its own), written for this solve; or None.
+        x0: the solve's fp32 initial noise (its shape and device)"""
         return None
 
     def _write_solve_state(self, state) -> None:
@@ -152,7 +154,7 @@ class DeterministicSolver:
         if not graph:
             t_dev = self.t_steps.to(x0.device)
             w_dev = torch.full((1,), float(self.guidance), device=x0.device) if any(guided) else None
-            state = self._solve_state(x0.device)
+            state = self._solve_state(x0)
             return self._loop(model, x0, class_labels, t_dev, guided, w_dev, state).to(in_dtype)
         out = self._solve_graphed(model, x0, class_labels, guided).to(in_dtype)
         # the Heun kernels leave a bit in the device health word when the state went non-finite: a replay that ran
@@ -190,7 +192,7 @@ class DeterministicSolver:
             _runtime_env.require_graph_replay_safe("DeterministicSolver.solve(graph=True)")
             t_dev = self.t_steps.to(x0.device)
             w_dev = None if guide is None else torch.full((1,), float(self.guidance), device=x0.device)
-            state = self._solve_state(x0.device)
+            state = self._solve_state(x0)
             sx = x0.clone()
             sl = None if class_labels is None else class_labels.clone()
             side = torch.cuda.Stream()
@@ -320,12 +322,12 @@ class StochasticSolver(DeterministicSolver):
         steps = self._churn_steps()
         return (steps,) if any(s[0] for s in steps) else ()
 
-    def _solve_state(self, device):
+    def _solve_state(self, x0):
         steps = self._churn_steps()
         if not any(s[0] for s in steps):
             return None
-        return _ChurnState(ops.churn_record(self.seed, self.solve_index, device),
-                           torch.tensor([s[1] for s in steps], dtype=torch.float32, device=device), steps)
+        return _ChurnState(ops.churn_record(self.seed, self.solve_index, x0.device),
+                           torch.tensor([s[1] for s in steps], dtype=torch.float32, device=x0.device), steps)
 
     def _write_solve_state(self, state) -> None:
         if state is not None:
@@ -342,3 +344,106 @@ class StochasticSolver(DeterministicSolver):
         out = super().solve(model, x0, class_labels, graph)
         self.solve_index += 1
         return out
+
+
+class _MultistepState(NamedTuple):
+    hist: tuple             # the solve's history buffers: the mixed D of the last steps, a ring of `order` tensors
+    steps: tuple            # per step: (effective order k_i, a_i, c0_i, c1_i, c2_i) as host floats
+
+
+def _check_multistep(num_steps, order) -> None:
+    if isinstance(order, bool) or order not in (1, 2, 3):
+        raise ValueError(f"MultistepSolver: order must be 1, 2 or 3, got {order!r}")
+    if num_steps < 2:
+        raise ValueError(f"MultistepSolver: needs num_steps >= 2, got {num_steps}")
+
+
+class MultistepSolver(DeterministicSolver):
+    """DPM-Solver++ multistep (Lu et al. 2022) in data-prediction form on the Karras sigma table of DeterministicSolver:
+    one network evaluation per step, N in all, against Heun's 2N - 1.  With lambda_i = -log sigma_i, h_i = lambda_{i+1}
+    - lambda_i and m_i the D of step i (after guidance mixing), step i computes
+
+        x_{i+1} = a_i x_i + c0_i m_i + c1_i m_{i-1} + c2_i m_{i-2},   a_i = sigma_{i+1} / sigma_i,
+
+    at effective order k_i = min(order, i + 1): k = 1 is EDM's Euler step, k = 2 k-diffusion's dpmpp_2m, k = 3 the
+    third-order multistep update.  The last step is first order (sigma_N = 0 makes h infinite): x_N = m_{N-1}.  The
+    coefficients are computed once on the host (multistep_coefficients()); the update is one fused kernel per evaluation
+    (ops.dpm_multistep) that also writes m_i into a history buffer the solve owns (a captured entry owns its own).
+
+    Same arguments as DeterministicSolver, guidance included, plus keyword-only ``order`` (1, 2 or 3).  Guidance flags
+    (guided_evaluations()) are per evaluation, at sigma_0 ... sigma_{N-1}.  ``order`` is a plain attribute: a new order
+    captures a new graph."""
+
+    def __init__(self, num_steps: int = 18, sigma_min: float = 0.002, sigma_max: float = 80.0, rho: float = 7.0,
+                 dtype: str | None = None, *, order: int = 2, guide=None, guidance: float = 1.0,
+                 guidance_interval: tuple[float, float] | None = None):
+        _check_multistep(num_steps, order)
+        self.order = order
+        super().__init__(num_steps, sigma_min, sigma_max, rho, dtype, guide=guide, guidance=guidance,
+                         guidance_interval=guidance_interval)
+
+    def _steps(self) -> tuple:
+        """(k_i, a_i, c0_i, c1_i, c2_i) per step: the effective order and the fp32 coefficients as host floats"""
+        _check_multistep(self.num_steps, self.order)
+        N, order = self.num_steps, int(self.order)
+        sig = self.t_steps.double().tolist()                # fp64 from the fp32 table
+        lam = [-math.log(v) for v in sig[:N]]               # lambda_N = +inf
+        steps = []
+        for i in range(N):
+            if i == N - 1:                                  # h = inf: a = 0, e = -1
+                steps.append((1, 0.0, 1.0, 0.0, 0.0))
+                continue
+            k = min(order, i + 1)
+            h = lam[i + 1] - lam[i]
+            a = sig[i + 1] / sig[i]
+            e = math.expm1(-h)
+            if k == 1:
+                row = (a, -e, 0.0, 0.0)
+            elif k == 2:
+                r = (lam[i] - lam[i - 1]) / h
+                row = (a, -e * (1.0 + 0.5 / r), e * 0.5 / r, 0.0)
+            else:
+                # x_{i+1} = a x - e m_i + A D1 - B D2 with D1 = (1 + q) D1_0 - q D1_1, D2 = (D1_0 - D1_1) / (r0 + r1),
+                # D1_0 = (m_i - m_{i-1}) / r0 and D1_1 = (m_{i-1} - m_{i-2}) / r1, collected per m
+                r0 = (lam[i] - lam[i - 1]) / h
+                r1 = (lam[i - 1] - lam[i - 2]) / h
+                A, B = e / h + 1.0, (e + h) / (h * h) - 0.5
+                q, s = r0 / (r0 + r1), r0 + r1
+                row = (a,
+                       -e + A * (1.0 + q) / r0 - B / (r0 * s),
+                       -A * ((1.0 + q) / r0 + q / r1) + B * (1.0 / r0 + 1.0 / r1) / s,
+                       A * q / r1 - B / (r1 * s))
+            steps.append((k,) + row)
+        return tuple((k,) + tuple(torch.tensor(row, dtype=torch.float64).float().tolist())
+                     for k, *row in steps)
+
+    def multistep_coefficients(self) -> torch.Tensor:
+        """(N, 4) fp32 tensor of the rows (a_i, c0_i, c1_i, c2_i): computed in fp64 from the fp32 sigma table, rounded to
+        fp32.  The last row is (0, 1, 0, 0).  Host only; raises ValueError on an invalid order or num_steps."""
+        return torch.tensor([s[1:] for s in self._steps()], dtype=torch.float32)
+
+    def _evaluation_sigmas(self) -> list[float]:
+        """one evaluation per step, at sigma_0 ... sigma_{N-1}"""
+        _check_multistep(self.num_steps, self.order)
+        return self.t_steps.tolist()[:self.num_steps]
+
+    def _graph_key_extra(self) -> tuple:
+        # the coefficients are kernel arguments baked into a capture: a new order is a new graph
+        return ("multistep", self._steps())
+
+    def _solve_state(self, x0):
+        steps = self._steps()
+        L = int(self.order) if self.order > 1 else 0
+        return _MultistepState(tuple(torch.empty_like(x0) for _ in range(L)), steps)
+
+    def _loop(self, model, x0, class_labels, t_dev, guided, w_dev, state=None):
+        hist, N = state.hist, self.num_steps
+        L = len(hist)
+        x = ops.scale_f32(x0, self.t_steps[0].item())
+        for i, (k, a, c0, c1, c2) in enumerate(state.steps):
+            D = model(x, t_dev[i], class_labels).float().contiguous()
+            Dg = self.guide(x, t_dev[i], class_labels).float().contiguous() if guided[i] else None
+            x = ops.dpm_multistep(x, D, a, c0, c1, c2, Dg=Dg, w_dev=None if Dg is None else w_dev,
+                                  m1=hist[(i - 1) % L] if k >= 2 else None, m2=hist[(i - 2) % L] if k >= 3 else None,
+                                  m_out=hist[i % L] if L and i < N - 1 else None)
+        return x
