@@ -1,16 +1,21 @@
-"""Headline benchmark: CIFAR-10 32x32 EDM2 U-Net (35.6 M params) bf16 training images/sec on N MI355X,
-plus 32-step Heun sampler images/sec, roofline of the dominant kernel and a CPU baseline.
+"""Headline benchmark: CIFAR-10 32x32 EDM2 U-Net (35.6 M params) bf16 training images/sec on N MI355X;
+with --full also 32-step Heun sampler images/sec, roofline of the dominant kernel and a CPU baseline.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 A step = Diffuser -> Embedding -> Denoiser fwd -> sigma-weighted MSE -> backward -> bucketed gradient
 all-reduce over RCCL (overlapped with backward) -> fused Adam+EMA, on a synthetic device-resident batch
 (x = 0.5*randn(B,3,32,32), seed 42; conf/cifar10.yaml model, dropout 0.13, EMA 0.13, lr 0.02).
-Prints ONE JSON line on rank 0.  --dump-outputs DIR also writes what the timed paths computed, as DIR/<name>.npy
-(dump_sample): the loss of the last timed training step and the weights, EMA weights and Adam moments it left behind,
-and the images of each sampler leg's last timed solve -- seeded inputs, so two builds can be compared output for output.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline line; --full
+adds what takes runs of its own: the roofline (instrumented extra steps after the timed region, a vendor-GEMM comparison),
+the sampler legs (bf16, exact-fp32 and split-bf16 networks; one GPU only) and the CPU baseline.
+--dump-outputs DIR also writes what the timed paths computed, as DIR/<name>.npy (dump_sample): the loss of the last
+timed training step and the weights, EMA weights and Adam moments it left behind, and the images of each sampler leg's
+last timed solve -- seeded inputs, so two builds can be compared output for output.  Without --full the sampler legs
+run for those images alone: one replay of each captured solve, untimed, after the extra training steps whose weights
+they evaluate.
 """
 import argparse
 import json
@@ -203,9 +208,10 @@ def timed_region(args, step, world, device, marks=None, last=None):
     return dt
 
 
-def train_bench(args, rank, world, device, dumps=None):
+def train_bench(args, rank, world, device, dumps=None, extra_steps=True):
+    """extra_steps: take the eager steps after the timed region (instrumented for the roofline with --full, see
+    after_timed_region); without them the returned roof is None"""
     import tinyedm
-    from tinyedm_amd import ops
     from tinyedm_amd.ddp import GradReducer
     from tinyedm_amd.ema import EMAOptimizer
 
@@ -401,14 +407,21 @@ def train_bench(args, rank, world, device, dumps=None):
         dumps.update({"train_loss": dump_sample(loss.reshape(1)), "train_weights": dump_sample(base.arena.theta),
                       "train_ema_weights": dump_sample(opt.ema_arena), "train_adam_m": dump_sample(base.m),
                       "train_adam_v": dump_sample(base.v)})
+    roof = after_timed_region(args, rank, eager_step, instrument=args.full) if extra_steps else None
+    return model, B * world * args.steps / dt, dt / args.steps * 1e3, final_loss, roof, launch_info
 
-    # ---- roofline of the dominant kernel (3x3 implicit-GEMM conv): extra, instrumented EAGER steps AFTER the
-    # timed region: HIP events around every launch on the launch stream; algorithmic FLOPs from the shapes.
-    # Every rank runs the extra steps (they contain the gradient all-reduce); only rank 0 instruments them.  Kernels run
-    # back to back on one stream (the weight-gradient side stream is off by default since round 2); when it is enabled
-    # (EDM_WGRAD_STREAM=1) a second instrumented step records the per-kernel durations under that overlap too.
+
+def after_timed_region(args, rank, eager_step, instrument):
+    """Extra EAGER steps AFTER the timed region.  instrument (--full): the roofline of the dominant kernel (3x3
+    implicit-GEMM conv) from them -- HIP events around every launch on the launch stream; algorithmic FLOPs from the
+    shapes -- returned as per-kernel figures on rank 0 (None elsewhere, and without instrument).  Without instrument the
+    same steps run bare: the sampler legs evaluate the weights they leave behind.
+    Every rank runs the extra steps (they contain the gradient all-reduce); only rank 0 instruments them.  Kernels run
+    back to back on one stream first; when the weight-gradient side stream is enabled (EDM_WGRAD_STREAM, on by default)
+    a second round of steps records the per-kernel durations under that overlap too."""
     from tinyedm_amd import networks as _nets
-    roof = None
+    from tinyedm_amd import ops
+    instrument = instrument and rank == 0
     roofs = {}
     INSTR = 5          # instrumented steps per mode, behind 2 uninstrumented ones: a single step right after the
     nstep = [args.warmup + args.steps]   # synchronisation ran the big kernels 8 % slower than their steady state (clock ramp)
@@ -417,33 +430,35 @@ def train_bench(args, rank, world, device, dumps=None):
         _nets.WGRAD_STREAM = saved and overlapped
         for _ in range(2):
             eager_step(nstep[0]); nstep[0] += 1
-        if rank == 0:
+        if instrument:
             ops.PROFILE = {}
         for _ in range(INSTR):
             eager_step(nstep[0]); nstep[0] += 1
         torch.cuda.synchronize()
         _nets.WGRAD_STREAM = saved
-        if rank == 0:
+        if instrument:
             roofs[overlapped], ops.PROFILE = ops.PROFILE, None
-    if rank == 0:
-        roof = {}
-        for name, recs in roofs[False].items():           # per-step figures: sums over the INSTR steps / INSTR
-            ms = sum(s.elapsed_time(e) for s, e, _, _ in recs) / INSTR
-            roof[name] = {"launches": len(recs) // INSTR, "ms": ms, "gflop": sum(f for _, _, f, _ in recs) / 1e9 / INSTR,
-                          "gbytes": sum(b for _, _, _, b in recs) / 1e9 / INSTR}
-        for name, recs in roofs.get(True, {}).items():
-            if name in roof:
-                roof[name]["ms_overlapped"] = sum(s.elapsed_time(e) for s, e, _, _ in recs) / INSTR
-    return model, B * world * args.steps / dt, dt / args.steps * 1e3, final_loss, roof, launch_info
+    if not instrument:
+        return None
+    roof = {}
+    for name, recs in roofs[False].items():           # per-step figures: sums over the INSTR steps / INSTR
+        ms = sum(s.elapsed_time(e) for s, e, _, _ in recs) / INSTR
+        roof[name] = {"launches": len(recs) // INSTR, "ms": ms, "gflop": sum(f for _, _, f, _ in recs) / 1e9 / INSTR,
+                      "gbytes": sum(b for _, _, _, b in recs) / 1e9 / INSTR}
+    for name, recs in roofs.get(True, {}).items():
+        if name in roof:
+            roof[name]["ms_overlapped"] = sum(s.elapsed_time(e) for s, e, _, _ in recs) / INSTR
+    return roof
 
 
 F32_MFMA_PEAK_TFLOPS = 157.3   # v_mfma_f32_32x32x2_f32, MI355X_MICROARCH.md chip table (= the fp32 vector rate)
 
 
-def sampler_bench(args, model, device, network_dtype="bf16", dumps=None):
+def sampler_bench(args, model, device, network_dtype="bf16", dumps=None, timed=True):
     """32-step Heun solve (63 network evaluations) of the CIFAR-10 net, hipGraph-captured.  network_dtype "bf16": the
     training path's kernels; "f32": the reference-precision evaluation (exact-fp32 kernels, csrc/eval_f32.hip) -- the
-    reference itself samples in fp32 (generate.py:39-44)."""
+    reference itself samples in fp32 (generate.py:39-44).  timed=False (a plain run's --dump-outputs): the images of the
+    first replay of the captured solve -- the same graph on the same x0 as every timed replay -- and no figures (None)."""
     import tinyedm
     from tinyedm_amd import _runtime_env as _RE
     model.eval()
@@ -457,19 +472,22 @@ def sampler_bench(args, model, device, network_dtype="bf16", dumps=None):
     g = torch.Generator().manual_seed(7)
     x0 = torch.randn(B, 3, 32, 32, generator=g).to(device)
     note(f"sampler ({network_dtype} network): warm-up" + (" + hipGraph capture" if graph else ""))
-    solver.solve(model, x0, None, graph=graph)         # capture + first replay
+    out = solver.solve(model, x0, None, graph=graph)         # capture + first replay
     torch.cuda.synchronize()
-    note(f"sampler ({network_dtype} network): timing")
-    t0 = time.perf_counter()
-    for _ in range(iters):
-        out = solver.solve(model, x0, None, graph=graph)
-    torch.cuda.synchronize()
-    dt = (time.perf_counter() - t0) / iters
+    if timed:
+        note(f"sampler ({network_dtype} network): timing")
+        t0 = time.perf_counter()
+        for _ in range(iters):
+            out = solver.solve(model, x0, None, graph=graph)
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) / iters
     if not bool(torch.isfinite(out).all()):
         raise RuntimeError("bench: the sampler produced non-finite images")
     if dumps is not None:
         dumps[f"sampler_{network_dtype}_images"] = dump_sample(out)
     model.denoiser.set_eval_dtype("bf16")
+    if not timed:
+        return None
     peak = F32_MFMA_PEAK_TFLOPS if f32 else MFMA_PEAK_TFLOPS
     passes = 3 if split else 1      # split-bf16: every conv product is three bf16 MFMA passes (hi.w_hi + hi.w_lo + lo.w_hi)
     return {"img_per_s": B / dt, "batch": B, "heun_steps": 32, "nfe": 63, "ms_per_solve": dt * 1e3,
@@ -553,7 +571,11 @@ def main():
     ap.add_argument("--cpu-batch", type=int, default=8)
     ap.add_argument("--cpu-steps", type=int, default=20, help="timed CPU-oracle steps (~0.5 s each on 16 threads)")
     ap.add_argument("--dump-outputs", metavar="DIR",
-                    help="write what the timed paths computed (last timed step / solve) to DIR/<name>.npy, float32, at most 64 MB")
+                    help="write what the timed paths computed (last timed step / solve) to DIR/<name>.npy, float32, at most 64 MB; "
+                         "runs the sampler legs for their images (untimed without --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: roofline of the dominant kernel (instrumented extra steps, "
+                         "vendor GEMM), the sampler legs and the CPU baseline (--no-sampler / --no-cpu-baseline drop legs)")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -597,19 +619,14 @@ def main():
     assert world == args.gpus, f"--gpus {args.gpus} but WORLD_SIZE={world}"
 
     dumps = {} if args.dump_outputs and rank == 0 else None
-    model, ips, ms, final_loss, roof, launch_info = train_bench(args, rank, world, device, dumps)
+    # the sampler legs ride on the single-GPU line only (the N>1 lines are the training scaling series; hipGraph capture
+    # beside a live RCCL communicator is avoided).  Without --full they run untimed for their dumped images alone, after
+    # the extra training steps whose weights they evaluate.
+    sampler = world == 1 and not args.no_sampler and (args.full or dumps is not None)
+    model, ips, ms, final_loss, roof, launch_info = train_bench(args, rank, world, device, dumps,
+                                                                extra_steps=args.full or sampler)
     out = None
     if rank == 0:
-        # dominant kernel: k_conv3x3_v6<5,0,4> (3x3 implicit GEMM of the 32x32 layers: forward convs, with the modulation
-        # epilogue on the first conv of each block, and plain dgrads; the two backward-epilogue instantiations
-        # <5,1>/<5,2> are reported beside it in per_kernel as ..._v6_modbwd / ..._v6_silubwd).  per_kernel keys name the
-        # kernel that ran (ops.V46: _v6, or _v4 under EDM_V4_MFMA16=0)
-        from tinyedm_amd import ops as _ops
-        mfma16 = _ops.V46 == "_v6"
-        conv = roof.get("conv3x3_igemm" + _ops.V46, {"launches": 0, "ms": 0.0, "gflop": 0.0, "gbytes": 0.0})
-        achieved = conv["gflop"] / conv["ms"] if conv["ms"] > 0 else 0.0          # GFLOP/ms == TFLOP/s
-        kname = "k_conv3x3_v6" if mfma16 else "k_conv3x3_v4"
-        traffic = pmc_traffic(kname)
         out = {
             "metric": "train imgs/sec CIFAR-10 32x32 bf16",
             "value": round(ips, 2), "unit": "img/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -622,63 +639,76 @@ def main():
                        **launch_info,
                        "collective": ("rccl all-reduce (forced, 1 rank)" if forced else "rccl bucketed all-reduce")
                        if (world > 1 or forced) else "none"},
-            "roofline": {
-                "bound": "mfma", "kernel": kname + "<5,0,4> (3x3 implicit-GEMM conv of the 32x32 layers: forward, incl. fused "
-                                                   "modulation epilogue, and plain dgrad; "
-                                                   + ("v_mfma_f32_16x16x32_bf16" if mfma16 else "v_mfma_f32_32x32x16_bf16") + ")",
-                "achieved": round(achieved, 2), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                "frac": round(achieved / MFMA_PEAK_TFLOPS, 4), "traffic": traffic,
-                "traffic_source": pmc_source(),
-                "traffic_unit": "GB of HBM traffic per launch (FETCH_SIZE x2 + WRITE_SIZE, separate rocprofv3 --pmc "
-                                "passes, newest profiles/r*_pmc_hbm.json)",
-                "algorithmic_gbytes_per_launch": round(conv["gbytes"] / max(1, conv["launches"]), 4),
-                # the vendor GEMM (torch.matmul -> hipBLASLt) on the conv-as-GEMM shape of this kernel, M = 131072 pixels,
-                # N = 256, K = 2304, plain row-major operands with no im2col work -- measured in THIS run
-                "library_gemm_tflops_same_shape": vendor_gemm_tflops(device),
-                "achieved_overlapped": round(conv["gflop"] / conv["ms_overlapped"], 2) if conv.get("ms_overlapped") else None,
-                "launches_per_step": conv["launches"],
-                "avg_launch_ms": round(conv["ms"] / max(1, conv["launches"]), 4),
-                "algorithmic_gflop_per_step": round(conv["gflop"], 1),
-                # what the matrix pipe SUSTAINS on this power-limited part (not the contract's `peak`, kept above): a bare
-                # MFMA + LDS loop of the same instruction on all 256 CUs holds 1.80 GHz x 88 % = 1 660 TFLOP/s
-                # (tools/mfma_shape); inside this kernel's main loop the chip runs 1.845 GHz with the pipe 81 % busy
-                # (tools/v6_timeline.py, profiles/r04_v6_timeline_clock.txt) -- clock x occupancy is what the power cap fixes
-                "sustained_mfma_tflops": SUSTAINED_MFMA_TFLOPS,
-                "frac_of_sustained": round(achieved / SUSTAINED_MFMA_TFLOPS, 4),
-                "whole_step_mfma_frac": round(ips / world * TRAIN_GFLOP_PER_IMG / 1e3 / MFMA_PEAK_TFLOPS, 4),
-                "whole_step_hbm_frac": round(ips / world * 108.6e6 / 1e9 / HBM_PEAK_GBS, 4),
-                # BASELINE.json's literal "HBM-bound 3x3-conv roofline": 3x3-conv activation bytes only (59.7 MB per
-                # training image) over 8 TB/s; 70 % of it would need 7 PFLOP/s of bf16 MFMA (not reachable)
-                "northstar_hbm3x3_frac": round(ips / world * 59.7e6 / 1e9 / HBM_PEAK_GBS, 4),
-                # the other chip-filling MFMA kernel of the step: the grouped stream-K weight gradient (conv_wgrad3.hip)
-                # avg_launch_ms / achieved / frac: the k_wgrad3 LAUNCH alone (events recorded inside the grouped entry point,
-                # include/tinyedm_hip_diag.h edm_wgrad3_probe) -- what the rocprofv3 traces in profiles/ show for the kernel;
-                # call_ms: the whole edm_wgrad3_group call (launch-table upload + k_wgrad3 + k_wgrad3_finish), the figure
-                # rounds 2-5 reported as the kernel's
-                "wgrad3": (lambda w, c: {"kernel": f"k_wgrad3<1> (3x3 weight gradients, {w['launches']} grouped launches per step)",
-                                         "achieved": round(w["gflop"] / w["ms"], 2) if w["ms"] else 0.0,
-                                         "frac": round(w["gflop"] / w["ms"] / MFMA_PEAK_TFLOPS, 4) if w["ms"] else 0.0,
-                                         "avg_launch_ms": round(w["ms"] / max(1, w["launches"]), 4),
-                                         "call_ms_incl_table_upload_and_finish": round(c["ms"] / max(1, c["launches"]), 4),
-                                         "algorithmic_gbytes_per_launch": round(w["gbytes"] / max(1, w["launches"]), 4),
-                                         "traffic": pmc_traffic("k_wgrad3")})(
-                    roof.get("conv3x3_wgrad_kernel", roof.get("conv3x3_wgrad", {"launches": 0, "ms": 0.0, "gflop": 0.0, "gbytes": 0.0})),
-                    roof.get("conv3x3_wgrad", {"launches": 0, "ms": 0.0, "gflop": 0.0, "gbytes": 0.0})),
-                "per_kernel": {k: {kk: round(vv, 3) for kk, vv in v.items()} for k, v in roof.items()},
-            },
         }
-        # sampler + CPU baseline ride on the single-GPU line only (the N>1 lines are the training scaling series;
-        # hipGraph capture beside a live RCCL communicator is avoided)
-        if not args.no_sampler and world == 1:
-            out["sampler"] = sampler_bench(args, model, device, dumps=dumps)
-            if not args.no_sampler_fp32:
-                # the reference-faithful figure: the reference samples in fp32; priced against the f32-input MFMA peak
-                out["sampler_fp32"] = sampler_bench(args, model, device, "f32", dumps)
-                # the same precision class (2^-17 per operand; 32-step trajectory 2e-6 from the exact path) on the bf16 kernels:
-                # split-bf16, three MFMA passes per product (tinyedm_amd/networks.py _conv_f32)
-                out["sampler_fp32_split"] = sampler_bench(args, model, device, "f32x3", dumps)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(args)
+    if rank == 0 and roof is not None:
+        # dominant kernel: k_conv3x3_v6<5,0,4> (3x3 implicit GEMM of the 32x32 layers: forward convs, with the modulation
+        # epilogue on the first conv of each block, and plain dgrads; the two backward-epilogue instantiations
+        # <5,1>/<5,2> are reported beside it in per_kernel as ..._v6_modbwd / ..._v6_silubwd).  per_kernel keys name the
+        # kernel that ran (ops.V46: _v6, or _v4 under EDM_V4_MFMA16=0)
+        from tinyedm_amd import ops as _ops
+        mfma16 = _ops.V46 == "_v6"
+        conv = roof.get("conv3x3_igemm" + _ops.V46, {"launches": 0, "ms": 0.0, "gflop": 0.0, "gbytes": 0.0})
+        achieved = conv["gflop"] / conv["ms"] if conv["ms"] > 0 else 0.0          # GFLOP/ms == TFLOP/s
+        kname = "k_conv3x3_v6" if mfma16 else "k_conv3x3_v4"
+        traffic = pmc_traffic(kname)
+        out["roofline"] = {
+            "bound": "mfma", "kernel": kname + "<5,0,4> (3x3 implicit-GEMM conv of the 32x32 layers: forward, incl. fused "
+                                               "modulation epilogue, and plain dgrad; "
+                                               + ("v_mfma_f32_16x16x32_bf16" if mfma16 else "v_mfma_f32_32x32x16_bf16") + ")",
+            "achieved": round(achieved, 2), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+            "frac": round(achieved / MFMA_PEAK_TFLOPS, 4), "traffic": traffic,
+            "traffic_source": pmc_source(),
+            "traffic_unit": "GB of HBM traffic per launch (FETCH_SIZE x2 + WRITE_SIZE, separate rocprofv3 --pmc "
+                            "passes, newest profiles/r*_pmc_hbm.json)",
+            "algorithmic_gbytes_per_launch": round(conv["gbytes"] / max(1, conv["launches"]), 4),
+            # the vendor GEMM (torch.matmul -> hipBLASLt) on the conv-as-GEMM shape of this kernel, M = 131072 pixels,
+            # N = 256, K = 2304, plain row-major operands with no im2col work -- measured in THIS run
+            "library_gemm_tflops_same_shape": vendor_gemm_tflops(device),
+            "achieved_overlapped": round(conv["gflop"] / conv["ms_overlapped"], 2) if conv.get("ms_overlapped") else None,
+            "launches_per_step": conv["launches"],
+            "avg_launch_ms": round(conv["ms"] / max(1, conv["launches"]), 4),
+            "algorithmic_gflop_per_step": round(conv["gflop"], 1),
+            # what the matrix pipe SUSTAINS on this power-limited part (not the contract's `peak`, kept above): a bare
+            # MFMA + LDS loop of the same instruction on all 256 CUs holds 1.80 GHz x 88 % = 1 660 TFLOP/s
+            # (tools/mfma_shape); inside this kernel's main loop the chip runs 1.845 GHz with the pipe 81 % busy
+            # (tools/v6_timeline.py, profiles/r04_v6_timeline_clock.txt) -- clock x occupancy is what the power cap fixes
+            "sustained_mfma_tflops": SUSTAINED_MFMA_TFLOPS,
+            "frac_of_sustained": round(achieved / SUSTAINED_MFMA_TFLOPS, 4),
+            "whole_step_mfma_frac": round(ips / world * TRAIN_GFLOP_PER_IMG / 1e3 / MFMA_PEAK_TFLOPS, 4),
+            "whole_step_hbm_frac": round(ips / world * 108.6e6 / 1e9 / HBM_PEAK_GBS, 4),
+            # BASELINE.json's literal "HBM-bound 3x3-conv roofline": 3x3-conv activation bytes only (59.7 MB per
+            # training image) over 8 TB/s; 70 % of it would need 7 PFLOP/s of bf16 MFMA (not reachable)
+            "northstar_hbm3x3_frac": round(ips / world * 59.7e6 / 1e9 / HBM_PEAK_GBS, 4),
+            # the other chip-filling MFMA kernel of the step: the grouped stream-K weight gradient (conv_wgrad3.hip)
+            # avg_launch_ms / achieved / frac: the k_wgrad3 LAUNCH alone (events recorded inside the grouped entry point,
+            # include/tinyedm_hip_diag.h edm_wgrad3_probe) -- what the rocprofv3 traces in profiles/ show for the kernel;
+            # call_ms: the whole edm_wgrad3_group call (launch-table upload + k_wgrad3 + k_wgrad3_finish), the figure
+            # rounds 2-5 reported as the kernel's
+            "wgrad3": (lambda w, c: {"kernel": f"k_wgrad3<1> (3x3 weight gradients, {w['launches']} grouped launches per step)",
+                                     "achieved": round(w["gflop"] / w["ms"], 2) if w["ms"] else 0.0,
+                                     "frac": round(w["gflop"] / w["ms"] / MFMA_PEAK_TFLOPS, 4) if w["ms"] else 0.0,
+                                     "avg_launch_ms": round(w["ms"] / max(1, w["launches"]), 4),
+                                     "call_ms_incl_table_upload_and_finish": round(c["ms"] / max(1, c["launches"]), 4),
+                                     "algorithmic_gbytes_per_launch": round(w["gbytes"] / max(1, w["launches"]), 4),
+                                     "traffic": pmc_traffic("k_wgrad3")})(
+                roof.get("conv3x3_wgrad_kernel", roof.get("conv3x3_wgrad", {"launches": 0, "ms": 0.0, "gflop": 0.0, "gbytes": 0.0})),
+                roof.get("conv3x3_wgrad", {"launches": 0, "ms": 0.0, "gflop": 0.0, "gbytes": 0.0})),
+            "per_kernel": {k: {kk: round(vv, 3) for kk, vv in v.items()} for k, v in roof.items()},
+        }
+    if sampler:
+        legs = {"sampler": "bf16"}
+        if not args.no_sampler_fp32:
+            # the reference-faithful figure: the reference samples in fp32; priced against the f32-input MFMA peak
+            legs["sampler_fp32"] = "f32"
+            # the same precision class (2^-17 per operand; 32-step trajectory 2e-6 from the exact path) on the bf16 kernels:
+            # split-bf16, three MFMA passes per product (tinyedm_amd/networks.py _conv_f32)
+            legs["sampler_fp32_split"] = "f32x3"
+        for key, network_dtype in legs.items():
+            figures = sampler_bench(args, model, device, network_dtype, dumps, timed=args.full)
+            if figures is not None:
+                out[key] = figures
+    if world == 1 and args.full and not args.no_cpu_baseline:          # (single-GPU line only, as the sampler legs)
+        out["cpu_baseline"] = cpu_baseline(args)
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()

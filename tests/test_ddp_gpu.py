@@ -129,8 +129,8 @@ def test_two_rank_hip_backward_reduces_to_the_mean_of_shard_gradients():
 
 
 def test_bench_runs_with_two_ranks_on_one_gpu():
-    """bench.py's N>1 path end to end (rank set-up, barriers, max-over-ranks timing, the instrumented steps on every
-    rank, one JSON line from rank 0), launched exactly as the driver does but with both ranks on cuda:0 over gloo."""
+    """bench.py's N>1 path end to end (rank set-up, barriers, max-over-ranks timing, with --full the instrumented steps on
+    every rank, one JSON line from rank 0), launched exactly as the driver does but with both ranks on cuda:0 over gloo."""
     import json
     import subprocess
     import sys
@@ -140,7 +140,7 @@ def test_bench_runs_with_two_ranks_on_one_gpu():
     env = dict(os.environ, EDM_BENCH_ONE_DEVICE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "8"]
+           "--batch", "8", "--full"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

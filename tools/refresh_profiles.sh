@@ -11,8 +11,8 @@ cd /tmp && export TMPDIR=/tmp
 export DEBUG_CLR_GRAPH_PACKET_CAPTURE=0
 O=$R/gpurun_out
 mkdir -p $O
-# 1. the default bench line (sampler legs and CPU baseline included)
-timeout -k 10 600 python3 $R/bench.py > $O/${RD}_bench_unprofiled.json 2> $O/${RD}_bench_default.err
+# 1. the whole bench line (--full: roofline, sampler legs and CPU baseline included)
+timeout -k 10 600 python3 $R/bench.py --full > $O/${RD}_bench_unprofiled.json 2> $O/${RD}_bench_default.err
 # 2. kernel trace of the captured training step
 rm -rf $O/prof_${RD}b
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_${RD}b -- python3 $R/bench.py --steps 20 --warmup 5 --no-sampler --no-cpu-baseline --step-launch graph > $O/${RD}_bench_profiled.json 2> $O/${RD}_bench_profiled.log
