@@ -366,6 +366,10 @@ int edm_nhwc_bf16_to_nchw(const void* x, float* y, int B, int C, int HW, edm_str
 
 /* ---------------------------------------------------------------- fp32 linears + embedding (networks.py:58-60, 121-178) */
 int edm_linear_fwd(const float* X, const float* W, float* Y, int M, int N, int K, edm_stream_t stream);
+/* launch plan of the GEMM C[M,N] (=|+=) A[M,K] B[K,N] the three entry points run (fwd (M,N,K) -> GEMM (M,N,K), dgrad
+ * (M,N,K) -> (M,K,N), wgrad (M,N,K) -> (N,K,M)): tile_rows 32 (32x64 tile) or 64 (64x64), splits = K shares added with
+ * atomics (C is cleared first when splits > 1 and accumulate == 0).  Host logic only; the launches follow it. */
+int edm_linear_plan(int M, int N, int K, int accumulate, int* tile_rows, int* splits);
 int edm_linear_dgrad(const float* dY, const float* W, float* dX, int M, int N, int K, int accumulate,
                      edm_stream_t stream);
 int edm_linear_wgrad(const float* dY, const float* X, float* dW, int M, int N, int K, int accumulate,

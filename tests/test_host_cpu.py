@@ -393,3 +393,37 @@ def test_wgrad3_plan_splits_k_only_where_team_members_would_idle():
     from tinyedm_amd import _lib
     assert ops.W3_MAX_LAYERS == _lib.call("edm_wgrad3_max_layers") == 48
     assert ops.wgrad3_plan_ksplit([(128, 8, 8, 256, 256)] * 48) == [1] * 48
+
+
+def test_linear_plan_puts_the_named_shapes_on_their_branches():
+    """linear.hip edm_linear_plan (host logic, the plan sgemm() launches): the fp32 Linear GEMMs of the CIFAR-10 and ImageNet
+    steps reach the 32 x 64 tile, the 64 x 64 tile and split-K as tests/test_fp32_sidepath_gpu.py expects them to."""
+    from tinyedm_amd import networks, ops
+    assert ops.linear_plan("fwd", 5, 256, 64) == (32, 1)
+    assert ops.linear_plan("wgrad", 128, 256, 64) == (32, 1)                 # sigma-embed Linear wgrad, batch 128
+    # CIFAR-10 batched embed Linear: 21 blocks x 256 = 5 376 columns, E = 256, batch 128 (sampler batch 512)
+    assert ops.linear_plan("fwd", 128, 5376, 256) == (32, 1)
+    assert ops.linear_plan("dgrad", 128, 5376, 256, 1) == (32, 21)           # GEMM (128, 256, K = 5 376): 21 K shares
+    assert ops.linear_plan("wgrad", 128, 5376, 256) == (64, 1)               # GEMM (5 376, 256, K = 128)
+    assert ops.linear_plan("fwd", 512, 5376, 256) == (64, 1)
+    # ImageNet config: 36 blocks, sum C = 17 472, E = 768
+    sum_c = sum(networks.get_encoder_out_channels()) + sum(networks.get_decoder_out_channels())
+    assert sum_c == 17472
+    assert ops.linear_plan("fwd", 176, sum_c, 768) == (64, 1)
+    assert ops.linear_plan("dgrad", 176, sum_c, 768, 1) == (32, 15)
+    assert ops.linear_plan("wgrad", 176, sum_c, 768) == (64, 1)
+    # split-K with accumulate == 0 (the memset form): wgrad once the batch reaches 1 024; on the 64 x 64 tile too
+    assert ops.linear_plan("wgrad", 1024, 256, 64) == (32, 4)
+    assert ops.linear_plan("fwd", 512, 2048, 1024) == (64, 4)
+    # split-K whose K is no multiple of the 32-wide chunk, and 32 shares of which the last three are empty
+    assert ops.linear_plan("dgrad", 64, 1025, 128, 1) == (32, 4)
+    assert ops.linear_plan("dgrad", 33, 3001, 65, 1) == (32, 11)
+    assert ops.linear_plan("dgrad", 32, 8200, 64, 1) == (32, 32)
+    assert ops.linear_plan("wgrad", 8200, 64, 32) == (32, 32)
+    # below K = 1 024, or with enough tiles, nothing splits; accumulate never changes the plan
+    assert ops.linear_plan("fwd", 64, 64, 1023) == (32, 1)
+    assert ops.linear_plan("fwd", 2048, 1024, 4096) == (64, 1)
+    assert ops.linear_plan("dgrad", 128, 5376, 256, 0) == ops.linear_plan("dgrad", 128, 5376, 256, 1)
+    from tinyedm_amd import _lib
+    with pytest.raises(_lib.HipKernelError):
+        ops.linear_plan("fwd", 0, 1, 1)

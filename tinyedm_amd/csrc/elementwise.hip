@@ -836,8 +836,11 @@ __device__ __forceinline__ void skip_gate_fwd_body(const bf16* __restrict__ skip
   for (int c = threadIdx.x; c < C; c += blockDim.x) mean[(long)b * C + c] = m[c];
   if (threadIdx.x == 0) m[C] = 1.0f;
   __syncthreads();
+  // rows of W1 per WHOLE wave: skip_gate_threads() is a multiple of C/8, not of 64 (1008 threads for C = 192, 384, 576),
+  // and a trailing partial wave would sum its rows without the terms of its missing lanes, shuffle from them in wave_sum,
+  // and race wave 0, which owns the same rows (nw counts whole waves only), for z1save and h
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  for (int r = wave; r < R; r += nw) {
+  for (int r = wave < nw ? wave : R; r < R; r += nw) {
     float s = 0.f;
     for (int c = lane; c <= C; c += 64) s += W1[(long)r * (C + 1) + c] * m[c];
     s = wave_sum(s);
@@ -937,7 +940,7 @@ __device__ __forceinline__ void skip_gate_bwd_body(const bf16* __restrict__ gcat
   for (int r = threadIdx.x; r < R; r += blockDim.x) wsb[C + R + r] = mp_silu_f(z1save[(long)b * R + r]);
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  for (int r = wave; r < R; r += nw) {
+  for (int r = wave < nw ? wave : R; r < R; r += nw) {     // whole waves only (see skip_gate_fwd_body)
     float s = 0.f;
     for (int c = lane; c < C; c += 64) s += W2[(long)c * R + r] * gz2[c];
     s = wave_sum(s);

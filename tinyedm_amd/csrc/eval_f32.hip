@@ -523,8 +523,10 @@ __global__ __launch_bounds__(1024) void k_skip_gate_f32(const float* __restrict_
   }
   if (threadIdx.x == 0) m[C] = 1.0f;
   __syncthreads();
+  // whole waves only: the block is a multiple of C/4, not of 64 (1008 threads for C = 192, 576); a trailing partial wave
+  // would sum its rows without its missing lanes' terms and race wave 0, which owns the same rows, for h
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  for (int r = wave; r < R; r += nw) {
+  for (int r = wave < nw ? wave : R; r < R; r += nw) {
     float s = 0.f;
     for (int c = lane; c <= C; c += 64) s += W1[(long)r * (C + 1) + c] * m[c];
     s = wave_sum(s);

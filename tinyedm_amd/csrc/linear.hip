@@ -4,6 +4,29 @@
 // f32-input matrix instruction, with arbitrary operand strides, covers forward, dgrad and wgrad.
 #include "common.h"
 
+// Launch plan of the GEMM C[M,N] (=|+=) A[M,K] B[K,N] behind the three Linear entry points (edm_linear_fwd (M,N,K) runs
+// the GEMM (M,N,K), edm_linear_dgrad (M,N,K) runs (M,K,N), edm_linear_wgrad (M,N,K) runs (N,K,M)): tile_rows = 64 for the
+// 64x64 tile (four waves) when that still gives every CU a workgroup, 32 for the 32x64 tile (two waves) of the small
+// problems; splits = K shares over gridDim.z, added with atomics (long K, few tiles: split to fill the chip).  accumulate
+// does not change the plan; with splits > 1 and accumulate == 0 the launch clears C first.  sgemm() launches what this says.
+extern "C" int edm_linear_plan(int M, int N, int K, int accumulate, int* tile_rows, int* splits) {
+  EDM_REQUIRE(M > 0 && N > 0 && K > 0 && tile_rows && splits, "linear_plan: bad args");
+  (void)accumulate;
+  const long t64 = (long)((N + 63) / 64) * ((M + 63) / 64);
+  const bool big = t64 >= 256;
+  const long tiles = big ? t64 : (long)((N + 63) / 64) * ((M + 31) / 32);
+  int sp_out = 1;
+  if (K >= 1024 && tiles < 512) {
+    long sp = K / 256, cap = (1024 + tiles - 1) / tiles;
+    if (sp > cap) sp = cap;
+    if (sp > 32) sp = 32;
+    sp_out = (int)(sp < 1 ? 1 : sp);
+  }
+  *tile_rows = big ? 64 : 32;
+  *splits = sp_out;
+  return EDM_OK;
+}
+
 namespace {
 
 // C[m,n] (=|+=) alpha * sum_k A[m*asm + k*ask] * B[k*bsk + n*bsn]
@@ -95,19 +118,11 @@ __global__ __launch_bounds__(64 * WM * WN) void k_sgemm_mfma(const float* __rest
 
 int sgemm(const float* A, long asm_, long ask, const float* B, long bsk, long bsn, float* C, long csm, long csn, int M,
           int N, int K, float alpha, int accumulate, hipStream_t st) {
-  // tile: 64x64 (four waves) when that still gives every CU a workgroup, 32x64 (two waves) for the small problems
-  const long t64 = (long)((N + 63) / 64) * ((M + 63) / 64);
-  const bool big = t64 >= 256;
-  const long tiles = big ? t64 : (long)((N + 63) / 64) * ((M + 31) / 32);
-  int splits = 1;
-  if (K >= 1024 && tiles < 512 && csn == 1 && csm == N) {  // long-K, few tiles: split K to fill the chip
-    long sp = K / 256, cap = (1024 + tiles - 1) / tiles;
-    if (sp > cap) sp = cap;
-    if (sp > 32) sp = 32;
-    splits = (int)(sp < 1 ? 1 : sp);
-    if (splits > 1 && !accumulate) (void)hipMemsetAsync(C, 0, (size_t)M * N * sizeof(float), st);
-  }
-  if (big)
+  int rows = 32, splits = 1;
+  edm_linear_plan(M, N, K, accumulate, &rows, &splits);
+  if (csn != 1 || csm != N) splits = 1;     // split-K clears and adds into C as one dense block (every export's C is)
+  if (splits > 1 && !accumulate) (void)hipMemsetAsync(C, 0, (size_t)M * N * sizeof(float), st);
+  if (rows == 64)
     hipLaunchKernelGGL((k_sgemm_mfma<2, 2>), dim3((N + 63) / 64, (M + 63) / 64, splits), dim3(256), 0, st, A, asm_, ask, B,
                        bsk, bsn, C, csm, csn, M, N, K, alpha, accumulate);
   else

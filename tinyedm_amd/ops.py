@@ -1340,6 +1340,18 @@ def attention_qkv_bwd(x, y, gout, stat, wf_qkv, wd_out, heads, alpha=1.0):
 
 
 # ------------------------------------------------------------------ fp32 linears / embedding
+_LINEAR_GEMM = {"fwd": lambda M, N, K: (M, N, K), "dgrad": lambda M, N, K: (M, K, N), "wgrad": lambda M, N, K: (N, K, M)}
+
+
+def linear_plan(op, M, N, K, accumulate=0):
+    """(tile_rows, splits) of the GEMM that edm_linear_<op>(M, N, K, accumulate) launches (host logic only: no launch, no
+    device memory).  tile_rows 32 / 64 = the 32x64 / 64x64 tile; splits > 1 = split-K over atomics."""
+    gm, gn, gk = _LINEAR_GEMM[op](M, N, K)
+    rows, splits = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.call("edm_linear_plan", gm, gn, gk, int(accumulate), ctypes.byref(rows), ctypes.byref(splits))
+    return rows.value, splits.value
+
+
 def linear_fwd(x, w):
     _chk(x, f32, "x")
     _chk(w, f32, "w")
