@@ -376,10 +376,17 @@ int edm_linear_wgrad(const float* dY, const float* X, float* dW, int M, int N, i
                      edm_stream_t stream);
 int edm_fourier_fwd(const float* sigma, int sigma_stride, const float* freqs, const float* phases, float* out, int B,
                     int Fd, edm_stream_t stream);
+/* label dropout of classifier-free guidance training (networks.py _EmbeddingFn, Embedding(label_dropout=p)): a dropped
+ * sample takes the labels == NULL path for its row.  drop_in (B int32, nullable): the mask, given; otherwise, with
+ * drop_out set, drawn per sample b as philox4x32_10((b, 0x4C41424C, 0, step), (seed_lo, seed_hi)).x < drop_thr
+ * (drop_thr = round(p * 2^32), at most 2^32; dyn, nullable edm_step_params, overrides step / seed).  drop_out (B int32,
+ * nullable) receives the mask used; the backward reads it as drop.  All NULL / 0: the plain combine. */
 int edm_embed_combine_fwd(const float* emb_sigma, const float* wcls_hat, const long long* labels, float add_factor,
-                          int K, float* pre, float* out, int B, int E, edm_stream_t stream);
+                          int K, float* pre, float* out, int B, int E, unsigned long long drop_thr,
+                          unsigned long long seed, unsigned step, const void* dyn, const int* drop_in, int* drop_out,
+                          edm_stream_t stream);
 int edm_embed_combine_bwd(const float* gout, const float* pre, const long long* labels, float add_factor, int K,
-                          float* gemb_sigma, float* gwcls_hat, int B, int E, edm_stream_t stream);
+                          float* gemb_sigma, float* gwcls_hat, int B, int E, const int* drop, edm_stream_t stream);
 
 /* ---------------------------------------------------------------- step level (edm.py:84-93, 212; metric.py:8-18; edm.py:251; ema.py:137-140; solvers.py:49-57) */
 int edm_diffuse(const float* clean, float* noisy, float* sigma, float P_mean, float P_std, int B, long CHW,

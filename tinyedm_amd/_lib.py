@@ -93,8 +93,8 @@ SIGNATURES = {
     "edm_linear_dgrad": [P, P, P, I, I, I, I, P],
     "edm_linear_wgrad": [P, P, P, I, I, I, I, P],
     "edm_fourier_fwd": [P, I, P, P, P, I, I, P],
-    "edm_embed_combine_fwd": [P, P, P, F, I, P, P, I, I, P],
-    "edm_embed_combine_bwd": [P, P, P, F, I, P, P, I, I, P],
+    "edm_embed_combine_fwd": [P, P, P, F, I, P, P, I, I, U64, U64, U, P, P, P, P],
+    "edm_embed_combine_bwd": [P, P, P, F, I, P, P, I, I, P, P],
     # optim.hip
     "edm_diffuse": [P, P, P, F, F, I, L, U64, U, P, P],
     "edm_diffuse_given": [P, P, P, P, P, F, F, I, L, P],

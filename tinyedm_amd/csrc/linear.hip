@@ -142,30 +142,52 @@ __global__ void k_fourier(const float* __restrict__ sigma, int sstride, const fl
 }
 
 // pre = labels ? mp_add(emb_sigma, Wcls_hat[:,label]*sqrt(K), t) : emb_sigma ; out = mp_silu(pre)   (networks.py:169-177)
+//
+// Label dropout (classifier-free guidance training): a dropped sample b takes the labels == nullptr path for its row
+// (pre = emb_sigma, no mp_add).  The mask comes from drop_in (given by the caller) or, when drop_in is null and drop_out
+// is set, from Philox: r = philox4x32_10((b, 0x4C41424C, 0, step), (seed_lo, seed_hi)), dropped iff r.x < thr
+// (thr = round(p * 2^32) in [0, 2^32]; dyn overrides step / seed as in k_mod_silu_drop_fwd).  Every element of row b
+// makes the same call: no LDS round trip or barrier, and a row's lanes are one wave whenever E % 64 == 0.  The element
+// e == 0 of each row writes the mask it used to drop_out, which the backward reads.  drop_in == drop_out == nullptr is
+// the plain path.
 __global__ void k_embed_combine_fwd(const float* __restrict__ es, const float* __restrict__ wcls,
                                     const long long* __restrict__ labels, float t, int K, float* __restrict__ pre,
-                                    float* __restrict__ out, int B, int E) {
+                                    float* __restrict__ out, int B, int E, unsigned long long thr, uint32_t seed_lo,
+                                    uint32_t seed_hi, uint32_t step, const StepParams* __restrict__ dyn,
+                                    const int* __restrict__ drop_in, int* __restrict__ drop_out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B * E) return;
   const int b = i / E, e = i % E;
   float v = es[i];
   if (labels) {
-    const float c = rsqrtf((1.f - t) * (1.f - t) + t * t);
-    const long long lab = labels[b];
-    const float cls = (lab >= 0 && lab < K) ? wcls[(long)e * K + lab] * sqrtf((float)K) : 0.f;
-    v = ((1.f - t) * v + t * cls) * c;
+    bool dropped = false;
+    if (drop_in) {
+      dropped = drop_in[b] != 0;
+    } else if (drop_out) {
+      if (dyn) { step = dyn->step; seed_lo = dyn->seed_lo; seed_hi = dyn->seed_hi; }
+      const Philox4 r = philox4x32_10((uint32_t)b, 0x4C41424Cu, 0u, step, seed_lo, seed_hi);
+      dropped = (unsigned long long)r.x < thr;
+    }
+    if (drop_out && e == 0) drop_out[b] = dropped ? 1 : 0;
+    if (!dropped) {
+      const float c = rsqrtf((1.f - t) * (1.f - t) + t * t);
+      const long long lab = labels[b];
+      const float cls = (lab >= 0 && lab < K) ? wcls[(long)e * K + lab] * sqrtf((float)K) : 0.f;
+      v = ((1.f - t) * v + t * cls) * c;
+    }
   }
   pre[i] = v;
   out[i] = mp_silu_f(v);
 }
+// drop (nullable): the forward's mask output; a dropped row passes gout * mp_silu'(pre) to ges and adds nothing to gwcls
 __global__ void k_embed_combine_bwd(const float* __restrict__ gout, const float* __restrict__ pre,
                                     const long long* __restrict__ labels, float t, int K, float* __restrict__ ges,
-                                    float* __restrict__ gwcls, int B, int E) {
+                                    float* __restrict__ gwcls, int B, int E, const int* __restrict__ drop) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B * E) return;
   const int b = i / E, e = i % E;
   float g = gout[i] * mp_silu_grad_f(pre[i]);
-  if (labels) {
+  if (labels && !(drop && drop[b])) {
     const float c = rsqrtf((1.f - t) * (1.f - t) + t * t);
     const long long lab = labels[b];
     if (lab >= 0 && lab < K) atomicAdd(gwcls + (long)e * K + lab, g * t * c * sqrtf((float)K));
@@ -209,20 +231,28 @@ extern "C" int edm_fourier_fwd(const float* sigma, int sigma_stride, const float
   EDM_CHECK_LAUNCH("fourier_fwd");
   return EDM_OK;
 }
+// Label dropout: drop_in (B int32, nullable) gives the mask; otherwise, with drop_out set, the kernel draws it with
+// threshold drop_thr (<= 2^32) from (seed, step) or from dyn.  drop_out (B int32, nullable) receives the mask used.
 extern "C" int edm_embed_combine_fwd(const float* emb_sigma, const float* wcls_hat, const long long* labels,
-                                     float add_factor, int K, float* pre, float* out, int B, int E, hipStream_t st) {
-  EDM_REQUIRE(emb_sigma && pre && out && B > 0 && E > 0 && (!labels || (wcls_hat && K > 0)), "embed_combine_fwd: bad args");
+                                     float add_factor, int K, float* pre, float* out, int B, int E,
+                                     unsigned long long drop_thr, unsigned long long seed, unsigned step, const void* dyn,
+                                     const int* drop_in, int* drop_out, hipStream_t st) {
+  EDM_REQUIRE(emb_sigma && pre && out && B > 0 && E > 0 && (!labels || (wcls_hat && K > 0)) &&
+              drop_thr <= (1ull << 32) && (labels || (!drop_in && !drop_out)), "embed_combine_fwd: bad args");
   hipLaunchKernelGGL(k_embed_combine_fwd, dim3((B * E + 255) / 256), dim3(256), 0, st, emb_sigma, wcls_hat, labels,
-                     add_factor, K, pre, out, B, E);
+                     add_factor, K, pre, out, B, E, drop_thr, (uint32_t)seed, (uint32_t)(seed >> 32), step,
+                     (const StepParams*)dyn, drop_in, drop_out);
   EDM_CHECK_LAUNCH("embed_combine_fwd");
   return EDM_OK;
 }
-// gwcls_hat [E,K] is accumulated (+=): caller zero-fills.
+// gwcls_hat [E,K] is accumulated (+=): caller zero-fills.  drop (nullable): the mask edm_embed_combine_fwd wrote.
 extern "C" int edm_embed_combine_bwd(const float* gout, const float* pre, const long long* labels, float add_factor,
-                                     int K, float* gemb_sigma, float* gwcls_hat, int B, int E, hipStream_t st) {
-  EDM_REQUIRE(gout && pre && gemb_sigma && B > 0 && E > 0 && (!labels || (gwcls_hat && K > 0)), "embed_combine_bwd: bad args");
+                                     int K, float* gemb_sigma, float* gwcls_hat, int B, int E, const int* drop,
+                                     hipStream_t st) {
+  EDM_REQUIRE(gout && pre && gemb_sigma && B > 0 && E > 0 && (!labels || (gwcls_hat && K > 0)) && (labels || !drop),
+              "embed_combine_bwd: bad args");
   hipLaunchKernelGGL(k_embed_combine_bwd, dim3((B * E + 255) / 256), dim3(256), 0, st, gout, pre, labels, add_factor, K,
-                     gemb_sigma, gwcls_hat, B, E);
+                     gemb_sigma, gwcls_hat, B, E, drop);
   EDM_CHECK_LAUNCH("embed_combine_bwd");
   return EDM_OK;
 }

@@ -20,6 +20,11 @@ a guide network, evaluated at the same `--network_dtype`, and `--guidance W` sam
 classifier-free guidance with an unconditional guide, autoguidance with a smaller / less-trained conditional one.
 `--guidance_interval LO HI` guides only the evaluations with LO < sigma <= HI.  `--guidance 1` (the default) leaves the guide
 unused and the output byte-identical to a run without one.
+`--guide_unconditional` (instead of a guide network) is classifier-free guidance from the one checkpoint: the guide is the
+model's own label-free evaluation, for a conditional model trained with `model.embedding.label_dropout=p`.
+
+    python -m tinyedm.generate --ckpt_path cond.ckpt --load_ema --guide_unconditional --guidance 2 \\
+        --output_dir samples --num_samples 50000 --image_size 32 --num_classes 10 --batch_size 512
 
     python -m tinyedm.generate --ckpt_path cond.ckpt --load_ema --guide_ckpt_path uncond.ckpt --guide_load_ema \\
         --guidance 2.0 --guidance_interval 0.28 5.42 --output_dir samples --num_samples 50000 --image_size 32 \\
@@ -86,7 +91,11 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
         if guide is not None:
             raise ValueError("generate: pass guide or guide_ckpt_path, not both")
         guide = EDM.load_from_checkpoint(guide_ckpt_path, load_ema=guide_load_ema)
-    if guide is not None:
+    if guide == "unconditional":
+        if float(getattr(model.embedding, "label_dropout", 0.0)) == 0.0:
+            print(f"[rank {rank}] warning: the model was trained with label_dropout 0: it never saw label-free samples, "
+                  "its unconditional evaluation is untrained", flush=True)
+    elif guide is not None:
         guide = guide.to(dev).eval()
         guide.denoiser.set_eval_dtype(network_dtype)
         if float(guidance) == 1.0:
@@ -148,6 +157,8 @@ def main(argv=None):
     parser.add_argument("--guide_load_ema", action="store_true", help="load the EMA weights of the guide")
     parser.add_argument("--guide_config_name", type=str, default=None,
                         help="random-init guide from experiments/conf/<name>.yaml (no checkpoint)")
+    parser.add_argument("--guide_unconditional", action="store_true",
+                        help="classifier-free guidance from the model alone: its label-free evaluation is the guide")
     parser.add_argument("--guidance", type=float, default=1.0,
                         help="guidance weight w: D = D_guide + w*(D_main - D_guide) (default 1.0 = unguided)")
     parser.add_argument("--guidance_interval", type=float, nargs=2, metavar=("LO", "HI"), default=None,
@@ -169,6 +180,9 @@ def main(argv=None):
     _check_solver(args.solver, args.S_churn)
     if args.guide_ckpt_path is not None and args.guide_config_name is not None:
         parser.error("--guide_ckpt_path and --guide_config_name are exclusive")
+    if args.guide_unconditional and (args.guide_ckpt_path is not None or args.guide_config_name is not None):
+        parser.error("--guide_unconditional evaluates the model itself as the guide: no --guide_ckpt_path or "
+                     "--guide_config_name")
     from . import networks
     from .config import compose, instantiate
     conf_dir = args.config_path or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
@@ -181,6 +195,8 @@ def main(argv=None):
         return instantiate(cfg.model)
     # the guide first: the main network's seeding is then the last, as without a guide
     guide = None if args.guide_config_name is None else random_init(args.guide_config_name)
+    if args.guide_unconditional:
+        guide = "unconditional"
     model = None
     if args.ckpt_path is None:
         if args.config_name is None:

@@ -741,8 +741,15 @@ class _EmbeddingFn(torch.autograd.Function):
         wsh = mod.sigma_embed.packs()[2]
         wch = mod.class_embed.linear.packs()[2] if labels is not None else None
         es = ops.linear_fwd(four, wsh)
-        pre, out = ops.embed_combine_fwd(es, wch, labels, mod.add_factor)
-        ctx.mod, ctx.labels = mod, labels
+        drop = None
+        if labels is not None and mod.training and mod.label_dropout > 0:
+            # label dropout: the per-sample mask is drawn in the combine kernel from the Diffuser's (seed, step)
+            pre, out, drop = ops.embed_combine_fwd(es, wch, labels, mod.add_factor, drop_p=mod.label_dropout,
+                                                   seed=rng.seed, step=rng.step, dyn=rng.dyn)
+        else:
+            pre, out = ops.embed_combine_fwd(es, wch, labels, mod.add_factor)
+        ctx.mod, ctx.labels, ctx.drop = mod, labels, drop
+        mod.last_label_drop = drop
         ctx.save_for_backward(four, pre)
         ctx.mark_non_differentiable(four)
         return four, out
@@ -752,7 +759,7 @@ class _EmbeddingFn(torch.autograd.Function):
         four, pre = ctx.saved_tensors
         mod = ctx.mod
         wshape = tuple(mod.class_embed.linear.weight.shape) if ctx.labels is not None else None
-        ges, gwch = ops.embed_combine_bwd(gout.contiguous(), pre, ctx.labels, mod.add_factor, wshape)
+        ges, gwch = ops.embed_combine_bwd(gout.contiguous(), pre, ctx.labels, mod.add_factor, wshape, drop=ctx.drop)
         dws = ops.linear_wgrad(ges, four)
         gws = mod.sigma_embed.finish_grad(dws.view(1, 1, *dws.shape))
         gwc = mod.class_embed.linear.finish_grad(gwch.view(1, 1, *gwch.shape)) if gwch is not None else None
@@ -760,10 +767,26 @@ class _EmbeddingFn(torch.autograd.Function):
 
 
 class Embedding(nn.Module):
-    """networks.py:144-178: (sigma, labels|None) -> (fourier (B,F), emb (B,E)), fp32."""
+    """networks.py:144-178: (sigma, labels|None) -> (fourier (B,F), emb (B,E)), fp32.
 
-    def __init__(self, fourier_dim: int, embedding_dim: int, num_classes: int | None = None, add_factor: float = 0.5):
+    ``label_dropout`` (extension, default 0): in training mode, each sample's class label is dropped with probability
+    p -- its embedding is the label-free one, ``forward(sigma, None)`` -- so that the same network can serve as its own
+    unconditional guide (classifier-free guidance, ``guide="unconditional"`` of the solvers).  The per-sample choice is
+    drawn in the combine kernel from the Philox stream of the Diffuser's (seed, step); ``last_label_drop`` holds the
+    int32 mask of the last training forward (None when nothing was dropped).  eval() and label-free calls never drop."""
+
+    _local_extensions = ("label_dropout",)      # not in the reference's signature: left out of deinstantiate at default
+
+    def __init__(self, fourier_dim: int, embedding_dim: int, num_classes: int | None = None, add_factor: float = 0.5,
+                 label_dropout: float = 0.0):
         super().__init__()
+        label_dropout = float(label_dropout)
+        if not 0.0 <= label_dropout <= 1.0:
+            raise ValueError(f"Embedding: label_dropout must be in [0, 1], got {label_dropout}")
+        if label_dropout > 0 and (num_classes is None or num_classes == -1):
+            raise ValueError("Embedding: label_dropout > 0 needs a class-conditional embedding (num_classes)")
+        self.label_dropout = label_dropout
+        self.last_label_drop = None
         self.fourier_dim = fourier_dim
         self.add_factor = add_factor
         self.embedding_dim = embedding_dim

@@ -1410,20 +1410,40 @@ def _labels_arg(labels, B):
     return labels
 
 
-def embed_combine_fwd(emb_sigma, wcls_hat, labels, add_factor):
+def label_drop_threshold(p) -> int:
+    """the drop threshold of edm_embed_combine_fwd: round(p * 2^32) in fp64, clamped to [0, 2^32] (p = 0 drops no sample,
+    p = 1 every one)"""
+    return min(max(int(round(float(p) * 4294967296.0)), 0), 1 << 32)
+
+
+def embed_combine_fwd(emb_sigma, wcls_hat, labels, add_factor, *, drop_p=0.0, seed=0, step=0, dyn=None, drop=None):
+    """-> (pre, out); with label dropout (drop_p > 0 or a given mask `drop`, B int32 / bool, nonzero = dropped; needs
+    labels) -> (pre, out, mask): the B int32 mask the kernel used, drawn from (seed, step) or dyn unless given.  A dropped
+    sample's row is the labels=None row."""
     _chk(emb_sigma, f32, "emb_sigma")
     B, E = emb_sigma.shape
     K = 0
     if labels is not None:
         _chk(wcls_hat, f32, "wcls_hat")
         K = wcls_hat.shape[1]
+    thr = label_drop_threshold(drop_p)
+    masked = thr > 0 or drop is not None
+    if masked and labels is None:
+        raise ValueError("embed_combine_fwd: label dropout needs labels")
+    drop_in = None
+    if drop is not None:
+        if not drop.is_cuda or drop.numel() != B:
+            raise ValueError(f"embed_combine_fwd: drop must be a device tensor of {B} elements")
+        drop_in = drop.flatten().to(torch.int32).contiguous()
+    mask = torch.empty(B, device=emb_sigma.device, dtype=torch.int32) if masked else None
     pre, out = torch.empty_like(emb_sigma), torch.empty_like(emb_sigma)
     _lib.call("edm_embed_combine_fwd", _p(emb_sigma), _p(wcls_hat), _p(labels), float(add_factor), K, _p(pre), _p(out), B,
-              E, _stream())
-    return pre, out
+              E, thr, int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFF, _dyn(dyn), _p(drop_in), _p(mask), _stream())
+    return (pre, out, mask) if masked else (pre, out)
 
 
-def embed_combine_bwd(gout, pre, labels, add_factor, wcls_shape):
+def embed_combine_bwd(gout, pre, labels, add_factor, wcls_shape, *, drop=None):
+    """drop (nullable): the int32 mask embed_combine_fwd returned"""
     _chk(gout, f32, "gout", pre.shape)
     B, E = pre.shape
     ges = torch.empty_like(pre)
@@ -1431,7 +1451,12 @@ def embed_combine_bwd(gout, pre, labels, add_factor, wcls_shape):
     if labels is not None:
         gw = zeros_f32(wcls_shape, pre.device)
         K = wcls_shape[1]
-    _lib.call("edm_embed_combine_bwd", _p(gout), _p(pre), _p(labels), float(add_factor), K, _p(ges), _p(gw), B, E, _stream())
+    if drop is not None:
+        if labels is None:
+            raise ValueError("embed_combine_bwd: label dropout needs labels")
+        _chk(drop, torch.int32, "drop", (B,))
+    _lib.call("edm_embed_combine_bwd", _p(gout), _p(pre), _p(labels), float(add_factor), K, _p(ges), _p(gw), B, E, _p(drop),
+              _stream())
     return ges, gw
 
 

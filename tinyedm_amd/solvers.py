@@ -9,6 +9,12 @@ import torch
 
 from . import _runtime_env, ops
 
+UNCONDITIONAL = "unconditional"     # guide= sentinel: the model's own label-free evaluation is the guide
+
+
+def _is_unconditional(guide) -> bool:
+    return isinstance(guide, str) and guide == UNCONDITIONAL
+
 
 def _release_solves(per_model: dict):
     try:
@@ -32,7 +38,9 @@ class DeterministicSolver:
         D(x; sigma, c) = D_guide(x; sigma, c) + guidance * (D_main(x; sigma, c) - D_guide(x; sigma, c))
 
     classifier-free guidance with an unconditional ``guide`` (an unconditional EDM drops the labels itself),
-    autoguidance with a smaller / less-trained conditional one.  With ``guidance_interval=(lo, hi)`` only the
+    autoguidance with a smaller / less-trained conditional one.  ``guide="unconditional"`` is classifier-free guidance
+    from the model alone: D_guide is the model's own label-free evaluation ``model(x, sigma, None)`` (same weights, same
+    evaluation packs), for a conditional EDM trained with ``Embedding(label_dropout=p)``.  With ``guidance_interval=(lo, hi)`` only the
     evaluations with lo < sigma <= hi (sigma = the fp32 table value) are guided; the others use D_main alone and do not
     evaluate the guide.  ``guidance == 1`` guides nothing: the guide is never evaluated and the solve is the unguided
     one.  ``guidance`` and ``guidance_interval`` are plain attributes, read at every solve; a captured solve reads the
@@ -67,6 +75,9 @@ class DeterministicSolver:
         w = float(self.guidance)
         if not math.isfinite(w):
             raise ValueError(f"DeterministicSolver: guidance must be finite, got {self.guidance}")
+        if isinstance(self.guide, str) and self.guide != UNCONDITIONAL:
+            raise ValueError(f"DeterministicSolver: guide must be a network, None or {UNCONDITIONAL!r}, got "
+                             f"{self.guide!r}")
         if w != 1.0 and self.guide is None:
             raise ValueError(f"DeterministicSolver: guidance={w} needs a guide network (guide=None)")
         if self.guidance_interval is not None:
@@ -103,9 +114,17 @@ class DeterministicSolver:
         """the state, sigma and device sigma the step-i Euler evaluation starts from"""
         return x, ts[i], t_dev[i]
 
-    def _check_guide(self, model, device):
+    def _check_guide(self, model, device, class_labels):
         """the checks that need the networks: run before any launch of a solve that evaluates the guide"""
         from .edm import EDM
+        if _is_unconditional(self.guide):
+            owner = getattr(model, "__self__", model)
+            if not (isinstance(owner, EDM) and owner.conditional):
+                raise ValueError("DeterministicSolver: guide='unconditional' needs a class-conditional EDM as the model")
+            if class_labels is None:
+                raise ValueError("DeterministicSolver: guide='unconditional' needs class_labels (without them the "
+                                 "model's evaluation is the unconditional one already)")
+            return
         guide = getattr(self.guide, "__self__", self.guide)
         if isinstance(guide, torch.nn.Module):
             if guide.training:
@@ -120,6 +139,12 @@ class DeterministicSolver:
                 raise ValueError(f"DeterministicSolver: guide channels (in {g.in_channels}, out {g.out_channels}) differ "
                                  f"from the model's (in {m.in_channels}, out {m.out_channels})")
 
+    def _guide_eval(self, model, x, sigma, class_labels):
+        """D_guide of one guided evaluation (the one place that resolves guide='unconditional')"""
+        if _is_unconditional(self.guide):
+            return model(x, sigma, None).float().contiguous()
+        return self.guide(x, sigma, class_labels).float().contiguous()
+
     # ------------------------------------------------------------------ eager
     def _loop(self, model, x0, class_labels, t_dev, guided, w_dev, state=None):
         ts = self.t_steps.tolist()
@@ -129,14 +154,14 @@ class DeterministicSolver:
             t1 = ts[i + 1]
             D = model(x, s0, class_labels).float().contiguous()
             if guided[2 * i]:
-                Dg = self.guide(x, s0, class_labels).float().contiguous()
+                Dg = self._guide_eval(model, x, s0, class_labels)
                 dx, x1 = ops.heun_euler_guided(x, D, Dg, w_dev, t0, t1)
             else:
                 dx, x1 = ops.heun_euler(x, D, t0, t1)
             if i < self.num_steps - 1:
                 D1 = model(x1, t_dev[i + 1], class_labels).float().contiguous()
                 if guided[2 * i + 1]:
-                    Dg1 = self.guide(x1, t_dev[i + 1], class_labels).float().contiguous()
+                    Dg1 = self._guide_eval(model, x1, t_dev[i + 1], class_labels)
                     x1 = ops.heun_correct_guided(x, dx, x1, D1, Dg1, w_dev, t0, t1)
                 else:
                     x1 = ops.heun_correct(x, dx, x1, D1, t0, t1)
@@ -148,7 +173,7 @@ class DeterministicSolver:
             raise RuntimeError("tinyedm_amd.DeterministicSolver: x0 must be a GPU tensor (there is no CPU path)")
         guided = self.guided_evaluations()
         if any(guided):
-            self._check_guide(model, x0.device)
+            self._check_guide(model, x0.device, class_labels)
         in_dtype = x0.dtype
         x0 = x0.float().contiguous()
         if not graph:
@@ -182,9 +207,13 @@ class DeterministicSolver:
                eval_dtypes(owner))
         # a guided solve also keys on the guide (the entry holds it, so its id cannot be reused while the graph that
         # reads its weights exists) and on which evaluations are guided; NOT on the guidance weight, which the graph
-        # reads from the entry's w_dev.  An unguided solve keeps the unguided key whatever guide is set.
+        # reads from the entry's w_dev.  An unguided solve keeps the unguided key whatever guide is set.  The model as its
+        # own guide is a constant tag: the entry then holds no guide (a wrapper referencing the model would keep the
+        # model, the weak key of _graphs, alive)
         guide = getattr(self.guide, "__self__", self.guide) if any(guided) else None
-        if guide is not None:
+        if _is_unconditional(guide):
+            key += ((UNCONDITIONAL,), guided)
+        elif guide is not None:
             key += (id(guide), eval_dtypes(guide), guided)
         key += self._graph_key_extra()
         ent = per_model.get(key)
@@ -192,6 +221,8 @@ class DeterministicSolver:
             _runtime_env.require_graph_replay_safe("DeterministicSolver.solve(graph=True)")
             t_dev = self.t_steps.to(x0.device)
             w_dev = None if guide is None else torch.full((1,), float(self.guidance), device=x0.device)
+            if _is_unconditional(guide):
+                guide = None
             state = self._solve_state(x0)
             sx = x0.clone()
             sl = None if class_labels is None else class_labels.clone()
@@ -442,7 +473,7 @@ class MultistepSolver(DeterministicSolver):
         x = ops.scale_f32(x0, self.t_steps[0].item())
         for i, (k, a, c0, c1, c2) in enumerate(state.steps):
             D = model(x, t_dev[i], class_labels).float().contiguous()
-            Dg = self.guide(x, t_dev[i], class_labels).float().contiguous() if guided[i] else None
+            Dg = self._guide_eval(model, x, t_dev[i], class_labels) if guided[i] else None
             x = ops.dpm_multistep(x, D, a, c0, c1, c2, Dg=Dg, w_dev=None if Dg is None else w_dev,
                                   m1=hist[(i - 1) % L] if k >= 2 else None, m2=hist[(i - 2) % L] if k >= 3 else None,
                                   m_out=hist[i % L] if L and i < N - 1 else None)

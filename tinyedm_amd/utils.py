@@ -7,12 +7,16 @@ import torch
 def deinstantiate(obj):
     """Module -> Hydra-instantiable dict: ``_target_`` + every constructor argument read back from the
     same-named attribute (nested modules recursively, tuples as lists) -- reference utils.py:5-27.
-    ``_target_`` uses the *tinyedm* alias path so checkpoints stay interchangeable with the reference."""
+    ``_target_`` uses the *tinyedm* alias path so checkpoints stay interchangeable with the reference: an argument a
+    class lists in ``_local_extensions`` (not in the reference's signature) is left out while it equals its default."""
     mod = obj.__class__.__module__.replace("tinyedm_amd", "tinyedm", 1)
     target = f"{mod}.{obj.__class__.__name__}"
+    local = getattr(obj, "_local_extensions", ())
     out = {}
     for name, param in inspect.signature(obj.__init__).parameters.items():
         if name == "self":
+            continue
+        if name in local and getattr(obj, name, param.default) == param.default:
             continue
         if hasattr(obj, name):
             value = getattr(obj, name)

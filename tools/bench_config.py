@@ -4,6 +4,7 @@
   --shape C,H,W       input shape (sets the denoiser's in / out channels too): 3,64,64 = ImageNet-64 pixel space,
                       4,64,64 = the YAML's latents, 4,32,32 = BASELINE.json configs[4] (ImageNet-256 through the SD-VAE)
   --sampler DT B      also time a captured 32-step Heun solve (63 network evaluations) of the same net at batch B
+  --label-dropout P   model.embedding.label_dropout (class-conditional configs: label dropout of CFG training)
   --fwd-gflop G       GFLOP of one network evaluation per image (192.9 at 64x64, 48.0 at 32x32 for the default
                       Denoiser; 27.0 CIFAR-10; 20.1 MNIST): prints achieved fractions of the 2.5 PFLOP/s bf16 MFMA peak
                       (training = 3 x forward) -- and of 8 TB/s with --fwd-mb M (conv activation MB per evaluation)
@@ -33,6 +34,7 @@ def main():
     argv = [a for a in argv if a != "--graph"]
     shape_o = _opt(argv, "--shape")
     sampler = _opt(argv, "--sampler", 2)
+    label_dropout = _opt(argv, "--label-dropout")
     gflop = float(_opt(argv, "--fwd-gflop", default=0) or 0)
     fwd_mb = float(_opt(argv, "--fwd-mb", default=0) or 0)
     no_train = "--no-train" in argv
@@ -49,6 +51,8 @@ def main():
         cfg.datamodule.image_shape = shp
         cfg.model.denoiser.in_channels = shp[0]
         cfg.model.denoiser.out_channels = shp[0]
+    if label_dropout is not None:
+        cfg.model.embedding.label_dropout = float(label_dropout)
     tinyedm.manual_seed(cfg.seed)
     torch.manual_seed(cfg.seed)
     dev = torch.device("cuda:0")
