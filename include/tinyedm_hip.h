@@ -446,6 +446,23 @@ int edm_heun_churn(const float* x, float c, const void* rec, int step, int B, lo
 int edm_dpm_multistep(const float* x, const float* Dm, const float* Dg, const float* w, const float* m1,
                       const float* m2, float a, float c0, float c1, float c2, float* x_out, float* m_out, long n,
                       unsigned* health, edm_stream_t stream);
+/* state of an image-conditioned solve at noise level t >= 0: out = image + t*x0 as one fma, x0 the caller's unit
+ * noise, all fp32 of n elements.  image is nullable: out = x0*t then, bit for bit what edm_scale_f32 gives.  dwordx4
+ * when every operand is 16-byte aligned.  out aliases no operand.  Same health bit as the Heun updates. */
+int edm_state_init(const float* image, const float* x0, float t, float* out, long n, unsigned* health,
+                   edm_stream_t stream);
+/* replacement step of inpainting (Song et al. 2021): out = mask ? image + t*n : x, n ~ N(0, 1) drawn in the kernel,
+ * x / image / out contiguous [B, C, HW] fp32, t >= 0.  mask: uint8 [mask_B, HW], mask_B in {1, B}, broadcast over the
+ * channels (and the batch when mask_B == 1); non-zero = known pixel, taken from image.  Element j of sample b (j over
+ * C*HW) is normal j % 4 of one Philox4x32-10 call with counter (j / 4, b, 0x49500000 ^ step, solve_index) and key
+ * (seed_lo, seed_hi), Box-Muller of words (0, 1) and (2, 3) as edm_heun_churn; the tag differs from the churn's
+ * 0x43480000 (and from edm_diffuse's 0xD1FF / 0x5167), so the two streams of one (seed, solve_index, step) are
+ * independent; step < 65536.  rec is the churn's DEVICE record {seed_lo, seed_hi, solve_index, 0}, read at run time.
+ * The noise of a sample does not depend on B, the mask or the memory path (dwordx4 and one 32-bit mask load per quad when
+ * HW % 4 == 0, x / image / out are 16-byte and mask 4-byte aligned).  t == 0 returns image bit for bit on the mask.
+ * Same health bit as the Heun updates. */
+int edm_inpaint_blend(const float* x, const float* image, const unsigned char* mask, float t, const void* rec, int step,
+                      int B, int C, long HW, int mask_B, float* out, unsigned* health, edm_stream_t stream);
 int edm_scale_f32(const float* x, float s, float* y, long n, edm_stream_t stream);
 
 /* ---------------------------------------------------------------- reference-precision evaluation (eval_f32.hip)

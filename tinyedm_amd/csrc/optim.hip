@@ -393,6 +393,92 @@ __global__ void k_heun_churn(const float* __restrict__ x, float c, const uint32_
   }
   if (health && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(health, 2u);
 }
+// State of an image-conditioned solve at noise level t: out = image + t*x0 as one fma (x0 the caller's unit noise).
+// image == nullptr: out = x0*t, the product k_scale_f32 computes, bit for bit.  vec: every operand 16-byte aligned ->
+// dwordx4 over the first n/4*4 elements, the tail (and the whole range when !vec) element by element.
+__global__ void k_state_init(const float* __restrict__ image, const float* __restrict__ x0, float t,
+                             float* __restrict__ out, long n, bool vec, unsigned* __restrict__ health) {
+  const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long)gridDim.x * blockDim.x;
+  bool bad = false;
+  long head = 0;
+  if (vec) {
+    head = n / 4 * 4;
+    for (long i = tid * 4; i < head; i += stride * 4) {
+      const f32x4 nv = *reinterpret_cast<const f32x4*>(x0 + i);
+      f32x4 iv{}, ov;
+      if (image) iv = *reinterpret_cast<const f32x4*>(image + i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        ov[j] = image ? fmaf(t, nv[j], iv[j]) : nv[j] * t;
+        bad |= !(fabsf(ov[j]) <= 3.0e38f);
+      }
+      *reinterpret_cast<f32x4*>(out + i) = ov;
+    }
+  }
+  for (long i = head + tid; i < n; i += stride) {
+    const float o = image ? fmaf(t, x0[i], image[i]) : x0[i] * t;
+    bad |= !(fabsf(o) <= 3.0e38f);
+    out[i] = o;
+  }
+  if (health && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(health, 2u);
+}
+// Replacement step of inpainting (Song et al. 2021): out = mask ? image + t*n : x, n ~ N(0, 1) drawn here: the known
+// pixels are re-noised to the level t of the state they are pasted into.  mask: uint8 [mask_B, HW], mask_B in {1, B},
+// broadcast over the C channels (and over the batch when mask_B == 1); non-zero = known pixel.  The noise is k_heun_churn's
+// construction under its own tag: one thread per quad q of a sample b, element j = 4q + k of sample b takes normal k of
+//   philox4x32_10(ctr = (q, b, 0x49500000 ^ step, solve_index), key = (seed_lo, seed_hi))
+// so it depends only on (seed, solve_index, step, b, j): not on the batch size, the grid, the mask or the memory path,
+// and it is independent of the churn noise of the same (seed, solve_index, step).  A quad whose mask is clear, and every
+// quad when t == 0, draws nothing; t == 0 returns image itself on the mask.  vec: CHW % 4 == 0, HW % 4 == 0 (a quad
+// then lies in one channel and its four mask bytes are one aligned 32-bit word), x / image / out 16-byte aligned and
+// mask 4-byte aligned -> one dwordx4 per operand and one dword of mask per quad; otherwise the same quads element by
+// element (the last quad of a sample may be partial).
+__global__ void k_inpaint_blend(const float* __restrict__ x, const float* __restrict__ image,
+                                const uint8_t* __restrict__ mask, float t, const uint32_t* __restrict__ rec,
+                                uint32_t step, int B, long CHW, long HW, int mask_B, float* __restrict__ out, bool vec,
+                                unsigned* __restrict__ health) {
+  const uint32_t seed_lo = rec[0], seed_hi = rec[1], solve_index = rec[2];
+  const long nq = (CHW + 3) / 4, total = (long)B * nq;
+  bool bad = false;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long b = i / nq, q = i - b * nq;
+    const long e = b * CHW + 4 * q;
+    const uint8_t* mrow = mask + (mask_B == 1 ? 0 : b * HW);
+    const int m = vec ? 4 : (int)(CHW - 4 * q < 4 ? CHW - 4 * q : 4);
+    bool keep[4] = {false, false, false, false};
+    if (vec) {
+      const uint32_t mw = *reinterpret_cast<const uint32_t*>(mrow + (4 * q) % HW);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) keep[k] = ((mw >> (8 * k)) & 0xFFu) != 0;
+    } else {
+      for (int k = 0; k < m; ++k) keep[k] = mrow[(4 * q + k) % HW] != 0;
+    }
+    float nn[4] = {0.f, 0.f, 0.f, 0.f};
+    if (t != 0.f && (keep[0] || keep[1] || keep[2] || keep[3])) {
+      const Philox4 r = philox4x32_10((uint32_t)q, (uint32_t)b, 0x49500000u ^ step, solve_index, seed_lo, seed_hi);
+      box_muller(r.x, r.y, nn[0], nn[1]);
+      box_muller(r.z, r.w, nn[2], nn[3]);
+    }
+    if (vec) {
+      const f32x4 xv = *reinterpret_cast<const f32x4*>(x + e);
+      const f32x4 iv = *reinterpret_cast<const f32x4*>(image + e);
+      f32x4 ov;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        ov[k] = keep[k] ? (t != 0.f ? fmaf(t, nn[k], iv[k]) : iv[k]) : xv[k];
+        bad |= !(fabsf(ov[k]) <= 3.0e38f);
+      }
+      *reinterpret_cast<f32x4*>(out + e) = ov;
+    } else {
+      for (int k = 0; k < m; ++k) {
+        const float o = keep[k] ? (t != 0.f ? fmaf(t, nn[k], image[e + k]) : image[e + k]) : x[e + k];
+        bad |= !(fabsf(o) <= 3.0e38f);
+        out[e + k] = o;
+      }
+    }
+  }
+  if (health && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(health, 2u);
+}
 // DPM-Solver++ multistep update in data-prediction form (sigma(t) = t, s(t) = 1):
 //   m = Dg + w*(Dm - Dg)  (G; else m = Dm),   x_out = a*x + c0*m + c1*m1 + c2*m2   (H = number of history terms)
 // evaluated as fmaf(a, x, fmaf(c2, m2, fmaf(c1, m1, c0*m))), so the row (0, 1, 0, 0) of the final step returns m
@@ -639,6 +725,32 @@ extern "C" int edm_dpm_multistep(const float* x, const float* Dm, const float* D
   }
 #undef EDM_DPM_LAUNCH
   EDM_CHECK_LAUNCH("dpm_multistep");
+  return EDM_OK;
+}
+// image nullable: out = x0*t (edm_scale_f32's result); else out = image + t*x0.  out aliases no operand.
+extern "C" int edm_state_init(const float* image, const float* x0, float t, float* out, long n, unsigned* health,
+                              hipStream_t st) {
+  EDM_REQUIRE(x0 && out && n > 0 && std::isfinite(t) && t >= 0.f, "state_init: bad args");
+  const bool vec = aligned16({image, x0, out});        // (a null pointer counts as aligned)
+  hipLaunchKernelGGL(k_state_init, dim3(grid_for(vec ? (n + 3) / 4 : n, 256)), dim3(256), 0, st, image, x0, t, out, n,
+                     vec, health);
+  EDM_CHECK_LAUNCH("state_init");
+  return EDM_OK;
+}
+// rec: device pointer to {seed_lo, seed_hi, solve_index, 0} (uint32), read by the kernel; step and t by value.  step is
+// below 2^16: the tag then differs from the churn's in its high half whatever the two steps are.
+extern "C" int edm_inpaint_blend(const float* x, const float* image, const unsigned char* mask, float t,
+                                 const void* rec, int step, int B, int C, long HW, int mask_B, float* out,
+                                 unsigned* health, hipStream_t st) {
+  EDM_REQUIRE(x && image && mask && rec && out && B > 0 && C > 0 && HW > 0 && step >= 0 && step < 65536 &&
+              (mask_B == 1 || mask_B == B) && std::isfinite(t) && t >= 0.f, "inpaint_blend: bad args");
+  const long CHW = (long)C * HW;
+  EDM_REQUIRE((CHW + 3) / 4 <= 0xFFFFFFFFL, "inpaint_blend: CHW / 4 must fit the 32-bit Philox counter word");
+  const bool vec = CHW % 4 == 0 && HW % 4 == 0 && aligned16({x, image, out}) &&
+                   (reinterpret_cast<uintptr_t>(mask) & 3) == 0;
+  hipLaunchKernelGGL(k_inpaint_blend, dim3(grid_for((long)B * ((CHW + 3) / 4), 256)), dim3(256), 0, st, x, image, mask,
+                     t, (const uint32_t*)rec, (uint32_t)step, B, CHW, HW, mask_B, out, vec, health);
+  EDM_CHECK_LAUNCH("inpaint_blend");
   return EDM_OK;
 }
 extern "C" int edm_scale_f32(const float* x, float s, float* y, long n, hipStream_t st) {

@@ -69,15 +69,24 @@ class SyntheticImageDataModule:
 class RandomNoiseDataModule:
     """datamodules/random_datamodule.py:21-45, same positional order (batch_size, num_workers, image_size,
     num_samples, num_classes).  Extensions are keyword-only: `in_channels` (the reference hard-codes 3),
-    `image_shape` (overrides in_channels/image_size), `seed`, `device`.  num_workers is accepted and ignored."""
+    `image_shape` (overrides in_channels/image_size), `seed`, `device`.  num_workers is accepted and ignored.
+    `images` (host fp32 [num_samples, *image_shape], normalised) and `mask` (uint8 [H, W], non-zero = known pixel) are the
+    image conditioning of EDM.predict_step: a batch is then (noise, labels, images[, mask]); the noise and the labels
+    are those of a module without them."""
 
     def __init__(self, batch_size: int, num_workers: int, image_size: int, num_samples: int,
                  num_classes: int | None, *, in_channels: int = 3, image_shape=None, seed: int = 0,
-                 device: str | None = None):
+                 device: str | None = None, images=None, mask=None):
         self.batch_size, self.num_workers, self.image_size = batch_size, num_workers, image_size
         self.num_samples, self._num_classes = num_samples, num_classes
         self.image_shape = tuple(image_shape) if image_shape is not None else (in_channels, image_size, image_size)
         self.seed, self.device = seed, device
+        if images is not None and tuple(images.shape) != (num_samples,) + self.image_shape:
+            raise ValueError(f"RandomNoiseDataModule: images must have shape {(num_samples,) + self.image_shape}, got "
+                             f"{tuple(images.shape)}")
+        if mask is not None and (images is None or tuple(mask.shape) != self.image_shape[1:]):
+            raise ValueError(f"RandomNoiseDataModule: mask needs images and the shape {self.image_shape[1:]}")
+        self.images, self.mask = images, mask
 
     @property
     def num_classes(self):
@@ -99,7 +108,10 @@ class RandomNoiseDataModule:
             x = torch.randn(b, *self.image_shape, generator=g)
             k = self.num_classes if self.num_classes else 1
             y = torch.randint(0, k, (b, 1), generator=g)
-            return x.to(dev), y.to(dev)
+            if self.images is None:
+                return x.to(dev), y.to(dev)
+            img = self.images[i * self.batch_size:i * self.batch_size + b].to(dev)
+            return (x.to(dev), y.to(dev), img) + (() if self.mask is None else (self.mask.to(dev),))
 
         return _DeviceBatches(make, n_batches)
 

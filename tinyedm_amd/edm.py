@@ -193,9 +193,11 @@ class EDM(LightningModule):
         return self.denoiser(noisy_image, sigma, embedding)
 
     def predict_step(self, batch: Any, batch_idx: int, dataloader_idx: int | None = None):
-        x0, class_label = batch
+        x0, class_label, *cond = batch       # cond: (image[, mask]) of an image-conditioned batch (RandomNoiseDataModule)
         class_label = class_label if self.conditional else None
-        return self.solver.solve(self, x0, class_label)
+        if not cond:
+            return self.solver.solve(self, x0, class_label)
+        return self.solver.solve(self, x0, class_label, image=cond[0], mask=cond[1] if len(cond) > 1 else None)
 
     @property
     def num_classes(self) -> int | None:

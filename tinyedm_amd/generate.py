@@ -44,6 +44,22 @@ byte-identical to a run without these flags.
 
     python -m tinyedm.generate --ckpt_path last.ckpt --load_ema --solver dpmpp --solver_order 2 --num_steps 32 \\
         --output_dir samples --num_samples 50000 --image_size 32 --num_classes 10 --batch_size 512
+Image-conditioned sampling: `--init_dir DIR` reads PNGs as this program writes them (`<index>.png`, taken in numeric order
+of the index, normalised with `--mean/--std`), one per sample.  `--start_step K` (SDEdit / image-to-image) noises each
+image to sigma_K of the table and solves from there.  `--mask_box X0 Y0 X1 Y1` (inpainting) regenerates the pixels with
+X0 <= x < X1, Y0 <= y < Y1 and keeps everything outside the box, which comes out as the input image.  Both combine
+with each other, with guidance, churn and `--solver dpmpp`.  `--invert_to OUT.pt` (Heun solver only) writes no images:
+it runs the ODE upwards from each image to sigma_K and saves {"latents", "class_labels", "end_step", "num_steps"}, the
+unit-scale latents that `solve(..., start_step=K)` turns back into the images.  Without `--init_dir` nothing changes.
+
+    python -m tinyedm.generate --ckpt_path last.ckpt --load_ema --init_dir photos --start_step 12 \\
+        --output_dir variations --num_samples 64 --image_size 32 --num_classes 10 --batch_size 64
+
+    python -m tinyedm.generate --ckpt_path last.ckpt --load_ema --init_dir photos --mask_box 8 8 24 24 \\
+        --output_dir inpainted --num_samples 64 --image_size 32 --num_classes 10 --batch_size 64
+
+    python -m tinyedm.generate --ckpt_path last.ckpt --load_ema --init_dir photos --invert_to latents.pt \\
+        --output_dir unused --num_samples 64 --image_size 32 --num_classes 10 --batch_size 64
 Multi-GPU = replicas only: under `python -m torch.distributed.run --nproc-per-node N` every rank samples
 its own contiguous index range with its own noise seed and writes `<global index>.png`; there is no collective.
 """
@@ -67,11 +83,63 @@ def _check_solver(solver, S_churn) -> None:
                          "sampling is --solver heun)")
 
 
+def _check_conditioning(init_dir, start_step, mask_box, invert_to, solver, S_churn, image_size) -> None:
+    """the image-conditioning choices that need nothing loaded"""
+    if isinstance(start_step, bool) or not isinstance(start_step, int) or start_step < 0:
+        raise ValueError(f"generate: --start_step must be an integer >= 0, got {start_step!r}")
+    if init_dir is None:
+        for flag, on in (("--mask_box", mask_box is not None), ("--start_step", start_step > 0),
+                         ("--invert_to", invert_to is not None)):
+            if on:
+                raise ValueError(f"generate: {flag} needs --init_dir (the images to start from)")
+        return
+    if mask_box is not None:
+        try:
+            x0, y0, x1, y1 = (int(v) for v in mask_box)
+            ok = len(mask_box) == 4 and all(int(v) == v for v in mask_box)
+        except (TypeError, ValueError):
+            ok = False
+        if not (ok and 0 <= x0 < x1 <= image_size and 0 <= y0 < y1 <= image_size):
+            raise ValueError(f"generate: --mask_box X0 Y0 X1 Y1 needs integers with 0 <= X0 < X1 <= {image_size} and "
+                             f"0 <= Y0 < Y1 <= {image_size}, got {mask_box}")
+    if invert_to is not None:
+        if solver != "heun" or float(S_churn) != 0.0:
+            raise ValueError("generate: --invert_to runs the deterministic Heun solver upwards: no --solver dpmpp, no "
+                             "--S_churn")
+        if mask_box is not None:
+            raise ValueError("generate: --invert_to and --mask_box are exclusive")
+
+
+def load_images(init_dir, mean, std, image_size, channels) -> torch.Tensor:
+    """the PNGs of a directory as PreditionWriter names them (<index>.png), in numeric order of the index, normalised
+    as PreditionWriter denormalises (pixel = x * std * 2 + mean): fp32 [n, C, H, W] on the host"""
+    import numpy as np
+    from PIL import Image
+    names = [f for f in os.listdir(init_dir) if f.lower().endswith(".png")]
+    bad = [f for f in names if not os.path.splitext(f)[0].isdigit()]
+    if bad:
+        raise ValueError(f"generate: --init_dir holds PNGs that are not named <index>.png: {sorted(bad)[:3]}")
+    if not names:
+        raise ValueError(f"generate: no PNG in {init_dir}")
+    m = torch.tensor([float(v) for v in mean], dtype=torch.float32).view(-1, 1, 1)
+    sd = torch.tensor([float(v) for v in std], dtype=torch.float32).view(-1, 1, 1)
+    out = []
+    for f in sorted(names, key=lambda f: int(os.path.splitext(f)[0])):
+        a = np.asarray(Image.open(os.path.join(init_dir, f)))
+        a = a[:, :, None] if a.ndim == 2 else a
+        if a.dtype != np.uint8 or a.shape != (image_size, image_size, channels):
+            raise ValueError(f"generate: {f} is {a.dtype} {a.shape}, expected uint8 {(image_size, image_size, channels)}")
+        # the inverse of PreditionWriter's clamp(x * std * 2 + mean, 0, 1) * 255, truncated: level u is the bin
+        # [u, u + 1) / 255, read at its centre, so an image written and read back is written as the same levels
+        out.append(((torch.from_numpy(a.copy()).permute(2, 0, 1).float() + 0.5) / 255.0 - m) / (2.0 * sd))
+    return torch.stack(out)
+
+
 def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_classes, batch_size, num_workers=16,
              num_steps=32, *, in_channels=None, mean=None, std=None, seed=0, graph=True, model=None,
              network_dtype="f32x3", guide=None, guide_ckpt_path=None, guide_load_ema=False, guidance=1.0,
              guidance_interval=None, S_churn=0.0, S_min=0.0, S_max=float("inf"), S_noise=1.0, solver="heun",
-             solver_order=2) -> None:
+             solver_order=2, init_dir=None, start_step=0, mask_box=None, invert_to=None) -> None:
     from .callbacks import PreditionWriter
     from .datamodules import RandomNoiseDataModule
     from .edm import EDM
@@ -79,6 +147,7 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
     from .trainer import Trainer
 
     _check_solver(solver, S_churn)
+    _check_conditioning(init_dir, start_step, mask_box, invert_to, solver, S_churn, image_size)
 
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
@@ -102,26 +171,55 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
             print(f"[rank {rank}] guidance 1.0: the guide network is unused", flush=True)
     if solver == "dpmpp":
         model.solver = MultistepSolver(num_steps=num_steps, order=solver_order, guide=guide, guidance=guidance,
-                                       guidance_interval=guidance_interval)
+                                       guidance_interval=guidance_interval, seed=seed + 1000003 * rank)
     elif float(S_churn) != 0.0:     # (a negative or non-finite S_churn reaches the solver's validation)
         model.solver = StochasticSolver(num_steps=num_steps, guide=guide, guidance=guidance,
                                         guidance_interval=guidance_interval, S_churn=S_churn, S_min=S_min,
                                         S_max=S_max, S_noise=S_noise, seed=seed + 1000003 * rank)
     else:
         model.solver = DeterministicSolver(num_steps=num_steps, guide=guide, guidance=guidance,
-                                           guidance_interval=guidance_interval)
+                                           guidance_interval=guidance_interval, seed=seed + 1000003 * rank)
+    if start_step >= num_steps:
+        raise ValueError(f"generate: --start_step must be below --num_steps = {num_steps}, got {start_step}")
     from . import _runtime_env
-    if graph and _runtime_env.GRAPH_REPLAY_SAFE:      # otherwise the eager Heun loop: same values
+    graph = bool(graph and _runtime_env.GRAPH_REPLAY_SAFE)      # otherwise the eager loop: same values
+    if graph or init_dir is not None:
         solve = model.solver.solve
-        model.solver.solve = lambda m, x0, labels=None: solve(m, x0, labels, graph=True)
+        extra = {} if init_dir is None else {"start_step": start_step}
+        model.solver.solve = lambda m, x0, labels=None, **kw: solve(m, x0, labels, graph=graph, **extra, **kw)
     C = int(in_channels) if in_channels is not None else int(model.denoiser.in_channels)
     per_rank = (num_samples + world - 1) // world
     first = rank * per_rank
     n_local = max(0, min(per_rank, num_samples - first))
-    datamodule = RandomNoiseDataModule(batch_size, num_workers, image_size, n_local, num_classes, in_channels=C,
-                                       seed=seed + 1000003 * rank)
     if mean is None or std is None:
         mean, std = (CIFAR_MEAN, CIFAR_STD) if C == 3 else ((0.5,) * C, (0.25,) * C)
+    images = mask = None
+    if init_dir is not None:
+        images = load_images(init_dir, mean, std, image_size, C)
+        if images.shape[0] < num_samples:
+            raise ValueError(f"generate: --init_dir holds {images.shape[0]} images, --num_samples asks for {num_samples}")
+        images = images[first:first + n_local]
+        if mask_box is not None:
+            x0_, y0_, x1_, y1_ = (int(v) for v in mask_box)
+            mask = torch.ones(image_size, image_size, dtype=torch.uint8)      # non-zero = known pixel, kept
+            mask[y0_:y1_, x0_:x1_] = 0
+    datamodule = RandomNoiseDataModule(batch_size, num_workers, image_size, n_local, num_classes, in_channels=C,
+                                       seed=seed + 1000003 * rank, images=images, mask=mask)
+    if invert_to is not None:
+        # the labels of each batch are the ones a solve of the same --seed draws: the saved latents close the loop
+        model.eval()
+        lat, lab = [], []
+        for x0, y, img in datamodule.predict_dataloader():
+            y = y if model.conditional else None
+            lat.append(model.solver.invert(model, img, y, graph=graph, end_step=start_step).cpu())
+            lab.append(None if y is None else y.cpu())
+        if world > 1:
+            root, ext = os.path.splitext(invert_to)
+            invert_to = f"{root}.rank{rank}{ext}"
+        torch.save({"latents": torch.cat(lat) if lat else torch.empty(0), "end_step": start_step, "num_steps": num_steps,
+                    "class_labels": None if not lab or lab[0] is None else torch.cat(lab)}, invert_to)
+        print(f"[rank {rank}] wrote the latents of images {first}..{first + n_local - 1} to {invert_to}", flush=True)
+        return
     writer = PreditionWriter(output_dir=output_dir, write_interval="batch", mean=mean, std=std, first_index=first)
     trainer = Trainer(accelerator="gpu", strategy="auto", callbacks=[writer])
     if n_local > 0:
@@ -176,8 +274,25 @@ def main(argv=None):
                              "multistep, N evaluations")
     parser.add_argument("--solver_order", type=int, choices=[1, 2, 3], default=2,
                         help="order of --solver dpmpp (default 2: DPM-Solver++(2M))")
+    # image-conditioned sampling
+    parser.add_argument("--init_dir", type=str, default=None,
+                        help="directory of <index>.png images to start from (as this program writes them)")
+    parser.add_argument("--start_step", type=int, default=0,
+                        help="enter the sigma table at step K: the images are noised to sigma_K (default 0)")
+    parser.add_argument("--mask_box", type=int, nargs=4, metavar=("X0", "Y0", "X1", "Y1"), default=None,
+                        help="inpainting: regenerate the box X0 <= x < X1, Y0 <= y < Y1, keep everything outside it")
+    parser.add_argument("--invert_to", type=str, default=None, metavar="OUT.pt",
+                        help="write the latents of the --init_dir images (the ODE run upwards to --start_step) instead "
+                             "of sampling; Heun solver only")
     args = parser.parse_args(argv)
     _check_solver(args.solver, args.S_churn)
+    try:
+        _check_conditioning(args.init_dir, args.start_step, args.mask_box, args.invert_to, args.solver, args.S_churn,
+                            args.image_size)
+        if args.start_step >= args.num_steps:
+            raise ValueError(f"generate: --start_step must be below --num_steps = {args.num_steps}, got {args.start_step}")
+    except ValueError as e:
+        parser.error(str(e))
     if args.guide_ckpt_path is not None and args.guide_config_name is not None:
         parser.error("--guide_ckpt_path and --guide_config_name are exclusive")
     if args.guide_unconditional and (args.guide_ckpt_path is not None or args.guide_config_name is not None):
@@ -207,7 +322,8 @@ def main(argv=None):
              std=args.std, seed=args.seed, graph=not args.no_graph, model=model, network_dtype=args.network_dtype,
              guide=guide, guide_ckpt_path=args.guide_ckpt_path, guide_load_ema=args.guide_load_ema,
              guidance=args.guidance, guidance_interval=args.guidance_interval, S_churn=args.S_churn, S_min=args.S_min,
-             S_max=args.S_max, S_noise=args.S_noise, solver=args.solver, solver_order=args.solver_order)
+             S_max=args.S_max, S_noise=args.S_noise, solver=args.solver, solver_order=args.solver_order,
+             init_dir=args.init_dir, start_step=args.start_step, mask_box=args.mask_box, invert_to=args.invert_to)
 
 
 if __name__ == "__main__":

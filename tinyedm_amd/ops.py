@@ -1701,6 +1701,58 @@ def dpm_multistep(x, Dm, a, c0, c1=0.0, c2=0.0, Dg=None, w_dev=None, m1=None, m2
     return x_out
 
 
+def state_init(x0, t, image=None):
+    """The state of a solve at noise level t: image + t*x0 (one fma), x0 the unit noise.  image=None: x0*t, bit for bit
+    scale_f32(x0, t).  x0 / image: contiguous fp32 of one shape on one device; t finite and >= 0."""
+    _chk(x0, f32, "x0")
+    if x0.numel() == 0:
+        raise ValueError("x0: expected a non-empty tensor")
+    if image is not None:
+        _chk(image, f32, "image", x0.shape)
+        if image.device != x0.device:
+            raise ValueError(f"image: expected a tensor on {x0.device}, got {image.device}")
+    t = float(t)
+    if not (math.isfinite(t) and t >= 0.0):
+        raise ValueError(f"state_init: t must be finite and >= 0, got {t}")
+    out = torch.empty_like(x0)
+    _lib.call("edm_state_init", _p(image), _p(x0), t, _p(out), x0.numel(), _p(health(x0.device)), _stream())
+    return out
+
+
+INPAINT_MAX_STEPS = 1 << 16     # step < 2**16 keeps the blend's Philox tag apart from the churn's for every pair of steps
+
+
+def inpaint_blend(x, image, mask, t, rec, step):
+    """out = mask ? image + t*n : x with n ~ N(0, 1) drawn in the kernel (the replacement step of inpainting).  x, image:
+    contiguous fp32 [B, C, ...]; mask: contiguous uint8 [mask_B, HW] with mask_B in {1, B} and HW the number of pixels,
+    non-zero = known pixel, broadcast over the channels (and the batch when mask_B == 1); rec: the device record of
+    ops.churn_record (seed, solve index); step: the solver step, part of the Philox counter.  The noise of sample b
+    depends only on (seed, solve index, step, b, element) and is independent of heun_churn's.  t == 0 gives image itself
+    on the mask."""
+    _chk(x, f32, "x")
+    if x.dim() < 3 or x.numel() == 0:
+        raise ValueError(f"x: expected a non-empty [B, C, ...] tensor, got {tuple(x.shape)}")
+    _chk(image, f32, "image", x.shape)
+    _chk(mask, torch.uint8, "mask")
+    B, C = x.shape[0], x.shape[1]
+    HW = x.numel() // (B * C)
+    if mask.dim() != 2 or mask.shape[0] not in (1, B) or mask.shape[1] != HW:
+        raise ValueError(f"mask: expected uint8 [1 or {B}, {HW}], got {tuple(mask.shape)}")
+    for tt, nme in ((image, "image"), (mask, "mask")):
+        if tt.device != x.device:
+            raise ValueError(f"{nme}: expected a tensor on {x.device}, got {tt.device}")
+    _churn_rec(rec, x)
+    t, step = float(t), int(step)
+    if not (math.isfinite(t) and t >= 0.0):
+        raise ValueError(f"inpaint_blend: t must be finite and >= 0, got {t}")
+    if not 0 <= step < INPAINT_MAX_STEPS:
+        raise ValueError(f"inpaint_blend: step must be in [0, {INPAINT_MAX_STEPS}), got {step}")
+    out = torch.empty_like(x)
+    _lib.call("edm_inpaint_blend", _p(x), _p(image), _p(mask), t, _p(rec), step, B, C, HW, mask.shape[0], _p(out),
+              _p(health(x.device)), _stream())
+    return out
+
+
 def scale_f32(x, s):
     _chk(x, f32, "x")
     y = torch.empty_like(x)

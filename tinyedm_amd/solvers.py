@@ -25,6 +25,27 @@ def _release_solves(per_model: dict):
         pass
 
 
+class _Conditioning(NamedTuple):
+    """the image conditioning of one solve (a captured entry owns static copies)"""
+    start: int              # the step the solve enters at: x_start = image + t_start * x0
+    image: object           # fp32 [B, C, H, W] or None (= 0)
+    mask: object            # uint8 [1 or B, H*W], non-zero = known pixel, or None
+    rec: object             # the device record of the inpainting noise (ops.churn_record), or None without a mask
+
+
+def _mask_u8(mask, shape):
+    """a bool / uint8 / float mask of shape [B,1,H,W], [1,1,H,W] or [H,W] as uint8 [B or 1, H*W] (non-zero = known)"""
+    B, _, H, W = shape
+    if not isinstance(mask, torch.Tensor):
+        raise ValueError(f"solve: mask must be a tensor, got {type(mask).__name__}")
+    if not (mask.dtype in (torch.bool, torch.uint8) or mask.dtype.is_floating_point):
+        raise ValueError(f"solve: mask must be bool, uint8 or floating point, got {mask.dtype}")
+    if tuple(mask.shape) not in {(B, 1, H, W), (1, 1, H, W), (H, W)}:
+        raise ValueError(f"solve: mask must have shape {(B, 1, H, W)}, {(1, 1, H, W)} or {(H, W)}, got "
+                         f"{tuple(mask.shape)}")
+    return (mask != 0).to(torch.uint8).reshape(-1, H * W).contiguous()
+
+
 class DeterministicSolver:
     """Algorithm 1 of Karras et al. 2022 with sigma(t)=t, s(t)=1.  Same constructor as the reference.
 
@@ -44,14 +65,27 @@ class DeterministicSolver:
     evaluations with lo < sigma <= hi (sigma = the fp32 table value) are guided; the others use D_main alone and do not
     evaluate the guide.  ``guidance == 1`` guides nothing: the guide is never evaluated and the solve is the unguided
     one.  ``guidance`` and ``guidance_interval`` are plain attributes, read at every solve; a captured solve reads the
-    guidance weight from device memory, so changing it replays the same graph."""
+    guidance weight from device memory, so changing it replays the same graph.
+
+    Image-conditioned sampling (keyword-only arguments of ``solve``; the defaults are the plain solve, bit for bit):
+    ``start_step=k`` enters the table at t_k with the state x_k = image + t_k * x0 (``image`` defaults to 0, x0 is unit
+    noise) and runs the steps i >= k only: SDEdit / image-to-image.  ``mask`` (with ``image``) is inpainting by
+    replacement (Song et al. 2021; RePaint without its resampling jumps): before the Euler evaluation of every step
+    i >= k the pixels where the mask is non-zero are replaced by image + t_i * n with fresh n ~ N(0, I), and after the
+    last step by the image itself, so the result equals ``image`` there bit for bit.  That is N - k + 1 blends
+    (ops.inpaint_blend) and no extra network evaluation.  The mask is binary (non-zero = known pixel, kept); soft masks
+    and RePaint's resampling are not implemented.  The noise comes from ``seed`` and ``solve_index`` as the churn of
+    StochasticSolver does, under a Philox tag of its own; ``solve_index`` increments after every inpainting solve.
+    ``invert`` runs the probability-flow ODE upwards, image -> latent."""
 
     MAX_GRAPHS = 4      # captured solves kept per model (shape / precision combinations; least recently used dropped)
 
     def __init__(self, num_steps: int = 18, sigma_min: float = 0.002, sigma_max: float = 80.0, rho: float = 7.0,
                  dtype: str | None = None, *, guide=None, guidance: float = 1.0,
-                 guidance_interval: tuple[float, float] | None = None):
+                 guidance_interval: tuple[float, float] | None = None, seed: int = 0):
         self.num_steps = num_steps
+        self.seed = seed
+        self.solve_index = 0
         self.sigma_min = sigma_min
         self.sigma_max = sigma_max
         self.rho = rho
@@ -67,6 +101,7 @@ class DeterministicSolver:
         self.guidance = guidance
         self.guidance_interval = guidance_interval
         self.guided_evaluations()                       # (validates guidance and guidance_interval)
+        self._check_stream()
 
     # ------------------------------------------------------------------ guidance
     def guided_evaluations(self) -> tuple[bool, ...]:
@@ -97,12 +132,52 @@ class DeterministicSolver:
         ts = self.t_steps.tolist()
         return [ts[i // 2 + i % 2] for i in range(2 * self.num_steps - 1)]
 
+    def _check_stream(self) -> None:
+        """the seed and solve index of the in-kernel noise (inpainting; the churn of StochasticSolver)"""
+        _check_uint(self.seed, 64, "seed")
+        _check_uint(self.solve_index, 32, "solve_index")
+
+    # ------------------------------------------------------------------ image conditioning
+    def _conditioning(self, x0, start_step, image, mask):
+        """Validate start_step / image / mask of a solve against x0 on the host (shapes, dtypes and devices: nothing is
+        read from a device) and return (start, image, mask as uint8 [B or 1, H*W]); None for the plain solve."""
+        if isinstance(start_step, bool) or not isinstance(start_step, int) or not 0 <= start_step < self.num_steps:
+            raise ValueError(f"solve: start_step must be an integer in [0, {self.num_steps - 1}], got {start_step!r}")
+        if mask is not None and image is None:
+            raise ValueError("solve: mask needs image (the known pixels)")
+        if image is None and start_step == 0:
+            return None
+        if image is not None:
+            if not isinstance(image, torch.Tensor) or not image.dtype.is_floating_point:
+                raise ValueError("solve: image must be a floating-point tensor")
+            if tuple(image.shape) != tuple(x0.shape):
+                raise ValueError(f"solve: image must have x0's shape {tuple(x0.shape)}, got {tuple(image.shape)}")
+        if mask is not None:
+            if x0.dim() != 4:
+                raise ValueError(f"solve: a mask needs x0 of shape [B, C, H, W], got {tuple(x0.shape)}")
+            mask = _mask_u8(mask, x0.shape)
+            self._check_stream()
+            if self.num_steps >= ops.INPAINT_MAX_STEPS:
+                raise ValueError(f"solve: inpainting needs num_steps < {ops.INPAINT_MAX_STEPS}")
+        for t, name in ((image, "image"), (mask, "mask")):
+            if t is not None and t.device != x0.device:
+                raise ValueError(f"solve: {name} is on {t.device}, x0 on {x0.device}")
+        return start_step, image, mask
+
+    def _blend(self, x, cond, t, step):
+        return ops.inpaint_blend(x, cond.image, cond.mask, t, cond.rec, step)
+
+    def _solve_done(self, masked: bool) -> None:
+        """after every solve: an inpainting solve has used up the noise of solve_index"""
+        if masked:
+            self.solve_index += 1
+
     # ------------------------------------------------------------------ subclass hooks (StochasticSolver)
-    def _graph_key_extra(self) -> tuple:
+    def _graph_key_extra(self, start_step: int = 0) -> tuple:
         """what the subclass adds to the key of a captured solve"""
         return ()
 
-    def _solve_state(self, x0):
+    def _solve_state(self, x0, start_step: int = 0):
         """per-solve device tensors the loop reads (a captured entry owns its own), written for this solve; or None.
         x0: the solve's fp32 initial noise (its shape and device)"""
         return None
@@ -146,10 +221,14 @@ class DeterministicSolver:
         return self.guide(x, sigma, class_labels).float().contiguous()
 
     # ------------------------------------------------------------------ eager
-    def _loop(self, model, x0, class_labels, t_dev, guided, w_dev, state=None):
+    def _loop(self, model, x0, class_labels, t_dev, guided, w_dev, state=None, cond=None):
         ts = self.t_steps.tolist()
-        x1 = ops.scale_f32(x0, ts[0])
-        for i in range(self.num_steps):
+        k = 0 if cond is None else cond.start
+        masked = cond is not None and cond.mask is not None
+        x1 = ops.scale_f32(x0, ts[0]) if cond is None else ops.state_init(x0, ts[k], cond.image)
+        for i in range(k, self.num_steps):
+            if masked:
+                x1 = self._blend(x1, cond, ts[i], i)
             x, t0, s0 = self._step_start(x1, i, ts, t_dev, state)
             t1 = ts[i + 1]
             D = model(x, s0, class_labels).float().contiguous()
@@ -165,10 +244,13 @@ class DeterministicSolver:
                     x1 = ops.heun_correct_guided(x, dx, x1, D1, Dg1, w_dev, t0, t1)
                 else:
                     x1 = ops.heun_correct(x, dx, x1, D1, t0, t1)
+        if masked:
+            x1 = self._blend(x1, cond, 0.0, self.num_steps)
         return x1
 
     @torch.no_grad()
-    def solve(self, model, x0, class_labels=None, graph: bool = False):
+    def solve(self, model, x0, class_labels=None, graph: bool = False, *, start_step: int = 0, image=None, mask=None):
+        cond = self._conditioning(x0, start_step, image, mask)
         if not x0.is_cuda:
             raise RuntimeError("tinyedm_amd.DeterministicSolver: x0 must be a GPU tensor (there is no CPU path)")
         guided = self.guided_evaluations()
@@ -176,19 +258,67 @@ class DeterministicSolver:
             self._check_guide(model, x0.device, class_labels)
         in_dtype = x0.dtype
         x0 = x0.float().contiguous()
+        masked = False
+        if cond is not None:
+            k, image, mask = cond
+            masked = mask is not None
+            cond = _Conditioning(k, None if image is None else image.float().contiguous(), mask,
+                                 ops.churn_record(self.seed, self.solve_index, x0.device) if masked else None)
         if not graph:
             t_dev = self.t_steps.to(x0.device)
             w_dev = torch.full((1,), float(self.guidance), device=x0.device) if any(guided) else None
-            state = self._solve_state(x0)
-            return self._loop(model, x0, class_labels, t_dev, guided, w_dev, state).to(in_dtype)
-        out = self._solve_graphed(model, x0, class_labels, guided).to(in_dtype)
+            state = self._solve_state(x0, 0 if cond is None else cond.start)
+            out = self._loop(model, x0, class_labels, t_dev, guided, w_dev, state, cond).to(in_dtype)
+            self._solve_done(masked)
+            return out
+        out = self._solve_graphed(model, x0, class_labels, guided, cond).to(in_dtype)
         # the Heun kernels leave a bit in the device health word when the state went non-finite: a replay that ran
         # with corrupted arguments fails HERE, loudly (one host sync per solve of 2N-1 network evaluations)
         ops.check_health(x0.device, "DeterministicSolver.solve(graph=True)")
+        self._solve_done(masked)
+        return out
+
+    # ------------------------------------------------------------------ inversion
+    def _check_invert(self) -> None:
+        """which solvers can run the ODE upwards (subclasses refuse)"""
+
+    def _invert_loop(self, model, image, class_labels, t_dev, end_step):
+        ts = self.t_steps.tolist()
+        x = image
+        for i in range(self.num_steps - 1, end_step, -1):        # a full Heun step t_i -> t_{i-1}
+            t0, t1 = ts[i], ts[i - 1]
+            D = model(x, t_dev[i], class_labels).float().contiguous()
+            dx, x1 = ops.heun_euler(x, D, t0, t1)
+            D1 = model(x1, t_dev[i - 1], class_labels).float().contiguous()
+            x = ops.heun_correct(x, dx, x1, D1, t0, t1)
+        return ops.scale_f32(x, 1.0 / ts[end_step])
+
+    @torch.no_grad()
+    def invert(self, model, image, class_labels=None, graph: bool = False, *, end_step: int = 0):
+        """Encode: run the probability-flow ODE up the sigma table, image -> latent.  ``image`` is taken as the state at
+        t_{N-1} (sigma_min noise is negligible), the steps t_{N-1} -> t_{N-2} -> ... -> t_k, k = ``end_step``, are
+        full Heun steps (Euler + correction, the kernels of ``solve``: their algebra does not care about the
+        direction), 2(N - 1 - k) network evaluations.  Returns the UNIT-SCALE latent x_k / t_k, the convention of
+        ``solve``'s x0: ``solve(model, invert(model, img, end_step=k), start_step=k)`` closes the loop.  Only D_main is
+        evaluated: guided inversion is not implemented, ``guide`` and ``guidance`` are ignored here."""
+        self._check_invert()
+        if isinstance(end_step, bool) or not isinstance(end_step, int) or not 0 <= end_step < self.num_steps:
+            raise ValueError(f"invert: end_step must be an integer in [0, {self.num_steps - 1}], got {end_step!r}")
+        if not isinstance(image, torch.Tensor) or not image.dtype.is_floating_point:
+            raise ValueError("invert: image must be a floating-point tensor")
+        if not image.is_cuda:
+            raise RuntimeError("tinyedm_amd.DeterministicSolver: image must be a GPU tensor (there is no CPU path)")
+        in_dtype = image.dtype
+        image = image.float().contiguous()
+        if not graph:
+            return self._invert_loop(model, image, class_labels, self.t_steps.to(image.device), end_step).to(in_dtype)
+        out = self._solve_graphed(model, image, class_labels, (), None, end_step).to(in_dtype)
+        ops.check_health(image.device, "DeterministicSolver.invert(graph=True)")
         return out
 
     # ------------------------------------------------------------------ hipGraph
-    def _solve_graphed(self, model, x0, class_labels, guided):
+    def _solve_graphed(self, model, x0, class_labels, guided, cond=None, invert_to=None):
+        """replay (after capturing, the first time) the solve, or with invert_to = its end step the inversion of x0"""
         # graphs are cached PER MODEL OBJECT (weakly: a new model allocated at a dead one's address must not replay the
         # dead one's graph, which id(model) as a key allowed)
         owner = getattr(model, "__self__", model)        # a bound method is a fresh object per access: key on its object
@@ -215,7 +345,13 @@ class DeterministicSolver:
             key += ((UNCONDITIONAL,), guided)
         elif guide is not None:
             key += (id(guide), eval_dtypes(guide), guided)
-        key += self._graph_key_extra()
+        if invert_to is not None:
+            key += ("invert", invert_to)
+        else:
+            key += self._graph_key_extra(0 if cond is None else cond.start)
+        if cond is not None:        # (the plain solve keeps the key it always had)
+            key += ("conditioned", cond.start, cond.image is not None,
+                    None if cond.mask is None else tuple(cond.mask.shape))
         ent = per_model.get(key)
         if ent is None:
             _runtime_env.require_graph_replay_safe("DeterministicSolver.solve(graph=True)")
@@ -223,20 +359,29 @@ class DeterministicSolver:
             w_dev = None if guide is None else torch.full((1,), float(self.guidance), device=x0.device)
             if _is_unconditional(guide):
                 guide = None
-            state = self._solve_state(x0)
+            state = None if invert_to is not None else self._solve_state(x0, 0 if cond is None else cond.start)
             sx = x0.clone()
             sl = None if class_labels is None else class_labels.clone()
+            # the entry's own image, mask and noise record: copied / rewritten before every replay, as sx and sl are
+            sc = None if cond is None else _Conditioning(cond.start, *(None if v is None else v.clone()
+                                                                      for v in cond[1:]))
+            if invert_to is not None:
+                def loop():
+                    return self._invert_loop(model, sx, sl, t_dev, invert_to)
+            else:
+                def loop():
+                    return self._loop(model, sx, sl, t_dev, guided, w_dev, state, sc)
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):          # warm-up outside capture (weight packs, lazy inits)
-                self._loop(model, sx, sl, t_dev, guided, w_dev, state)
+                loop()
             torch.cuda.current_stream().wait_stream(side)
             g = torch.cuda.CUDAGraph()
             ops.capture_begin()
             ok = False
             try:
                 with torch.cuda.graph(g):
-                    out = self._loop(model, sx, sl, t_dev, guided, w_dev, state)
+                    out = loop()
                 ok = True
             finally:
                 token = ops.capture_end()
@@ -246,11 +391,17 @@ class DeterministicSolver:
                 old = per_model.pop(next(iter(per_model)))
                 torch.cuda.synchronize()
                 ops.release_capture(old[5])
-            ent = per_model[key] = (g, sx, sl, out, t_dev, token, w_dev, guide, state)
+            ent = per_model[key] = (g, sx, sl, out, t_dev, token, w_dev, guide, state, sc)
         else:
             per_model[key] = per_model.pop(key)              # most recently used last
             self._write_solve_state(ent[8])
-        g, sx, sl, out, _, _, w_dev, _, _ = ent
+        g, sx, sl, out, _, _, w_dev, _, _, sc = ent
+        if sc is not None:
+            if sc.image is not None:
+                sc.image.copy_(cond.image)
+            if sc.mask is not None:
+                sc.mask.copy_(cond.mask)
+                sc.rec.copy_(cond.rec)
         # the captured evaluations read the persistent eval-mode weight packs: refresh them (a no-op unless the
         # master weights changed since the last solve: optimizer steps, EMA swap, load_state_dict) before replaying
         from .networks import Denoiser
@@ -314,10 +465,8 @@ class StochasticSolver(DeterministicSolver):
         self.S_min = S_min
         self.S_max = S_max
         self.S_noise = S_noise
-        self.seed = seed
-        self.solve_index = 0
         super().__init__(num_steps, sigma_min, sigma_max, rho, dtype, guide=guide, guidance=guidance,
-                         guidance_interval=guidance_interval)     # (validates the churn settings too)
+                         guidance_interval=guidance_interval, seed=seed)    # (validates the churn settings too)
 
     def churn_schedule(self) -> ChurnSchedule:
         """gamma_i, t_hat_i and c_i of every step, computed in fp64 from the fp32 sigma table and rounded to fp32
@@ -349,11 +498,11 @@ class StochasticSolver(DeterministicSolver):
         ts = self.t_steps.tolist()
         return [th[i // 2] if i % 2 == 0 else ts[i // 2 + 1] for i in range(2 * self.num_steps - 1)]
 
-    def _graph_key_extra(self) -> tuple:
+    def _graph_key_extra(self, start_step: int = 0) -> tuple:
         steps = self._churn_steps()
         return (steps,) if any(s[0] for s in steps) else ()
 
-    def _solve_state(self, x0):
+    def _solve_state(self, x0, start_step: int = 0):
         steps = self._churn_steps()
         if not any(s[0] for s in steps):
             return None
@@ -370,11 +519,13 @@ class StochasticSolver(DeterministicSolver):
         _, t_hat, c = state.steps[i]
         return ops.heun_churn(x, c, state.rec, i), t_hat, state.t_hat[i]
 
-    @torch.no_grad()
-    def solve(self, model, x0, class_labels=None, graph: bool = False):
-        out = super().solve(model, x0, class_labels, graph)
-        self.solve_index += 1
-        return out
+    def _solve_done(self, masked: bool) -> None:
+        self.solve_index += 1           # every solve, churned or not, draws from its own index
+
+    def _check_invert(self) -> None:
+        if any(s[0] for s in self._churn_steps()):
+            raise ValueError("StochasticSolver.invert: a churned solve is not an ODE and has no inverse; set S_churn = 0 "
+                             "(or use DeterministicSolver)")
 
 
 class _MultistepState(NamedTuple):
@@ -407,16 +558,20 @@ class MultistepSolver(DeterministicSolver):
 
     def __init__(self, num_steps: int = 18, sigma_min: float = 0.002, sigma_max: float = 80.0, rho: float = 7.0,
                  dtype: str | None = None, *, order: int = 2, guide=None, guidance: float = 1.0,
-                 guidance_interval: tuple[float, float] | None = None):
+                 guidance_interval: tuple[float, float] | None = None, seed: int = 0):
         _check_multistep(num_steps, order)
         self.order = order
         super().__init__(num_steps, sigma_min, sigma_max, rho, dtype, guide=guide, guidance=guidance,
-                         guidance_interval=guidance_interval)
+                         guidance_interval=guidance_interval, seed=seed)
 
-    def _steps(self) -> tuple:
-        """(k_i, a_i, c0_i, c1_i, c2_i) per step: the effective order and the fp32 coefficients as host floats"""
+    def _steps(self, start_step: int = 0) -> tuple:
+        """(k_i, a_i, c0_i, c1_i, c2_i) per step: the effective order and the fp32 coefficients as host floats.  A
+        solve entering at start_step has no history there: k_i = min(order, i - start_step + 1) (the rows before
+        start_step are those of a full solve; such a solve does not run them)"""
         _check_multistep(self.num_steps, self.order)
         N, order = self.num_steps, int(self.order)
+        if isinstance(start_step, bool) or not isinstance(start_step, int) or not 0 <= start_step < N:
+            raise ValueError(f"MultistepSolver: start_step must be an integer in [0, {N - 1}], got {start_step!r}")
         sig = self.t_steps.double().tolist()                # fp64 from the fp32 table
         lam = [-math.log(v) for v in sig[:N]]               # lambda_N = +inf
         steps = []
@@ -424,7 +579,7 @@ class MultistepSolver(DeterministicSolver):
             if i == N - 1:                                  # h = inf: a = 0, e = -1
                 steps.append((1, 0.0, 1.0, 0.0, 0.0))
                 continue
-            k = min(order, i + 1)
+            k = min(order, i + 1 if i < start_step else i - start_step + 1)
             h = lam[i + 1] - lam[i]
             a = sig[i + 1] / sig[i]
             e = math.expm1(-h)
@@ -448,33 +603,47 @@ class MultistepSolver(DeterministicSolver):
         return tuple((k,) + tuple(torch.tensor(row, dtype=torch.float64).float().tolist())
                      for k, *row in steps)
 
-    def multistep_coefficients(self) -> torch.Tensor:
+    def multistep_coefficients(self, start_step: int = 0) -> torch.Tensor:
         """(N, 4) fp32 tensor of the rows (a_i, c0_i, c1_i, c2_i): computed in fp64 from the fp32 sigma table, rounded to
-        fp32.  The last row is (0, 1, 0, 0).  Host only; raises ValueError on an invalid order or num_steps."""
-        return torch.tensor([s[1:] for s in self._steps()], dtype=torch.float32)
+        fp32.  The last row is (0, 1, 0, 0).  With start_step = k the order restarts there (row k is first order), as in
+        solve(..., start_step=k).  Host only; raises ValueError on an invalid order, num_steps or start_step."""
+        return torch.tensor([s[1:] for s in self._steps(start_step)], dtype=torch.float32)
 
     def _evaluation_sigmas(self) -> list[float]:
         """one evaluation per step, at sigma_0 ... sigma_{N-1}"""
         _check_multistep(self.num_steps, self.order)
         return self.t_steps.tolist()[:self.num_steps]
 
-    def _graph_key_extra(self) -> tuple:
+    def _graph_key_extra(self, start_step: int = 0) -> tuple:
         # the coefficients are kernel arguments baked into a capture: a new order is a new graph
-        return ("multistep", self._steps())
+        return ("multistep", self._steps(start_step))
 
-    def _solve_state(self, x0):
-        steps = self._steps()
+    def _check_invert(self) -> None:
+        raise ValueError("MultistepSolver.invert: a multistep inversion is not implemented; invert with "
+                         "DeterministicSolver (Heun) on the same sigma table")
+
+    def _solve_state(self, x0, start_step: int = 0):
+        steps = self._steps(start_step)
         L = int(self.order) if self.order > 1 else 0
         return _MultistepState(tuple(torch.empty_like(x0) for _ in range(L)), steps)
 
-    def _loop(self, model, x0, class_labels, t_dev, guided, w_dev, state=None):
+    def _loop(self, model, x0, class_labels, t_dev, guided, w_dev, state=None, cond=None):
         hist, N = state.hist, self.num_steps
         L = len(hist)
-        x = ops.scale_f32(x0, self.t_steps[0].item())
+        ts = self.t_steps.tolist()
+        start = 0 if cond is None else cond.start
+        masked = cond is not None and cond.mask is not None
+        x = ops.scale_f32(x0, self.t_steps[0].item()) if cond is None else ops.state_init(x0, ts[start], cond.image)
         for i, (k, a, c0, c1, c2) in enumerate(state.steps):
+            if i < start:
+                continue
+            if masked:
+                x = self._blend(x, cond, ts[i], i)
             D = model(x, t_dev[i], class_labels).float().contiguous()
             Dg = self._guide_eval(model, x, t_dev[i], class_labels) if guided[i] else None
             x = ops.dpm_multistep(x, D, a, c0, c1, c2, Dg=Dg, w_dev=None if Dg is None else w_dev,
                                   m1=hist[(i - 1) % L] if k >= 2 else None, m2=hist[(i - 2) % L] if k >= 3 else None,
                                   m_out=hist[i % L] if L and i < N - 1 else None)
+        if masked:
+            x = self._blend(x, cond, 0.0, N)
         return x
