@@ -463,6 +463,40 @@ int edm_state_init(const float* image, const float* x0, float t, float* out, lon
  * Same health bit as the Heun updates. */
 int edm_inpaint_blend(const float* x, const float* image, const unsigned char* mask, float t, const void* rec, int step,
                       int B, int C, long HW, int mask_B, float* out, unsigned* health, edm_stream_t stream);
+/* Likelihood evaluation along the probability-flow ODE dx/dt = (x - D(x; t)) / t: the Heun updates plus the integral of
+ * the drift's divergence (CHW - tr dD/dx) / t, the trace estimated without a backward pass (Hutchinson with Rademacher
+ * probes, central difference through the network):
+ *   q_b = 1/K sum_p sum_j eps_pj (D(x + h eps_p)_bj - D(x - h eps_p)_bj) / (2h).
+ * An evaluation batch is [(1 + 2K) B, CHW] fp32: rows [0, B) the state x, rows [(1 + 2p) B, (2 + 2p) B) x + h eps_p,
+ * rows [(2 + 2p) B, (3 + 2p) B) x - h eps_p (one fp32 add each), 1 <= K <= 32.  eps is never stored: element j of sample
+ * b (j over CHW) takes bit p of word j % 4 of one Philox4x32-10 call with counter
+ * (j / 4, b, (0x4E4C0000 + (ev << 16)) ^ step, solve_index) and key (seed_lo, seed_hi); bit clear = +1, set = -1; ev = 0
+ * for the Euler evaluation of step `step`, 1 for its correction; step < 65536, so the tags differ from the churn's
+ * 0x43480000 and the blend's 0x49500000 whatever the steps are.  rec is the churn's DEVICE record {seed_lo, seed_hi,
+ * solve_index, 0}, read at run time.  The bits do not depend on B or on the memory path (dwordx4 when CHW % 4 == 0 and
+ * every fp32 operand is 16-byte aligned, else element by element).  Outputs alias no operand.
+ * Reductions are order-fixed (no floating-point atomics): per-(sample, chunk) fp64 partials go to `part`, a DEVICE
+ * workspace of B * EDM_NLL_MAX_CHUNKS doubles, and a one-thread-per-sample finish launch adds them in index order into
+ * L, DEVICE fp64 [B], += in place.  Same health bit as the Heun updates (also set when L goes non-finite).
+ *
+ * edm_nll_probe: E = the evaluation batch of x [B, CHW] with half-width h under (step, ev).
+ * edm_heun_euler_div: edm_heun_euler on rows [0, B) of (E, D): dx [B, CHW], and E1 = the evaluation batch of x1 with
+ *   half-width h1 under (step, 1);  L_b += (t1 - t0) / 2 * (CHW - q_b) / t0 with q_b from D under (step, 0) and h0.
+ * edm_heun_correct_div: edm_heun_correct on rows [0, B) of (E, dx, E1, D1): out = the evaluation batch of the new state
+ *   with half-width hn under (step - 1, 0) (the next step's Euler evaluation) when probes_out != 0, else the new state
+ *   alone, [B, CHW];  L_b += (t1 - t0) / 2 * (CHW - q_b) / t1 with q_b from D1 under (step, 1) and h1.
+ * edm_nll_prior: L_b += log N(x_b; 0, t^2 I) = -CHW/2 log(2 pi t^2) - sum_j (x_bj / t)^2 / 2, x [B, CHW]. */
+#define EDM_NLL_MAX_CHUNKS 64
+int edm_nll_probe(const float* x, float h, const void* rec, int step, int ev, int K, int B, long CHW, float* E,
+                  unsigned* health, edm_stream_t stream);
+int edm_heun_euler_div(const float* E, const float* D, float t0, float t1, float h0, float h1, const void* rec, int step,
+                       int K, int B, long CHW, float* dx, float* E1, double* part, double* L, unsigned* health,
+                       edm_stream_t stream);
+int edm_heun_correct_div(const float* E, const float* dx, const float* E1, const float* D1, float t0, float t1, float h1,
+                         float hn, const void* rec, int step, int K, int probes_out, int B, long CHW, float* out,
+                         double* part, double* L, unsigned* health, edm_stream_t stream);
+int edm_nll_prior(const float* x, float t, int B, long CHW, double* part, double* L, unsigned* health,
+                  edm_stream_t stream);
 int edm_scale_f32(const float* x, float s, float* y, long n, edm_stream_t stream);
 
 /* ---------------------------------------------------------------- reference-precision evaluation (eval_f32.hip)

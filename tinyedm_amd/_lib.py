@@ -111,6 +111,10 @@ SIGNATURES = {
     "edm_dpm_multistep": [P, P, P, P, P, P, F, F, F, F, P, P, L, P, P],
     "edm_state_init": [P, P, F, P, L, P, P],
     "edm_inpaint_blend": [P, P, P, F, P, I, I, I, L, I, P, P, P],
+    "edm_nll_probe": [P, F, P, I, I, I, I, L, P, P, P],
+    "edm_heun_euler_div": [P, P, F, F, F, F, P, I, I, I, L, P, P, P, P, P, P],
+    "edm_heun_correct_div": [P, P, P, P, F, F, F, F, P, I, I, I, I, L, P, P, P, P, P],
+    "edm_nll_prior": [P, F, I, L, P, P, P, P],
     "edm_scale_f32": [P, F, P, L, P],
     # weights.hip
     "edm_weight_prep": [P, I, I, I, I, P, P, P, P, I, P],

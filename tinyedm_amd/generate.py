@@ -51,6 +51,11 @@ X0 <= x < X1, Y0 <= y < Y1 and keeps everything outside the box, which comes out
 with each other, with guidance, churn and `--solver dpmpp`.  `--invert_to OUT.pt` (Heun solver only) writes no images:
 it runs the ODE upwards from each image to sigma_K and saves {"latents", "class_labels", "end_step", "num_steps"}, the
 unit-scale latents that `solve(..., start_step=K)` turns back into the images.  Without `--init_dir` nothing changes.
+`--likelihood_to OUT.json` (Heun solver only, `--network_dtype f32x3` or `f32`) writes no images either: it evaluates
+log p of each image along the same upward ODE (DeterministicSolver.log_likelihood, `--num_probes K` Rademacher probes
+per evaluation) and saves {"logp", "bpd", "logp_mean", "bpd_mean", "num_steps", "end_step", "num_probes", "delta", "seed",
+"network_dtype"}: nats of the normalised image and bits per dimension in pixel units.  `--dequantize` first adds
+U[0, 1) / 255 in pixel units, drawn from `--seed` on the host: the usual uniform dequantisation of discrete images.
 
     python -m tinyedm.generate --ckpt_path last.ckpt --load_ema --init_dir photos --start_step 12 \\
         --output_dir variations --num_samples 64 --image_size 32 --num_classes 10 --batch_size 64
@@ -59,6 +64,9 @@ unit-scale latents that `solve(..., start_step=K)` turns back into the images.  
         --output_dir inpainted --num_samples 64 --image_size 32 --num_classes 10 --batch_size 64
 
     python -m tinyedm.generate --ckpt_path last.ckpt --load_ema --init_dir photos --invert_to latents.pt \\
+        --output_dir unused --num_samples 64 --image_size 32 --num_classes 10 --batch_size 64
+
+    python -m tinyedm.generate --ckpt_path last.ckpt --load_ema --init_dir photos --likelihood_to bpd.json --dequantize \\
         --output_dir unused --num_samples 64 --image_size 32 --num_classes 10 --batch_size 64
 Multi-GPU = replicas only: under `python -m torch.distributed.run --nproc-per-node N` every rank samples
 its own contiguous index range with its own noise seed and writes `<global index>.png`; there is no collective.
@@ -83,13 +91,14 @@ def _check_solver(solver, S_churn) -> None:
                          "sampling is --solver heun)")
 
 
-def _check_conditioning(init_dir, start_step, mask_box, invert_to, solver, S_churn, image_size) -> None:
+def _check_conditioning(init_dir, start_step, mask_box, invert_to, solver, S_churn, image_size, *, likelihood_to=None,
+                        network_dtype="f32x3", num_probes=1, dequantize=False) -> None:
     """the image-conditioning choices that need nothing loaded"""
     if isinstance(start_step, bool) or not isinstance(start_step, int) or start_step < 0:
         raise ValueError(f"generate: --start_step must be an integer >= 0, got {start_step!r}")
     if init_dir is None:
         for flag, on in (("--mask_box", mask_box is not None), ("--start_step", start_step > 0),
-                         ("--invert_to", invert_to is not None)):
+                         ("--invert_to", invert_to is not None), ("--likelihood_to", likelihood_to is not None)):
             if on:
                 raise ValueError(f"generate: {flag} needs --init_dir (the images to start from)")
         return
@@ -108,6 +117,23 @@ def _check_conditioning(init_dir, start_step, mask_box, invert_to, solver, S_chu
                              "--S_churn")
         if mask_box is not None:
             raise ValueError("generate: --invert_to and --mask_box are exclusive")
+    if isinstance(num_probes, bool) or not isinstance(num_probes, int) or not 1 <= num_probes <= 32:
+        raise ValueError(f"generate: --num_probes must be an integer in [1, 32], got {num_probes!r}")
+    if likelihood_to is None:
+        for flag, on in (("--num_probes", num_probes != 1), ("--dequantize", bool(dequantize))):
+            if on:
+                raise ValueError(f"generate: {flag} needs --likelihood_to")
+        return
+    if solver != "heun" or float(S_churn) != 0.0:
+        raise ValueError("generate: --likelihood_to runs the deterministic Heun solver upwards: no --solver dpmpp, no "
+                         "--S_churn")
+    if mask_box is not None:
+        raise ValueError("generate: --likelihood_to and --mask_box are exclusive")
+    if invert_to is not None:
+        raise ValueError("generate: --likelihood_to and --invert_to are exclusive (one output per run)")
+    if network_dtype == "bf16":
+        raise ValueError("generate: --likelihood_to needs --network_dtype f32x3 or f32 (a difference quotient at bf16 "
+                         "evaluation error is meaningless)")
 
 
 def load_images(init_dir, mean, std, image_size, channels) -> torch.Tensor:
@@ -139,7 +165,8 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
              num_steps=32, *, in_channels=None, mean=None, std=None, seed=0, graph=True, model=None,
              network_dtype="f32x3", guide=None, guide_ckpt_path=None, guide_load_ema=False, guidance=1.0,
              guidance_interval=None, S_churn=0.0, S_min=0.0, S_max=float("inf"), S_noise=1.0, solver="heun",
-             solver_order=2, init_dir=None, start_step=0, mask_box=None, invert_to=None) -> None:
+             solver_order=2, init_dir=None, start_step=0, mask_box=None, invert_to=None, likelihood_to=None,
+             num_probes=1, dequantize=False) -> None:
     from .callbacks import PreditionWriter
     from .datamodules import RandomNoiseDataModule
     from .edm import EDM
@@ -147,7 +174,9 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
     from .trainer import Trainer
 
     _check_solver(solver, S_churn)
-    _check_conditioning(init_dir, start_step, mask_box, invert_to, solver, S_churn, image_size)
+    _check_conditioning(init_dir, start_step, mask_box, invert_to, solver, S_churn, image_size,
+                        likelihood_to=likelihood_to, network_dtype=network_dtype, num_probes=num_probes,
+                        dequantize=dequantize)
 
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
@@ -220,6 +249,35 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
                     "class_labels": None if not lab or lab[0] is None else torch.cat(lab)}, invert_to)
         print(f"[rank {rank}] wrote the latents of images {first}..{first + n_local - 1} to {invert_to}", flush=True)
         return
+    if likelihood_to is not None:
+        import json
+        from .solvers import bits_per_dim
+        model.eval()
+        sd2 = [2.0 * float(v) for v in std]         # load_images normalises with x = (pixel - mean) / (2 std)
+        gen = torch.Generator().manual_seed(seed + 1000003 * rank)
+        logp = []
+        for x0, y, img in datamodule.predict_dataloader():
+            y = y if model.conditional else None
+            if dequantize:      # level u read at its centre (load_images) -> uniform over its bin [u, u + 1) / 255
+                u = torch.rand(img.shape, generator=gen, dtype=torch.float32) - 0.5
+                img = img + (u / 255.0 / torch.tensor(sd2, dtype=torch.float32).view(-1, 1, 1)).to(img.device)
+            logp.append(model.solver.log_likelihood(model, img, y, graph=graph, end_step=start_step,
+                                                    num_probes=num_probes).cpu())
+        logp = torch.cat(logp) if logp else torch.empty(0, dtype=torch.float64)
+        bpd = bits_per_dim(logp, C * image_size * image_size, sd2)
+        if world > 1:
+            root, ext = os.path.splitext(likelihood_to)
+            likelihood_to = f"{root}.rank{rank}{ext}"
+        with open(likelihood_to, "w") as f:
+            json.dump({"logp": logp.tolist(), "bpd": bpd.tolist(),
+                       "logp_mean": float(logp.mean()) if logp.numel() else None,
+                       "bpd_mean": float(bpd.mean()) if bpd.numel() else None, "num_steps": num_steps,
+                       "end_step": start_step, "num_probes": num_probes, "delta": float(model.solver.delta),
+                       "seed": seed, "network_dtype": network_dtype, "dequantize": bool(dequantize),
+                       "first_index": first}, f)
+        print(f"[rank {rank}] wrote the likelihoods of images {first}..{first + n_local - 1} to {likelihood_to}",
+              flush=True)
+        return
     writer = PreditionWriter(output_dir=output_dir, write_interval="batch", mean=mean, std=std, first_index=first)
     trainer = Trainer(accelerator="gpu", strategy="auto", callbacks=[writer])
     if n_local > 0:
@@ -284,11 +342,19 @@ def main(argv=None):
     parser.add_argument("--invert_to", type=str, default=None, metavar="OUT.pt",
                         help="write the latents of the --init_dir images (the ODE run upwards to --start_step) instead "
                              "of sampling; Heun solver only")
+    parser.add_argument("--likelihood_to", type=str, default=None, metavar="OUT.json",
+                        help="write log p (nats) and bits/dim of the --init_dir images, evaluated along the ODE run "
+                             "upwards to --start_step, instead of sampling; Heun solver, --network_dtype f32x3 or f32")
+    parser.add_argument("--num_probes", type=int, default=1,
+                        help="Rademacher probes per evaluation of --likelihood_to (default 1; the batch grows to 1 + 2K)")
+    parser.add_argument("--dequantize", action="store_true",
+                        help="--likelihood_to: add uniform noise of one grey level to the images first")
     args = parser.parse_args(argv)
     _check_solver(args.solver, args.S_churn)
     try:
         _check_conditioning(args.init_dir, args.start_step, args.mask_box, args.invert_to, args.solver, args.S_churn,
-                            args.image_size)
+                            args.image_size, likelihood_to=args.likelihood_to, network_dtype=args.network_dtype,
+                            num_probes=args.num_probes, dequantize=args.dequantize)
         if args.start_step >= args.num_steps:
             raise ValueError(f"generate: --start_step must be below --num_steps = {args.num_steps}, got {args.start_step}")
     except ValueError as e:
@@ -323,7 +389,8 @@ def main(argv=None):
              guide=guide, guide_ckpt_path=args.guide_ckpt_path, guide_load_ema=args.guide_load_ema,
              guidance=args.guidance, guidance_interval=args.guidance_interval, S_churn=args.S_churn, S_min=args.S_min,
              S_max=args.S_max, S_noise=args.S_noise, solver=args.solver, solver_order=args.solver_order,
-             init_dir=args.init_dir, start_step=args.start_step, mask_box=args.mask_box, invert_to=args.invert_to)
+             init_dir=args.init_dir, start_step=args.start_step, mask_box=args.mask_box, invert_to=args.invert_to,
+             likelihood_to=args.likelihood_to, num_probes=args.num_probes, dequantize=args.dequantize)
 
 
 if __name__ == "__main__":

@@ -1753,6 +1753,131 @@ def inpaint_blend(x, image, mask, t, rec, step):
     return out
 
 
+NLL_MAX_PROBES = 32             # a probe is one bit of a Philox word
+NLL_MAX_STEPS = 1 << 16         # step < 2**16 keeps the probe tags apart from the churn's and the blend's
+NLL_MAX_CHUNKS = 64             # EDM_NLL_MAX_CHUNKS: per-sample partial sums of the order-fixed reduction
+
+
+def _nll_batch(t, name, B, K, sample_shape, device):
+    """an evaluation batch: contiguous fp32 [(1 + 2K) B, ...] on `device`"""
+    _chk(t, f32, name, ((1 + 2 * K) * B,) + tuple(sample_shape))
+    if t.device != device:
+        raise ValueError(f"{name}: expected a tensor on {device}, got {t.device}")
+
+
+def _nll_args(rec, x, step, K, **pos):
+    _churn_rec(rec, x)
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= NLL_MAX_PROBES:
+        raise ValueError(f"num_probes must be an integer in [1, {NLL_MAX_PROBES}], got {K!r}")
+    if isinstance(step, bool) or not isinstance(step, int) or not 0 <= step < NLL_MAX_STEPS:
+        raise ValueError(f"step must be an integer in [0, {NLL_MAX_STEPS}), got {step!r}")
+    for name, v in pos.items():
+        if not (math.isfinite(v) and v > 0.0):
+            raise ValueError(f"{name} must be finite and > 0, got {v}")
+
+
+def _nll_acc(L, B, device):
+    _chk(L, torch.float64, "L", (B,))
+    if L.device != device:
+        raise ValueError(f"L: expected a tensor on {device}, got {L.device}")
+    if B > 65535:
+        raise ValueError(f"the likelihood kernels take at most 65535 samples per call, got {B}")
+    return torch.empty(B * NLL_MAX_CHUNKS, dtype=torch.float64, device=device)
+
+
+def nll_probe(x, h, rec, step, ev=0, num_probes=1):
+    """The evaluation batch of the likelihood estimator: E = [x, x + h eps_0, x - h eps_0, x + h eps_1, ...] stacked along
+    the batch, [(1 + 2K) B, ...] for K = num_probes Rademacher probes eps_p = +-1 drawn in the kernel (one bit of a Philox
+    word each, under a tag of their own).  x: contiguous fp32 [B, ...]; h > 0; rec: the device record of ops.churn_record;
+    step < 2**16 and ev in {0, 1} (the Euler evaluation of the step / its correction) select the stream.  The probes of
+    sample b depend only on (seed, solve index, step, ev, probe, b, element)."""
+    _chk(x, f32, "x")
+    if x.dim() < 2 or x.numel() == 0:
+        raise ValueError(f"x: expected a non-empty [B, ...] tensor, got {tuple(x.shape)}")
+    h = float(h)
+    _nll_args(rec, x, step, num_probes, h=h)
+    if ev not in (0, 1):
+        raise ValueError(f"nll_probe: ev must be 0 or 1, got {ev!r}")
+    B = x.shape[0]
+    if B > 65535:
+        raise ValueError(f"the likelihood kernels take at most 65535 samples per call, got {B}")
+    E = torch.empty(((1 + 2 * num_probes) * B,) + tuple(x.shape[1:]), dtype=f32, device=x.device)
+    _lib.call("edm_nll_probe", _p(x), h, _p(rec), step, int(ev), num_probes, B, x.numel() // B, _p(E),
+              _p(health(x.device)), _stream())
+    return E
+
+
+def heun_euler_div(E, D, t0, t1, h0, h1, rec, step, L, num_probes=1):
+    """heun_euler on the first B rows of the evaluation batch E and the network's output D on it, plus the divergence
+    term: returns (dx [B, ...], E1) with E1 the evaluation batch of x1 (half-width h1, the probes of the step's
+    correction), and adds (t1 - t0) / 2 * (CHW - q_b) / t0 to L (fp64 [B], in place), where
+    q_b = mean_p sum_j eps_pj (D+_bj - D-_bj) / (2 h0) with the probes E was written with (ops.nll_probe(.., step, 0) or
+    the previous heun_correct_div).  dx and E1[:B] equal ops.heun_euler(E[:B], D[:B], t0, t1) bit for bit."""
+    _chk(E, f32, "E")
+    K = num_probes
+    t0, t1, h0, h1 = float(t0), float(t1), float(h0), float(h1)
+    _nll_args(rec, E, step, K, t0=t0, h0=h0, h1=h1)
+    if not math.isfinite(t1):
+        raise ValueError(f"heun_euler_div: t1 must be finite, got {t1}")
+    if E.dim() < 2 or E.numel() == 0 or E.shape[0] % (1 + 2 * K):
+        raise ValueError(f"E: expected a non-empty [(1 + 2 * {K}) B, ...] tensor, got {tuple(E.shape)}")
+    B = E.shape[0] // (1 + 2 * K)
+    _nll_batch(D, "D", B, K, E.shape[1:], E.device)
+    part = _nll_acc(L, B, E.device)
+    dx = torch.empty((B,) + tuple(E.shape[1:]), dtype=f32, device=E.device)
+    E1 = torch.empty_like(E)
+    _lib.call("edm_heun_euler_div", _p(E), _p(D), t0, t1, h0, h1, _p(rec), step, K, B, E.numel() // E.shape[0], _p(dx),
+              _p(E1), _p(part), _p(L), _p(health(E.device)), _stream())
+    return dx, E1
+
+
+def heun_correct_div(E, dx, E1, D1, t0, t1, h1, rec, step, L, num_probes=1, h_next=None):
+    """heun_correct on the first B rows of (E, dx, E1) and the network's output D1 on E1, plus the divergence term: adds
+    (t1 - t0) / 2 * (CHW - q_b) / t1 to L with q_b from D1 under the probes heun_euler_div wrote E1 with (half-width h1).
+    With h_next it returns the evaluation batch of the new state for the next step's Euler evaluation (the probes of
+    (step - 1, 0), half-width h_next; step >= 1); without, the new state alone, [B, ...].  Its first B rows equal
+    ops.heun_correct(E[:B], dx, E1[:B], D1[:B], t0, t1) bit for bit."""
+    _chk(E, f32, "E")
+    K = num_probes
+    t0, t1, h1 = float(t0), float(t1), float(h1)
+    pos = dict(t1=t1, h1=h1)
+    if h_next is not None:
+        pos["h_next"] = h_next = float(h_next)
+    _nll_args(rec, E, step, K, **pos)
+    if not math.isfinite(t0):
+        raise ValueError(f"heun_correct_div: t0 must be finite, got {t0}")
+    if h_next is not None and step < 1:
+        raise ValueError("heun_correct_div: h_next (probes for the next step) needs step >= 1")
+    if E.dim() < 2 or E.numel() == 0 or E.shape[0] % (1 + 2 * K):
+        raise ValueError(f"E: expected a non-empty [(1 + 2 * {K}) B, ...] tensor, got {tuple(E.shape)}")
+    B = E.shape[0] // (1 + 2 * K)
+    _nll_batch(E1, "E1", B, K, E.shape[1:], E.device)
+    _nll_batch(D1, "D1", B, K, E.shape[1:], E.device)
+    _chk(dx, f32, "dx", (B,) + tuple(E.shape[1:]))
+    if dx.device != E.device:
+        raise ValueError(f"dx: expected a tensor on {E.device}, got {dx.device}")
+    part = _nll_acc(L, B, E.device)
+    out = torch.empty_like(E) if h_next is not None else torch.empty_like(dx)
+    _lib.call("edm_heun_correct_div", _p(E), _p(dx), _p(E1), _p(D1), t0, t1, h1, 1.0 if h_next is None else h_next,
+              _p(rec), step, K, int(h_next is not None), B, E.numel() // E.shape[0], _p(out), _p(part), _p(L),
+              _p(health(E.device)), _stream())
+    return out
+
+
+def nll_prior(x, t, L):
+    """L_b += log N(x_b; 0, t^2 I) in nats, summed in fp64 in a fixed order.  x: contiguous fp32 [B, ...]; L: fp64 [B]."""
+    _chk(x, f32, "x")
+    if x.dim() < 2 or x.numel() == 0:
+        raise ValueError(f"x: expected a non-empty [B, ...] tensor, got {tuple(x.shape)}")
+    t = float(t)
+    if not (math.isfinite(t) and t > 0.0):
+        raise ValueError(f"nll_prior: t must be finite and > 0, got {t}")
+    B = x.shape[0]
+    part = _nll_acc(L, B, x.device)
+    _lib.call("edm_nll_prior", _p(x), t, B, x.numel() // B, _p(part), _p(L), _p(health(x.device)), _stream())
+    return L
+
+
 def scale_f32(x, s):
     _chk(x, f32, "x")
     y = torch.empty_like(x)

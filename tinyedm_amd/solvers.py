@@ -25,6 +25,34 @@ def _release_solves(per_model: dict):
         pass
 
 
+NLL_DELTA = 1e-2        # default relative half-width of the likelihood estimator's central difference
+
+
+class _NllState(NamedTuple):
+    """what a likelihood solve owns beside its images (a captured entry owns its own)"""
+    rec: torch.Tensor       # the device record of the probe stream (ops.churn_record), rewritten before every replay
+    L: torch.Tensor         # fp64 [B]: the accumulated log-density, zeroed by the loop itself
+
+
+def bits_per_dim(logp, dims: int, std, levels: int = 256) -> torch.Tensor:
+    """Bits per dimension of images with ``levels`` grey levels from the log-density ``logp`` (nats) of the NORMALISED
+    image x = (u / (levels - 1) - mean) / std, as DeterministicSolver.log_likelihood returns it:
+
+        bpd = (-logp / dims + mean_c log((levels - 1) * std_c)) / ln 2
+
+    the density carried back to pixel units u, where one grey level has width 1.  ``dims`` = C*H*W, ``std`` the
+    normalisation's standard deviation (a number or one per channel; channels have equal size).  Host only, fp64."""
+    if isinstance(dims, bool) or not isinstance(dims, int) or dims < 1:
+        raise ValueError(f"bits_per_dim: dims must be a positive integer, got {dims!r}")
+    if isinstance(levels, bool) or not isinstance(levels, int) or levels < 2:
+        raise ValueError(f"bits_per_dim: levels must be an integer >= 2, got {levels!r}")
+    std = torch.as_tensor(std, dtype=torch.float64).flatten().cpu()
+    if std.numel() == 0 or not bool((std > 0).all()) or not bool(torch.isfinite(std).all()):
+        raise ValueError(f"bits_per_dim: std must be positive and finite, got {std.tolist()}")
+    logp = torch.as_tensor(logp).detach().to(device="cpu", dtype=torch.float64)
+    return (-logp / dims + torch.log((levels - 1) * std).mean()) / math.log(2.0)
+
+
 class _Conditioning(NamedTuple):
     """the image conditioning of one solve (a captured entry owns static copies)"""
     start: int              # the step the solve enters at: x_start = image + t_start * x0
@@ -76,14 +104,16 @@ class DeterministicSolver:
     (ops.inpaint_blend) and no extra network evaluation.  The mask is binary (non-zero = known pixel, kept); soft masks
     and RePaint's resampling are not implemented.  The noise comes from ``seed`` and ``solve_index`` as the churn of
     StochasticSolver does, under a Philox tag of its own; ``solve_index`` increments after every inpainting solve.
-    ``invert`` runs the probability-flow ODE upwards, image -> latent."""
+    ``invert`` runs the probability-flow ODE upwards, image -> latent; ``log_likelihood`` does the same and integrates
+    the change of variables along the way (keyword-only ``delta``: the relative half-width of its central difference)."""
 
     MAX_GRAPHS = 4      # captured solves kept per model (shape / precision combinations; least recently used dropped)
 
     def __init__(self, num_steps: int = 18, sigma_min: float = 0.002, sigma_max: float = 80.0, rho: float = 7.0,
                  dtype: str | None = None, *, guide=None, guidance: float = 1.0,
-                 guidance_interval: tuple[float, float] | None = None, seed: int = 0):
+                 guidance_interval: tuple[float, float] | None = None, seed: int = 0, delta: float = NLL_DELTA):
         self.num_steps = num_steps
+        self.delta = delta
         self.seed = seed
         self.solve_index = 0
         self.sigma_min = sigma_min
@@ -316,9 +346,107 @@ class DeterministicSolver:
         ops.check_health(image.device, "DeterministicSolver.invert(graph=True)")
         return out
 
+    # ------------------------------------------------------------------ likelihood
+    def probe_widths(self, sigma_data: float = 0.5, delta: float | None = None) -> list[float]:
+        """h_i = delta * sqrt(t_i^2 + sigma_data^2) for the N table entries: the half-width of the likelihood estimator's
+        central difference at noise level t_i, relative to the rms of the state there.  fp64 from the fp32 table, rounded
+        to fp32, as host floats.  Host only; raises ValueError unless delta is finite and > 0."""
+        delta = self.delta if delta is None else delta
+        try:
+            d = float(delta)
+        except (TypeError, ValueError):
+            d = math.nan
+        if isinstance(delta, bool) or not (math.isfinite(d) and d > 0.0):
+            raise ValueError(f"log_likelihood: delta must be finite and > 0, got {delta!r}")
+        t = self.t_steps[:self.num_steps].double()
+        return (d * (t * t + float(sigma_data) ** 2).sqrt()).float().tolist()
+
+    def _nll_loop(self, model, image, class_labels, t_dev, end_step, K, hs, state):
+        ts = self.t_steps.tolist()
+        rec, L = state
+        L.zero_()
+        x = image
+        if end_step < self.num_steps - 1:
+            E = ops.nll_probe(image, hs[-1], rec, self.num_steps - 1, 0, K)
+            for i in range(self.num_steps - 1, end_step, -1):        # invert's Heun step t_i -> t_{i-1} on (x, L)
+                t0, t1 = ts[i], ts[i - 1]
+                D = model(E, t_dev[i], class_labels).float().contiguous()
+                dx, E1 = ops.heun_euler_div(E, D, t0, t1, hs[i], hs[i - 1], rec, i, L, K)
+                D1 = model(E1, t_dev[i - 1], class_labels).float().contiguous()
+                E = ops.heun_correct_div(E, dx, E1, D1, t0, t1, hs[i - 1], rec, i, L, K,
+                                         h_next=hs[i - 1] if i - 1 > end_step else None)
+            x = E
+        ops.nll_prior(x, ts[end_step], L)
+        return L, ops.scale_f32(x, 1.0 / ts[end_step])
+
+    @torch.no_grad()
+    def log_likelihood(self, model, image, class_labels=None, graph: bool = False, *, end_step: int = 0,
+                       num_probes: int = 1, return_latent: bool = False):
+        """log p(image) in nats under the sampler's own generative ODE, a [B] float64 tensor: the density of the
+        NORMALISED image as given, taken as the state at t_{N-1} (``bits_per_dim`` carries it to pixel units).  The
+        state takes ``invert``'s Heun steps t_{N-1} -> ... -> t_k, k = ``end_step``, unchanged, and along them
+
+            L += (t_{i-1} - t_i) / 2 * (g(x_i, t_i) + g(x~_{i-1}, t_{i-1})),   g(x, t) = (d - q(x, t)) / t,
+            log p(image) = log N(x_k; 0, t_k^2 I) + L,
+
+        with q ~ tr dD/dx estimated without a backward pass: Hutchinson with ``num_probes`` Rademacher probes eps and a
+        central difference through the network, q = mean_p eps_p . (D(x + h eps_p) - D(x - h eps_p)) / (2h),
+        h = delta * sqrt(t^2 + sigma_data^2).  The 1 + 2 * num_probes evaluations go through the network as one batch:
+        2(N - 1 - k) network calls, as for ``invert``, at (1 + 2 * num_probes) times the batch.  The probes are drawn in
+        the kernels from ``seed`` and ``solve_index`` as the inpainting noise is, under a Philox tag of their own;
+        ``solve_index`` increments after every likelihood solve, so repeated calls average independent probes.  L and
+        the prior term are accumulated in fp64 on the device in a fixed order: eager == graph and run == run bit for bit.
+
+        The network must evaluate in fp32 (``eval_dtype`` "f32x3" or "f32"): a difference quotient at bf16 evaluation
+        error is meaningless, so "bf16" raises ValueError.  Only D_main is evaluated: guided likelihoods are not
+        implemented, ``guide`` and ``guidance`` are ignored here, as in ``invert``.  With ``return_latent`` the result
+        is (logp, latent), latent the unit-scale x_k / t_k that ``invert`` returns, bit for bit."""
+        self._check_invert()
+        if isinstance(end_step, bool) or not isinstance(end_step, int) or not 0 <= end_step < self.num_steps:
+            raise ValueError(f"log_likelihood: end_step must be an integer in [0, {self.num_steps - 1}], got "
+                             f"{end_step!r}")
+        if isinstance(num_probes, bool) or not isinstance(num_probes, int) or \
+                not 1 <= num_probes <= ops.NLL_MAX_PROBES:
+            raise ValueError(f"log_likelihood: num_probes must be an integer in [1, {ops.NLL_MAX_PROBES}], got "
+                             f"{num_probes!r}")
+        if not isinstance(image, torch.Tensor) or not image.dtype.is_floating_point:
+            raise ValueError("log_likelihood: image must be a floating-point tensor")
+        if image.dim() < 2 or image.numel() == 0:
+            raise ValueError(f"log_likelihood: image must be a non-empty [B, ...] tensor, got {tuple(image.shape)}")
+        if self.num_steps >= ops.NLL_MAX_STEPS:
+            raise ValueError(f"log_likelihood: needs num_steps < {ops.NLL_MAX_STEPS}")
+        self._check_stream()
+        owner = getattr(model, "__self__", model)
+        hs = self.probe_widths(getattr(owner, "sigma_data", 0.5))
+        if isinstance(owner, torch.nn.Module):
+            for m in owner.modules():
+                if getattr(m, "eval_dtype", None) == "bf16":
+                    raise ValueError("log_likelihood: the network evaluates in bf16; a difference quotient needs the fp32 "
+                                     "evaluation path (set_eval_dtype('f32x3') or 'f32')")
+                if hasattr(m, "eval_dtype") and m.training:
+                    raise ValueError("log_likelihood: the network is in training mode; call model.eval()")
+        if not image.is_cuda:
+            raise RuntimeError("tinyedm_amd.DeterministicSolver: image must be a GPU tensor (there is no CPU path)")
+        in_dtype = image.dtype
+        image = image.float().contiguous()
+        if class_labels is not None:        # one label row per row of the evaluation batch
+            class_labels = class_labels.repeat(1 + 2 * num_probes, *([1] * (class_labels.dim() - 1)))
+        if not graph:
+            state = _NllState(ops.churn_record(self.seed, self.solve_index, image.device),
+                              torch.zeros(image.shape[0], dtype=torch.float64, device=image.device))
+            logp, latent = self._nll_loop(model, image, class_labels, self.t_steps.to(image.device), end_step,
+                                          num_probes, hs, state)
+        else:
+            logp, latent = self._solve_graphed(model, image, class_labels, (), None, None,
+                                               (end_step, num_probes, float(self.delta), hs))
+            ops.check_health(image.device, "DeterministicSolver.log_likelihood(graph=True)")
+        self.solve_index += 1
+        return (logp, latent.to(in_dtype)) if return_latent else logp
+
     # ------------------------------------------------------------------ hipGraph
-    def _solve_graphed(self, model, x0, class_labels, guided, cond=None, invert_to=None):
-        """replay (after capturing, the first time) the solve, or with invert_to = its end step the inversion of x0"""
+    def _solve_graphed(self, model, x0, class_labels, guided, cond=None, invert_to=None, nll=None):
+        """replay (after capturing, the first time) the solve, or with invert_to = its end step the inversion of x0, or
+        with nll = (end step, probes, delta, probe widths) its likelihood"""
         # graphs are cached PER MODEL OBJECT (weakly: a new model allocated at a dead one's address must not replay the
         # dead one's graph, which id(model) as a key allowed)
         owner = getattr(model, "__self__", model)        # a bound method is a fresh object per access: key on its object
@@ -345,7 +473,9 @@ class DeterministicSolver:
             key += ((UNCONDITIONAL,), guided)
         elif guide is not None:
             key += (id(guide), eval_dtypes(guide), guided)
-        if invert_to is not None:
+        if nll is not None:
+            key += ("nll",) + nll[:3]
+        elif invert_to is not None:
             key += ("invert", invert_to)
         else:
             key += self._graph_key_extra(0 if cond is None else cond.start)
@@ -359,13 +489,20 @@ class DeterministicSolver:
             w_dev = None if guide is None else torch.full((1,), float(self.guidance), device=x0.device)
             if _is_unconditional(guide):
                 guide = None
-            state = None if invert_to is not None else self._solve_state(x0, 0 if cond is None else cond.start)
+            if nll is not None:
+                state = _NllState(ops.churn_record(self.seed, self.solve_index, x0.device),
+                                  torch.zeros(x0.shape[0], dtype=torch.float64, device=x0.device))
+            else:
+                state = None if invert_to is not None else self._solve_state(x0, 0 if cond is None else cond.start)
             sx = x0.clone()
             sl = None if class_labels is None else class_labels.clone()
             # the entry's own image, mask and noise record: copied / rewritten before every replay, as sx and sl are
             sc = None if cond is None else _Conditioning(cond.start, *(None if v is None else v.clone()
                                                                       for v in cond[1:]))
-            if invert_to is not None:
+            if nll is not None:
+                def loop():
+                    return self._nll_loop(model, sx, sl, t_dev, nll[0], nll[1], nll[3], state)
+            elif invert_to is not None:
                 def loop():
                     return self._invert_loop(model, sx, sl, t_dev, invert_to)
             else:
@@ -394,7 +531,10 @@ class DeterministicSolver:
             ent = per_model[key] = (g, sx, sl, out, t_dev, token, w_dev, guide, state, sc)
         else:
             per_model[key] = per_model.pop(key)              # most recently used last
-            self._write_solve_state(ent[8])
+            if nll is not None:
+                ops.churn_record(self.seed, self.solve_index, out=ent[8].rec)
+            else:
+                self._write_solve_state(ent[8])
         g, sx, sl, out, _, _, w_dev, _, _, sc = ent
         if sc is not None:
             if sc.image is not None:
@@ -416,7 +556,7 @@ class DeterministicSolver:
         if sl is not None:
             sl.copy_(class_labels)
         g.replay()
-        return out.clone()
+        return tuple(o.clone() for o in out) if isinstance(out, tuple) else out.clone()
 
 
 class ChurnSchedule(NamedTuple):
