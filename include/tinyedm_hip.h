@@ -463,6 +463,27 @@ int edm_state_init(const float* image, const float* x0, float t, float* out, lon
  * Same health bit as the Heun updates. */
 int edm_inpaint_blend(const float* x, const float* image, const unsigned char* mask, float t, const void* rec, int step,
                       int B, int C, long HW, int mask_B, float* out, unsigned* health, edm_stream_t stream);
+/* zero-shot restoration from a linear measurement y = A x (DDNM, Wang et al. 2023; restore.hip).  A averages every
+ * scale x scale pixel block, scale in {1, 2, 4, 8} with H % scale == 0 and W % scale == 0, and with gray != 0 also the
+ * C <= 8 channels; its pseudo-inverse A+ replicates a value to its block (A A+ = I, A+ A an orthogonal projector).
+ * scale == 1 without gray is the identity and is refused.  x / Dm / Dg / out: contiguous [B, C, H, W] fp32; y:
+ * contiguous [B, gray ? 1 : C, H/scale, W/scale] fp32.
+ * edm_degrade: y = A x.
+ * edm_project_denoised: D = Dg + w*(Dm - Dg) when Dg and w are both non-null (w a DEVICE pointer to one float, read at
+ *   run time as in edm_heun_euler_guided, so a captured solve follows later writes to it; w == 0 equals the unguided
+ *   call fed Dg bit for bit), else D = Dm;  out = D + (y_block - mean_block(D)): the projection of D onto {x : A x = y}.
+ *   out aliases no operand.  Same health bit as the Heun updates when an element of out is non-finite.
+ * The block mean is the same code in both and order-fixed (no atomics, no cross-thread reduction: one thread owns whole
+ * blocks): acc = 0, then acc += D[c][row][column] in sequential fp32 adds with the channels ascending (gray only), then
+ * the rows of the block, then its columns; mean = acc * (1.0f / n), n = scale*scale*(gray ? C : 1), one multiplication.
+ * The correction is one subtraction y - mean per block and one addition per element, none contracted with another
+ * operation.  Hence project(D, degrade(D)) == D and project(0, y) == A+ y bit for bit, and a sample's result depends
+ * neither on B nor on the memory path: with W % 4 == 0 and every fp32 operand 16-byte aligned a thread reads its rows
+ * as dwordx4 (two blocks of a row for scale 2, one for 4, two loads for 8; neighbouring threads take neighbouring strips
+ * of the same rows), otherwise one block per thread element by element, with the same bits. */
+int edm_degrade(const float* x, float* y, int B, int C, int H, int W, int scale, int gray, edm_stream_t stream);
+int edm_project_denoised(const float* Dm, const float* Dg, const float* w, const float* y, float* out, int B, int C,
+                         int H, int W, int scale, int gray, unsigned* health, edm_stream_t stream);
 /* Likelihood evaluation along the probability-flow ODE dx/dt = (x - D(x; t)) / t: the Heun updates plus the integral of
  * the drift's divergence (CHW - tr dD/dx) / t, the trace estimated without a backward pass (Hutchinson with Rademacher
  * probes, central difference through the network):

@@ -116,6 +116,9 @@ SIGNATURES = {
     "edm_heun_correct_div": [P, P, P, P, F, F, F, F, P, I, I, I, I, L, P, P, P, P, P],
     "edm_nll_prior": [P, F, I, L, P, P, P, P],
     "edm_scale_f32": [P, F, P, L, P],
+    # restore.hip
+    "edm_degrade": [P, P, I, I, I, I, I, I, P],
+    "edm_project_denoised": [P, P, P, P, P, I, I, I, I, I, I, P, P],
     # weights.hip
     "edm_weight_prep": [P, I, I, I, I, P, P, P, P, I, P],
     "edm_weight_prep_multi": [P, P, I, I, I, P],

@@ -68,6 +68,19 @@ U[0, 1) / 255 in pixel units, drawn from `--seed` on the host: the usual uniform
 
     python -m tinyedm.generate --ckpt_path last.ckpt --load_ema --init_dir photos --likelihood_to bpd.json --dequantize \\
         --output_dir unused --num_samples 64 --image_size 32 --num_classes 10 --batch_size 64
+Zero-shot restoration (DDNM, Wang et al. 2023): `--restore_scale S` (1, 2, 4, 8: SxS box down-sampling) and / or
+`--restore_gray` (the mean over the channels) take the `--init_dir` images as ground truth, measure them in the process
+(y = A image, the usual simulated-measurement protocol) and sample images with A x = y: 4x super-resolution,
+colourisation, or both.  The solver never sees the ground truth: with `--start_step K` > 0 the state is entered from
+A+ y (the blocky / grey image), not from the image.  Restored images go to `--output_dir`, A+ y to `--save_degraded DIR`,
+and `--restore_report OUT.json` receives, per rank and computed in fp32 before the uint8 conversion,
+{"consistency": max |A x - y|, "max_abs": max(|x|, |y|), "psnr_restored", "psnr_degraded": mean PSNR in dB against the
+ground truth in pixel units, ...}.  Exclusive with `--mask_box`, `--invert_to` and `--likelihood_to`; combines with guidance, churn,
+`--solver dpmpp`, `--start_step` and `--network_dtype`.
+
+    python -m tinyedm.generate --ckpt_path last.ckpt --load_ema --init_dir photos --restore_scale 4 \\
+        --save_degraded lowres --restore_report sr.json --output_dir restored --num_samples 64 --image_size 32 \\
+        --num_classes 10 --batch_size 64
 Multi-GPU = replicas only: under `python -m torch.distributed.run --nproc-per-node N` every rank samples
 its own contiguous index range with its own noise seed and writes `<global index>.png`; there is no collective.
 """
@@ -136,6 +149,41 @@ def _check_conditioning(init_dir, start_step, mask_box, invert_to, solver, S_chu
                          "evaluation error is meaningless)")
 
 
+RESTORE_SCALES = (1, 2, 4, 8)
+
+
+def _check_restoration(init_dir, restore_scale, restore_gray, save_degraded, restore_report, mask_box, invert_to,
+                       likelihood_to, image_size) -> bool:
+    """the restoration choices that need nothing loaded; returns whether the run restores"""
+    if isinstance(restore_scale, bool) or not isinstance(restore_scale, int) or restore_scale not in RESTORE_SCALES:
+        raise ValueError(f"generate: --restore_scale must be one of {RESTORE_SCALES}, got {restore_scale!r}")
+    active = restore_scale != 1 or bool(restore_gray)
+    if not active:
+        for flag, on in (("--save_degraded", save_degraded is not None), ("--restore_report", restore_report is not None)):
+            if on:
+                raise ValueError(f"generate: {flag} needs --restore_scale > 1 or --restore_gray")
+        return False
+    if init_dir is None:
+        flag = "--restore_scale" if restore_scale != 1 else "--restore_gray"
+        raise ValueError(f"generate: {flag} needs --init_dir (the ground-truth images that are measured)")
+    for flag, on in (("--mask_box", mask_box is not None), ("--invert_to", invert_to is not None),
+                     ("--likelihood_to", likelihood_to is not None)):
+        if on:
+            raise ValueError(f"generate: --restore_scale / --restore_gray and {flag} are exclusive")
+    if image_size % restore_scale:
+        raise ValueError(f"generate: --restore_scale {restore_scale} must divide --image_size {image_size}")
+    return True
+
+
+def _psnr(x, ref, mean, std) -> torch.Tensor:
+    """per-image PSNR in dB of normalised fp32 images against ``ref`` in pixel units [0, 1] (the writer's
+    x * std * 2 + mean, clamped): [B] fp32 on x's device"""
+    m = torch.tensor([float(v) for v in mean], device=x.device).view(1, -1, 1, 1)
+    sd = torch.tensor([float(v) for v in std], device=x.device).view(1, -1, 1, 1)
+    a, b = ((t.float() * sd * 2.0 + m).clamp(0.0, 1.0) for t in (x, ref))
+    return -10.0 * torch.log10(((a - b) ** 2).mean(dim=(1, 2, 3)).clamp_min(1e-12))
+
+
 def load_images(init_dir, mean, std, image_size, channels) -> torch.Tensor:
     """the PNGs of a directory as PreditionWriter names them (<index>.png), in numeric order of the index, normalised
     as PreditionWriter denormalises (pixel = x * std * 2 + mean): fp32 [n, C, H, W] on the host"""
@@ -166,7 +214,8 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
              network_dtype="f32x3", guide=None, guide_ckpt_path=None, guide_load_ema=False, guidance=1.0,
              guidance_interval=None, S_churn=0.0, S_min=0.0, S_max=float("inf"), S_noise=1.0, solver="heun",
              solver_order=2, init_dir=None, start_step=0, mask_box=None, invert_to=None, likelihood_to=None,
-             num_probes=1, dequantize=False) -> None:
+             num_probes=1, dequantize=False, restore_scale=1, restore_gray=False, save_degraded=None,
+             restore_report=None) -> None:
     from .callbacks import PreditionWriter
     from .datamodules import RandomNoiseDataModule
     from .edm import EDM
@@ -177,6 +226,8 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
     _check_conditioning(init_dir, start_step, mask_box, invert_to, solver, S_churn, image_size,
                         likelihood_to=likelihood_to, network_dtype=network_dtype, num_probes=num_probes,
                         dequantize=dequantize)
+    restoring = _check_restoration(init_dir, restore_scale, restore_gray, save_degraded, restore_report, mask_box,
+                                   invert_to, likelihood_to, image_size)
 
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
@@ -278,6 +329,39 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
         print(f"[rank {rank}] wrote the likelihoods of images {first}..{first + n_local - 1} to {likelihood_to}",
               flush=True)
         return
+    if restoring:
+        import json
+        from .solvers import LinearDegradation
+        deg = LinearDegradation(restore_scale, bool(restore_gray))
+        writers = [PreditionWriter(output_dir=d, write_interval="batch", mean=mean, std=std, first_index=first)
+                   for d in (output_dir, save_degraded) if d is not None]
+        model.eval()
+        resid, peak, psnr_out, psnr_deg = 0.0, 0.0, [], []
+        for bi, (x0, y, img) in enumerate(datamodule.predict_dataloader()):
+            y = y if model.conditional else None
+            meas = deg.measure(img)             # the ground truth is used for this and for the report only
+            back = deg.pinv(meas, C)
+            out = model.solver.solve(model, x0, y, image=back if start_step > 0 else None, degradation=deg,
+                                     measurement=meas).float()
+            resid = max(resid, float((deg.measure(out) - meas).abs().max()))
+            peak = max(peak, float(out.abs().max()), float(meas.abs().max()))
+            psnr_out.append(_psnr(out, img, mean, std).cpu())
+            psnr_deg.append(_psnr(back, img, mean, std).cpu())
+            for w, pred in zip(writers, (out, back)):
+                w.write_on_batch_end(None, model, pred, None, None, bi, 0)
+        if restore_report is not None:
+            if world > 1:
+                root, ext = os.path.splitext(restore_report)
+                restore_report = f"{root}.rank{rank}{ext}"
+            with open(restore_report, "w") as f:
+                json.dump({"consistency": resid, "max_abs": peak,
+                           "psnr_restored": float(torch.cat(psnr_out).mean()) if psnr_out else None,
+                           "psnr_degraded": float(torch.cat(psnr_deg).mean()) if psnr_deg else None,
+                           "restore_scale": restore_scale, "restore_gray": bool(restore_gray), "num_steps": num_steps,
+                           "start_step": start_step, "seed": seed, "network_dtype": network_dtype,
+                           "first_index": first, "num_images": n_local}, f)
+        print(f"[rank {rank}] wrote the restored images {first}..{first + n_local - 1} to {output_dir}", flush=True)
+        return
     writer = PreditionWriter(output_dir=output_dir, write_interval="batch", mean=mean, std=std, first_index=first)
     trainer = Trainer(accelerator="gpu", strategy="auto", callbacks=[writer])
     if n_local > 0:
@@ -349,9 +433,22 @@ def main(argv=None):
                         help="Rademacher probes per evaluation of --likelihood_to (default 1; the batch grows to 1 + 2K)")
     parser.add_argument("--dequantize", action="store_true",
                         help="--likelihood_to: add uniform noise of one grey level to the images first")
+    # zero-shot restoration
+    parser.add_argument("--restore_scale", type=int, default=1, metavar="S",
+                        help="restoration: sample images whose SxS block means equal those of the --init_dir images "
+                             "(1, 2, 4 or 8; default 1 = off)")
+    parser.add_argument("--restore_gray", action="store_true",
+                        help="restoration: ... whose mean over the channels equals that of the --init_dir images "
+                             "(colourisation; combines with --restore_scale)")
+    parser.add_argument("--save_degraded", type=str, default=None, metavar="DIR",
+                        help="restoration: write A+ y, the measurement replicated to the image grid, as <index>.png")
+    parser.add_argument("--restore_report", type=str, default=None, metavar="OUT.json",
+                        help="restoration: write max |A x - y| and the mean PSNR of the restored images and of A+ y")
     args = parser.parse_args(argv)
     _check_solver(args.solver, args.S_churn)
     try:
+        _check_restoration(args.init_dir, args.restore_scale, args.restore_gray, args.save_degraded,
+                           args.restore_report, args.mask_box, args.invert_to, args.likelihood_to, args.image_size)
         _check_conditioning(args.init_dir, args.start_step, args.mask_box, args.invert_to, args.solver, args.S_churn,
                             args.image_size, likelihood_to=args.likelihood_to, network_dtype=args.network_dtype,
                             num_probes=args.num_probes, dequantize=args.dequantize)
@@ -390,7 +487,9 @@ def main(argv=None):
              guidance=args.guidance, guidance_interval=args.guidance_interval, S_churn=args.S_churn, S_min=args.S_min,
              S_max=args.S_max, S_noise=args.S_noise, solver=args.solver, solver_order=args.solver_order,
              init_dir=args.init_dir, start_step=args.start_step, mask_box=args.mask_box, invert_to=args.invert_to,
-             likelihood_to=args.likelihood_to, num_probes=args.num_probes, dequantize=args.dequantize)
+             likelihood_to=args.likelihood_to, num_probes=args.num_probes, dequantize=args.dequantize,
+             restore_scale=args.restore_scale, restore_gray=args.restore_gray, save_degraded=args.save_degraded,
+             restore_report=args.restore_report)
 
 
 if __name__ == "__main__":

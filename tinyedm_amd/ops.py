@@ -1753,6 +1753,71 @@ def inpaint_blend(x, image, mask, t, rec, step):
     return out
 
 
+RESTORE_SCALES = (1, 2, 4, 8)   # block sizes of the restoration operator (csrc/restore.hip)
+RESTORE_MAX_GRAY_CHANNELS = 8
+
+
+def check_degradation(scale, gray) -> None:
+    """the operator settings that need no tensor: scale in RESTORE_SCALES, gray a bool, not the identity"""
+    if isinstance(scale, bool) or not isinstance(scale, int) or scale not in RESTORE_SCALES:
+        raise ValueError(f"degradation: scale must be one of {RESTORE_SCALES}, got {scale!r}")
+    if not isinstance(gray, bool):
+        raise ValueError(f"degradation: gray must be a bool, got {gray!r}")
+    if scale == 1 and not gray:
+        raise ValueError("degradation: scale == 1 without gray is the identity: nothing to restore")
+
+
+def measurement_shape(x_shape, scale, gray) -> tuple:
+    """the shape of y = A x for x of shape [B, C, H, W]; raises ValueError where A is not defined"""
+    check_degradation(scale, gray)
+    if len(x_shape) != 4 or any(int(v) < 1 for v in x_shape):
+        raise ValueError(f"degradation: expected a non-empty [B, C, H, W] shape, got {tuple(x_shape)}")
+    B, C, H, W = (int(v) for v in x_shape)
+    if H % scale or W % scale:
+        raise ValueError(f"degradation: H and W must be multiples of scale = {scale}, got {H} x {W}")
+    if gray and C > RESTORE_MAX_GRAY_CHANNELS:
+        raise ValueError(f"degradation: gray averages at most {RESTORE_MAX_GRAY_CHANNELS} channels, got {C}")
+    return (B, 1 if gray else C, H // scale, W // scale)
+
+
+def degrade(x, scale, gray):
+    """y = A x: the mean of every scale x scale pixel block of x [B, C, H, W] (contiguous fp32), and with gray also over
+    the channels: [B, 1 if gray else C, H/scale, W/scale].  Order-fixed sum (include/tinyedm_hip.h)."""
+    _chk(x, f32, "x")
+    shape = measurement_shape(x.shape, scale, gray)
+    y = torch.empty(shape, device=x.device, dtype=f32)
+    _lib.call("edm_degrade", _p(x), _p(y), *x.shape, scale, int(gray), _stream())
+    return y
+
+
+def project_denoised(Dm, y, scale, gray, Dg=None, w_dev=None, out=None):
+    """D + A+ (y - A D): the projection of a denoiser output onto the images whose measurement is y (DDNM).  D = Dm, or
+    with Dg and w_dev (the one-element device tensor of the guided updates) D = Dg + w*(Dm - Dg).  Dm / Dg / out:
+    contiguous fp32 [B, C, H, W] on one device, y: contiguous fp32 of measurement_shape(Dm.shape, scale, gray); out
+    (allocated when None) aliases no operand.  project_denoised(D, degrade(D)) == D and project_denoised(0, y) == A+ y
+    bit for bit."""
+    _chk(Dm, f32, "Dm")
+    _chk(y, f32, "y", measurement_shape(Dm.shape, scale, gray))
+    if (Dg is None) != (w_dev is None):
+        raise ValueError("project_denoised: Dg and w_dev go together (guided) or are both None")
+    if Dg is not None:
+        _chk(Dg, f32, "Dg", Dm.shape)
+        _guidance_weight(w_dev, Dm)
+    if out is None:
+        out = torch.empty_like(Dm)
+    else:
+        _chk(out, f32, "out", Dm.shape)
+    ins = [(t, nme) for t, nme in ((Dm, "Dm"), (y, "y"), (Dg, "Dg")) if t is not None]
+    for t, nme in ins[1:] + [(out, "out")]:
+        if t.device != Dm.device:
+            raise ValueError(f"{nme}: expected a tensor on {Dm.device}, got {t.device}")
+    if any(t.data_ptr() == out.data_ptr() for t, _ in ins):
+        raise ValueError("out: must not alias an operand")
+    _lib.call("edm_project_denoised", _p(Dm), _p(Dg), _p(w_dev), _p(y), _p(out), *Dm.shape, scale, int(gray),
+              _p(health(Dm.device)), _stream())
+    return out
+
+
 NLL_MAX_PROBES = 32             # a probe is one bit of a Philox word
 NLL_MAX_STEPS = 1 << 16         # step < 2**16 keeps the probe tags apart from the churn's and the blend's
 NLL_MAX_CHUNKS = 64             # EDM_NLL_MAX_CHUNKS: per-sample partial sums of the order-fixed reduction

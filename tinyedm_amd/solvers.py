@@ -3,6 +3,7 @@ reference (solvers.py:4-59) and stochastic as Algorithm 2 of Karras et al. 2022,
 (Lu et al. 2022) that spends one network evaluation per step."""
 import math
 import weakref
+from dataclasses import dataclass
 from typing import NamedTuple
 
 import torch
@@ -61,6 +62,60 @@ class _Conditioning(NamedTuple):
     rec: object             # the device record of the inpainting noise (ops.churn_record), or None without a mask
 
 
+@dataclass(frozen=True)
+class LinearDegradation:
+    """The measurement operator of zero-shot restoration (``solve(..., degradation=, measurement=)``): y = A x with A
+    the mean over every ``scale`` x ``scale`` pixel block (``scale`` in 1, 2, 4, 8: box down-sampling) and, with
+    ``gray``, also over the channels (at most 8).  Its pseudo-inverse A+ replicates a value to its block: A A+ = I and
+    A+ A is an orthogonal projector.  ``scale=1`` without ``gray`` is the identity and raises ValueError.  Images are
+    [B, C, H, W] with H and W multiples of ``scale``; y is [B, 1 if gray else C, H/scale, W/scale]."""
+    scale: int = 4
+    gray: bool = False
+
+    def __post_init__(self):
+        ops.check_degradation(self.scale, self.gray)
+
+    def measurement_shape(self, x_shape) -> tuple:
+        """the shape of A x for x of shape ``x_shape``; ValueError where A is not defined.  Host only."""
+        return ops.measurement_shape(tuple(x_shape), self.scale, self.gray)
+
+    def measure(self, image) -> torch.Tensor:
+        """y = A image (ops.degrade), fp32.  ``image``: a floating-point GPU tensor [B, C, H, W]."""
+        if not isinstance(image, torch.Tensor) or not image.dtype.is_floating_point:
+            raise ValueError("LinearDegradation.measure: image must be a floating-point tensor")
+        self.measurement_shape(image.shape)
+        if not image.is_cuda:
+            raise RuntimeError("tinyedm_amd.LinearDegradation: image must be a GPU tensor (there is no CPU path)")
+        return ops.degrade(image.float().contiguous(), self.scale, self.gray)
+
+    def pinv(self, y, channels: int) -> torch.Tensor:
+        """A+ y, fp32 [B, channels, H*scale, W*scale]: every value replicated to its block (and to ``channels``
+        channels with ``gray``; otherwise ``channels`` is y's own).  It is the projection of the zero image
+        (ops.project_denoised), bit for bit the A+ of a solve."""
+        if not isinstance(y, torch.Tensor) or not y.dtype.is_floating_point or y.dim() != 4:
+            raise ValueError("LinearDegradation.pinv: y must be a floating-point [B, C', h, w] tensor")
+        if isinstance(channels, bool) or not isinstance(channels, int) or channels < 1:
+            raise ValueError(f"LinearDegradation.pinv: channels must be a positive integer, got {channels!r}")
+        shape = (y.shape[0], channels, y.shape[2] * self.scale, y.shape[3] * self.scale)
+        if tuple(y.shape) != self.measurement_shape(shape):
+            raise ValueError(f"LinearDegradation.pinv: y of shape {tuple(y.shape)} is no measurement of a "
+                             f"{channels}-channel image")
+        if not y.is_cuda:
+            raise RuntimeError("tinyedm_amd.LinearDegradation: y must be a GPU tensor (there is no CPU path)")
+        return ops.project_denoised(torch.zeros(shape, device=y.device), y.float().contiguous(), self.scale, self.gray)
+
+
+class _Restoration(NamedTuple):
+    """the measurement conditioning of one solve (a captured entry owns a static copy of y)"""
+    scale: int
+    gray: bool
+    y: torch.Tensor         # fp32, the measurement shape of the state
+
+    def project(self, D, Dg=None, w_dev=None):
+        """D^ = D + A+ (y - A D) of one network evaluation, the guidance mix included when Dg is given"""
+        return ops.project_denoised(D, self.y, self.scale, self.gray, Dg, None if Dg is None else w_dev)
+
+
 def _mask_u8(mask, shape):
     """a bool / uint8 / float mask of shape [B,1,H,W], [1,1,H,W] or [H,W] as uint8 [B or 1, H*W] (non-zero = known)"""
     B, _, H, W = shape
@@ -104,6 +159,15 @@ class DeterministicSolver:
     (ops.inpaint_blend) and no extra network evaluation.  The mask is binary (non-zero = known pixel, kept); soft masks
     and RePaint's resampling are not implemented.  The noise comes from ``seed`` and ``solve_index`` as the churn of
     StochasticSolver does, under a Philox tag of its own; ``solve_index`` increments after every inpainting solve.
+    Zero-shot restoration (keyword-only ``degradation`` and ``measurement`` of ``solve``, both or neither): sample an
+    image whose measurement ``degradation``(x) is ``measurement`` (LinearDegradation: super-resolution, colourisation)
+    by the range / null-space decomposition of DDNM (Wang et al. 2023): every network evaluation of the loop (guided
+    or not) is replaced by its projection D^ = D + A+ (y - A D) (ops.project_denoised, one more fp32 pass) before the
+    unguided update, so the last step returns an image with A x = y to rounding.  No extra network evaluation, no
+    backward pass.  ``start_step`` / ``image`` combine with it (SDEdit entered from ``degradation.pinv(y, C)``); ``mask``
+    with ``measurement`` raises ValueError, and so does any invalid combination, on the host before any launch.  Noisy
+    measurements (DDNM+), time travel / resampling and blur kernels are not implemented; ``invert`` and
+    ``log_likelihood`` do not take the arguments.
     ``invert`` runs the probability-flow ODE upwards, image -> latent; ``log_likelihood`` does the same and integrates
     the change of variables along the way (keyword-only ``delta``: the relative half-width of its central difference)."""
 
@@ -202,6 +266,31 @@ class DeterministicSolver:
         if masked:
             self.solve_index += 1
 
+    @staticmethod
+    def _restoration(x0, mask, degradation, measurement):
+        """Validate degradation / measurement of a solve against x0 on the host (nothing is read from a device) and
+        return them; None without them."""
+        if degradation is None and measurement is None:
+            return None
+        if degradation is None or measurement is None:
+            raise ValueError("solve: degradation and measurement go together (the operator and its y)")
+        if not isinstance(degradation, LinearDegradation):
+            raise ValueError(f"solve: degradation must be a LinearDegradation, got {type(degradation).__name__}")
+        if mask is not None:
+            raise ValueError("solve: mask (inpainting by replacement) and measurement (restoration) are two "
+                             "conditionings; their combination is not implemented")
+        if not isinstance(measurement, torch.Tensor) or not measurement.dtype.is_floating_point:
+            raise ValueError("solve: measurement must be a floating-point tensor")
+        if x0.dim() != 4:
+            raise ValueError(f"solve: a measurement needs x0 of shape [B, C, H, W], got {tuple(x0.shape)}")
+        shape = degradation.measurement_shape(x0.shape)
+        if tuple(measurement.shape) != shape:
+            raise ValueError(f"solve: measurement must have shape {shape} for x0 {tuple(x0.shape)} under "
+                             f"{degradation}, got {tuple(measurement.shape)}")
+        if measurement.device != x0.device:
+            raise ValueError(f"solve: measurement is on {measurement.device}, x0 on {x0.device}")
+        return degradation, measurement
+
     # ------------------------------------------------------------------ subclass hooks (StochasticSolver)
     def _graph_key_extra(self, start_step: int = 0) -> tuple:
         """what the subclass adds to the key of a captured solve"""
@@ -251,7 +340,7 @@ class DeterministicSolver:
         return self.guide(x, sigma, class_labels).float().contiguous()
 
     # ------------------------------------------------------------------ eager
-    def _loop(self, model, x0, class_labels, t_dev, guided, w_dev, state=None, cond=None):
+    def _loop(self, model, x0, class_labels, t_dev, guided, w_dev, state=None, cond=None, rest=None):
         ts = self.t_steps.tolist()
         k = 0 if cond is None else cond.start
         masked = cond is not None and cond.mask is not None
@@ -262,14 +351,21 @@ class DeterministicSolver:
             x, t0, s0 = self._step_start(x1, i, ts, t_dev, state)
             t1 = ts[i + 1]
             D = model(x, s0, class_labels).float().contiguous()
-            if guided[2 * i]:
+            if rest is not None:        # the projected (and mixed) evaluation, then the unguided update
+                D = rest.project(D, self._guide_eval(model, x, s0, class_labels) if guided[2 * i] else None, w_dev)
+                dx, x1 = ops.heun_euler(x, D, t0, t1)
+            elif guided[2 * i]:
                 Dg = self._guide_eval(model, x, s0, class_labels)
                 dx, x1 = ops.heun_euler_guided(x, D, Dg, w_dev, t0, t1)
             else:
                 dx, x1 = ops.heun_euler(x, D, t0, t1)
             if i < self.num_steps - 1:
                 D1 = model(x1, t_dev[i + 1], class_labels).float().contiguous()
-                if guided[2 * i + 1]:
+                if rest is not None:
+                    D1 = rest.project(D1, self._guide_eval(model, x1, t_dev[i + 1], class_labels)
+                                      if guided[2 * i + 1] else None, w_dev)
+                    x1 = ops.heun_correct(x, dx, x1, D1, t0, t1)
+                elif guided[2 * i + 1]:
                     Dg1 = self._guide_eval(model, x1, t_dev[i + 1], class_labels)
                     x1 = ops.heun_correct_guided(x, dx, x1, D1, Dg1, w_dev, t0, t1)
                 else:
@@ -279,8 +375,10 @@ class DeterministicSolver:
         return x1
 
     @torch.no_grad()
-    def solve(self, model, x0, class_labels=None, graph: bool = False, *, start_step: int = 0, image=None, mask=None):
+    def solve(self, model, x0, class_labels=None, graph: bool = False, *, start_step: int = 0, image=None, mask=None,
+              degradation=None, measurement=None):
         cond = self._conditioning(x0, start_step, image, mask)
+        rest = self._restoration(x0, mask, degradation, measurement)
         if not x0.is_cuda:
             raise RuntimeError("tinyedm_amd.DeterministicSolver: x0 must be a GPU tensor (there is no CPU path)")
         guided = self.guided_evaluations()
@@ -294,14 +392,16 @@ class DeterministicSolver:
             masked = mask is not None
             cond = _Conditioning(k, None if image is None else image.float().contiguous(), mask,
                                  ops.churn_record(self.seed, self.solve_index, x0.device) if masked else None)
+        if rest is not None:
+            rest = _Restoration(rest[0].scale, rest[0].gray, rest[1].float().contiguous())
         if not graph:
             t_dev = self.t_steps.to(x0.device)
             w_dev = torch.full((1,), float(self.guidance), device=x0.device) if any(guided) else None
             state = self._solve_state(x0, 0 if cond is None else cond.start)
-            out = self._loop(model, x0, class_labels, t_dev, guided, w_dev, state, cond).to(in_dtype)
+            out = self._loop(model, x0, class_labels, t_dev, guided, w_dev, state, cond, rest).to(in_dtype)
             self._solve_done(masked)
             return out
-        out = self._solve_graphed(model, x0, class_labels, guided, cond).to(in_dtype)
+        out = self._solve_graphed(model, x0, class_labels, guided, cond, rest=rest).to(in_dtype)
         # the Heun kernels leave a bit in the device health word when the state went non-finite: a replay that ran
         # with corrupted arguments fails HERE, loudly (one host sync per solve of 2N-1 network evaluations)
         ops.check_health(x0.device, "DeterministicSolver.solve(graph=True)")
@@ -444,7 +544,7 @@ class DeterministicSolver:
         return (logp, latent.to(in_dtype)) if return_latent else logp
 
     # ------------------------------------------------------------------ hipGraph
-    def _solve_graphed(self, model, x0, class_labels, guided, cond=None, invert_to=None, nll=None):
+    def _solve_graphed(self, model, x0, class_labels, guided, cond=None, invert_to=None, nll=None, rest=None):
         """replay (after capturing, the first time) the solve, or with invert_to = its end step the inversion of x0, or
         with nll = (end step, probes, delta, probe widths) its likelihood"""
         # graphs are cached PER MODEL OBJECT (weakly: a new model allocated at a dead one's address must not replay the
@@ -482,6 +582,8 @@ class DeterministicSolver:
         if cond is not None:        # (the plain solve keeps the key it always had)
             key += ("conditioned", cond.start, cond.image is not None,
                     None if cond.mask is None else tuple(cond.mask.shape))
+        if rest is not None:        # the measurement itself is the entry's static copy: a new y replays the same graph
+            key += ("restore", rest.scale, rest.gray, tuple(rest.y.shape))
         ent = per_model.get(key)
         if ent is None:
             _runtime_env.require_graph_replay_safe("DeterministicSolver.solve(graph=True)")
@@ -499,6 +601,7 @@ class DeterministicSolver:
             # the entry's own image, mask and noise record: copied / rewritten before every replay, as sx and sl are
             sc = None if cond is None else _Conditioning(cond.start, *(None if v is None else v.clone()
                                                                       for v in cond[1:]))
+            sr = None if rest is None else rest._replace(y=rest.y.clone())
             if nll is not None:
                 def loop():
                     return self._nll_loop(model, sx, sl, t_dev, nll[0], nll[1], nll[3], state)
@@ -507,7 +610,7 @@ class DeterministicSolver:
                     return self._invert_loop(model, sx, sl, t_dev, invert_to)
             else:
                 def loop():
-                    return self._loop(model, sx, sl, t_dev, guided, w_dev, state, sc)
+                    return self._loop(model, sx, sl, t_dev, guided, w_dev, state, sc, sr)
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):          # warm-up outside capture (weight packs, lazy inits)
@@ -528,14 +631,16 @@ class DeterministicSolver:
                 old = per_model.pop(next(iter(per_model)))
                 torch.cuda.synchronize()
                 ops.release_capture(old[5])
-            ent = per_model[key] = (g, sx, sl, out, t_dev, token, w_dev, guide, state, sc)
+            ent = per_model[key] = (g, sx, sl, out, t_dev, token, w_dev, guide, state, sc, sr)
         else:
             per_model[key] = per_model.pop(key)              # most recently used last
             if nll is not None:
                 ops.churn_record(self.seed, self.solve_index, out=ent[8].rec)
             else:
                 self._write_solve_state(ent[8])
-        g, sx, sl, out, _, _, w_dev, _, _, sc = ent
+        g, sx, sl, out, _, _, w_dev, _, _, sc, sr = ent
+        if sr is not None:
+            sr.y.copy_(rest.y)
         if sc is not None:
             if sc.image is not None:
                 sc.image.copy_(cond.image)
@@ -767,7 +872,7 @@ class MultistepSolver(DeterministicSolver):
         L = int(self.order) if self.order > 1 else 0
         return _MultistepState(tuple(torch.empty_like(x0) for _ in range(L)), steps)
 
-    def _loop(self, model, x0, class_labels, t_dev, guided, w_dev, state=None, cond=None):
+    def _loop(self, model, x0, class_labels, t_dev, guided, w_dev, state=None, cond=None, rest=None):
         hist, N = state.hist, self.num_steps
         L = len(hist)
         ts = self.t_steps.tolist()
@@ -781,6 +886,8 @@ class MultistepSolver(DeterministicSolver):
                 x = self._blend(x, cond, ts[i], i)
             D = model(x, t_dev[i], class_labels).float().contiguous()
             Dg = self._guide_eval(model, x, t_dev[i], class_labels) if guided[i] else None
+            if rest is not None:        # m_i is the projected (and mixed) evaluation; the history stores it
+                D, Dg = rest.project(D, Dg, w_dev), None
             x = ops.dpm_multistep(x, D, a, c0, c1, c2, Dg=Dg, w_dev=None if Dg is None else w_dev,
                                   m1=hist[(i - 1) % L] if k >= 2 else None, m2=hist[(i - 2) % L] if k >= 3 else None,
                                   m_out=hist[i % L] if L and i < N - 1 else None)
