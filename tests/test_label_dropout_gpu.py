@@ -471,7 +471,7 @@ def test_self_guided_solve_is_the_label_free_evaluation(ops, kind):
     key = next(iter(sol._graphs[model]))
     assert ("unconditional",) in key                 # a constant tag, not the id of a wrapper
     ent = sol._graphs[model][key]
-    assert ent[7] is None                           # the entry holds no guide
+    assert ent.guide is None                        # the entry holds no guide
     # a new guidance weight replays the cached graph
     sol.guidance = 3.5
     eager = _solve(sol, model, x0, labels)

@@ -448,6 +448,84 @@ def test_captured_restoration_reports_corruption(ops, pair):
     assert torch.isfinite(sol.solve(main, x0, labels, graph=True, degradation=deg, measurement=y)).all()
 
 
+# ------------------------------------------------------------------ 6b. a replay refreshes every per-call input
+REPLAY_SCHED = dict(num_steps=5, sigma_min=0.01, sigma_max=20.0, rho=5.0)
+REPLAY_MODES = ["heun", "guided", "churned", "multistep3", "inpaint", "sdedit", "restore", "invert", "likelihood"]
+
+
+@pytest.fixture(scope="module")
+def f32x3_model(ops):
+    em, dm = tiny_cfgs(10)
+    return _edm(O.init_params(em, dm, torch.Generator().manual_seed(7)), em, dm, "f32x3")     # (the likelihood needs fp32)
+
+
+def _replay_inputs(ops, call):
+    """everything a call can pass, different for call 0 and call 1 (same shapes: the second call must replay)"""
+    import tinyedm_amd as T
+    g = torch.Generator().manual_seed(50 + call)
+    x0 = torch.randn(2, 3, 8, 8, generator=g).to(DEV)
+    labels = torch.randint(0, 10, (2,), generator=g).to(DEV)
+    image = (0.5 * torch.randn(2, 3, 8, 8, generator=g)).to(DEV)
+    mask = torch.zeros(1, 1, 8, 8, device=DEV)      # broadcast over the batch; both values present, another half per call
+    mask[..., :, :4] = 1.0
+    if call:
+        mask = 1.0 - mask.transpose(2, 3)
+    y = T.LinearDegradation(2).measure((0.5 * torch.randn(2, 3, 8, 8, generator=g)).to(DEV))
+    assert tuple(y.shape) == (2, 3, 4, 4)
+    return dict(x0=x0, labels=labels, image=image, mask=mask, y=y, guidance=(2.0, 3.5)[call], solve_index=(0, 7)[call])
+
+
+def _replay_solver(mode):
+    import tinyedm_amd as T
+    if mode == "guided":
+        return T.DeterministicSolver(**REPLAY_SCHED, seed=11, guide="unconditional", guidance=2.0)
+    if mode == "churned":
+        return T.StochasticSolver(**REPLAY_SCHED, seed=11, S_churn=30.0, S_min=0.3, S_max=8.0)
+    if mode == "multistep3":
+        return T.MultistepSolver(**REPLAY_SCHED, seed=11, order=3)
+    return T.DeterministicSolver(**REPLAY_SCHED, seed=11)
+
+
+def _replay_call(mode, sol, model, inp, graph):
+    import tinyedm_amd as T
+    x0, labels, image = inp["x0"], inp["labels"], inp["image"]
+    sol.solve_index = inp["solve_index"]
+    if mode == "guided":
+        sol.guidance = inp["guidance"]
+    if mode == "inpaint":
+        return sol.solve(model, x0, labels, graph, image=image, mask=inp["mask"])
+    if mode == "sdedit":
+        return sol.solve(model, x0, labels, graph, start_step=2, image=image)
+    if mode == "restore":
+        return sol.solve(model, x0, labels, graph, degradation=T.LinearDegradation(2), measurement=inp["y"])
+    if mode == "invert":
+        return sol.invert(model, image, labels, graph, end_step=1)
+    if mode == "likelihood":
+        return torch.cat([t.double().flatten() for t in sol.log_likelihood(
+            model, image, labels, graph, end_step=1, num_probes=2, return_latent=True)])
+    return sol.solve(model, x0, labels, graph)
+
+
+@pytest.mark.parametrize("mode", REPLAY_MODES)
+def test_replay_refreshes_every_per_call_input(ops, f32x3_model, mode):
+    """Capture each mode once, then call it again with EVERY per-call input changed (x0, labels, image, mask values,
+    measurement, guidance weight, solve_index): the replay must equal, bit for bit, a fresh eager solver given the same
+    inputs, and the cache must still hold the one entry.  A static tensor that a replay forgets to refresh keeps the
+    first call's value and fails here."""
+    sol = _replay_solver(mode)
+    results = []
+    for call in (0, 1):
+        inp = _replay_inputs(ops, call)
+        got = _replay_call(mode, sol, f32x3_model, inp, True)
+        want = _replay_call(mode, _replay_solver(mode), f32x3_model, inp, False)
+        assert torch.equal(got, want), (mode, call)
+        assert len(sol._graphs[f32x3_model]) == 1
+        results.append(got)
+    assert not torch.equal(results[0], results[1])
+    if mode == "churned":
+        assert any(s[0] for s in sol._churn_steps())        # (the schedule does churn on this table)
+
+
 # ------------------------------------------------------------------ 7. generate CLI
 CLI = ["--config_name", "cifar10_cond", "--num_samples", "4", "--batch_size", "4", "--num_steps", "4", "--num_classes",
        "10", "--image_size", "32", "--num_workers", "0"]

@@ -17,6 +17,7 @@ Reference call sites this replaces: the Lightning automatic-optimisation loop ar
 from __future__ import annotations
 
 import math
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -63,6 +64,14 @@ class StepParams:
         ev = torch.cuda.Event()
         ev.record()
         self._events[k] = ev
+
+
+class _CapturedStep(NamedTuple):
+    graph: torch.cuda.CUDAGraph
+    x: torch.Tensor         # static copy of the batch's images
+    y: object               # ... and of its labels, or None
+    loss: torch.Tensor      # static: rewritten by every replay
+    token: object           # launch-table slots and plan pins of the capture (ops.release_capture)
 
 
 class CapturedTrainStep:
@@ -176,7 +185,7 @@ class CapturedTrainStep:
         or None when the job falls back to the eager step (single rank: the exception propagates)."""
         ent, err = None, None
         try:
-            ent = self._capture(batch)
+            ent = _CapturedStep(*self._capture(batch))
         except Exception as e:      # noqa: BLE001
             err = e
         multi = self.reducer is not None and self.reducer.world > 1
@@ -201,7 +210,7 @@ class CapturedTrainStep:
         self._upload()
         networks.rng.dyn = self.params.dev
         try:
-            ent = self._graphs.get(key)
+            ent = ops.lru_get(self._graphs, key)
             seen = self._seen.get(key, 0)
             self._seen[key] = seen + 1
             # (a batch shape is captured on its SECOND visit: its first step runs eagerly so that the plans / scratch of that
@@ -209,19 +218,15 @@ class CapturedTrainStep:
             if ent is None and not self.fallback and self._calls >= self.WARMUP and seen >= 1:
                 ent = self._capture_agreed(batch)
                 if ent is not None:
-                    while len(self._graphs) >= self.MAX_GRAPHS:      # (dict order = least recently used first)
-                        self._drop(next(iter(self._graphs)))
-                    self._graphs[key] = ent
-            elif ent is not None:
-                self._graphs[key] = self._graphs.pop(key)            # most recently used last
+                    ops.lru_put(self._graphs, key, ent, self.MAX_GRAPHS)
             if ent is None:
                 loss = self._eager(batch)          # allocator / plan / stream warm-up before capturing; the fallback
             else:
-                graph, sx, sy, loss, _tok = ent
-                sx.copy_(x, non_blocking=True)
-                if sy is not None:
-                    sy.copy_(y, non_blocking=True)
-                graph.replay()
+                loss = ent.loss
+                ent.x.copy_(x, non_blocking=True)
+                if ent.y is not None:
+                    ent.y.copy_(y, non_blocking=True)
+                ent.graph.replay()
         finally:
             networks.rng.dyn = None
         self._calls += 1
@@ -243,14 +248,13 @@ class CapturedTrainStep:
             import time
             time.sleep(0.5)
             mode = "thread_local"
-        ops.capture_begin()
-        failed = False
         graph = torch.cuda.CUDAGraph()
         # the step is captured as ONE chain: a weight-gradient side branch replays slower than the chain (CIFAR-10:
         # 15.5 vs 15.1 ms) -- hipGraph schedules the branch less favourably than the host's enqueue order does
         side, networks.WGRAD_STREAM = networks.WGRAD_STREAM, self.wgrad_fork
         try:
-            with torch.cuda.graph(graph, stream=self.stream, capture_error_mode=mode):
+            # (a failed capture leaves no graph: capturing() gives its launch-table slots back)
+            with ops.capturing(graph, stream=self.stream, capture_error_mode=mode) as capture:
                 loss = self.model.training_step((sx, sy), 0)
                 _backward(self.model, loss)     # the reducer's hooks fork the comm stream off the capture stream ...
                 if self.reducer is not None:
@@ -260,21 +264,14 @@ class CapturedTrainStep:
         except BaseException:
             if self.reducer is not None:
                 self.reducer.reset()        # pending counts / fired set of the aborted pass
-            failed = True
             raise
         finally:
             networks.WGRAD_STREAM = side
-            token = ops.capture_end()
-            if failed:
-                ops.release_capture(token)  # no graph came of it: its launch-table slots are free again
             self._restore(snap)
-        return graph, sx, sy, loss, token
+        return graph, sx, sy, loss, capture.token
 
     def _drop(self, key):
-        ent = self._graphs.pop(key, None)
-        if ent is not None:
-            torch.cuda.synchronize()            # no replay of it may still be running when its slots are reused
-            ops.release_capture(ent[4])
+        ops.drop_capture(self._graphs, key)
 
     def release(self):
         """drop every captured graph (their launch-table slots go back to the pool): call when the step object is retired"""
@@ -286,6 +283,6 @@ class CapturedTrainStep:
             if self._graphs:
                 torch.cuda.synchronize()        # (a replay of a dying graph may still be running: see _drop)
             for ent in self._graphs.values():
-                ops.release_capture(ent[4])
+                ops.release_capture(ent.token)
         except Exception:       # noqa: BLE001  (interpreter shutdown)
             pass

@@ -4,9 +4,11 @@ that faults can take the whole GPU node down), then pass raw pointers + the curr
 Layout conventions: activations are NHWC bf16 tensors of shape (B, H, W, C) (contiguous);
 "rows" means B*H*W.  Per-(sample,channel) quantities are fp32 (B, C).
 """
+import contextlib
 import ctypes
 import math
 import os
+import types
 from typing import Optional
 
 import torch
@@ -126,6 +128,49 @@ def release_capture(token):
     """the graph captured between the capture_begin() / capture_end() that returned `token` no longer exists: its
     launch-table slots may be reused by later captures (a long-lived process that re-captures does not grow)"""
     _tables.release(token)
+
+
+@contextlib.contextmanager
+def capturing(graph, **kw):
+    """`with capturing(g) as capture:` records the body into the torch.cuda.CUDAGraph `g` (`kw` goes to torch.cuda.graph)
+    between capture_begin() and capture_end().  Afterwards `capture.token` is the token of capture_end(), to be kept with
+    the graph; when the body (or the capture itself) raised, no graph came of it and the token is released here."""
+    capture = types.SimpleNamespace(token=None)
+    capture_begin()
+    ok = False
+    try:
+        with torch.cuda.graph(graph, **kw):
+            yield capture
+        ok = True
+    finally:
+        capture.token = capture_end()
+        if not ok:
+            release_capture(capture.token)
+
+
+# A cache of captured graphs is a plain dict in least-recently-used order (oldest first) whose entries carry the
+# `.token` of their capture.
+def drop_capture(cache: dict, key) -> None:
+    """forget cache[key] and give back what its capture took"""
+    ent = cache.pop(key, None)
+    if ent is not None:
+        torch.cuda.synchronize()            # no replay of it may still be running when its slots are reused
+        release_capture(ent.token)
+
+
+def lru_get(cache: dict, key):
+    """cache[key], now the most recently used; None on a miss"""
+    ent = cache.pop(key, None)
+    if ent is not None:
+        cache[key] = ent
+    return ent
+
+
+def lru_put(cache: dict, key, ent, limit: int) -> None:
+    """insert a freshly captured entry, dropping the least recently used ones so that at most `limit` remain"""
+    while len(cache) >= limit:
+        drop_capture(cache, next(iter(cache)))
+    cache[key] = ent
 
 
 class _LaunchTables:

@@ -9,6 +9,7 @@ from typing import NamedTuple
 import torch
 
 from . import _runtime_env, ops
+from .networks import Denoiser
 
 UNCONDITIONAL = "unconditional"     # guide= sentinel: the model's own label-free evaluation is the guide
 
@@ -17,10 +18,57 @@ def _is_unconditional(guide) -> bool:
     return isinstance(guide, str) and guide == UNCONDITIONAL
 
 
+def _check_step(who: str, name: str, step, num_steps: int) -> None:
+    if isinstance(step, bool) or not isinstance(step, int) or not 0 <= step < num_steps:
+        raise ValueError(f"{who}: {name} must be an integer in [0, {num_steps - 1}], got {step!r}")
+
+
+def _check_float(who: str, name: str, t) -> None:
+    if not isinstance(t, torch.Tensor) or not t.dtype.is_floating_point:
+        raise ValueError(f"{who}: {name} must be a floating-point tensor")
+
+
+def _check_gpu(cls: str, name: str, t) -> None:
+    if not t.is_cuda:
+        raise RuntimeError(f"tinyedm_amd.{cls}: {name} must be a GPU tensor (there is no CPU path)")
+
+
+def _denoisers(net):
+    """(module, its eval_dtype) of every Denoiser of a network -- the modules that own an evaluation precision and
+    eval-mode weight packs; nothing for a plain callable"""
+    if isinstance(net, torch.nn.Module):
+        for m in net.modules():
+            if isinstance(m, Denoiser):
+                yield m, m.eval_dtype
+
+
+class _Captured(NamedTuple):
+    """one captured solve: the graph, the static tensors it reads and writes, and what its destruction gives back"""
+    graph: object           # torch.cuda.CUDAGraph
+    x: torch.Tensor         # static copy of x0 (or of the image of invert / log_likelihood)
+    labels: object          # static copy of the class labels, or None
+    out: object             # what the captured loop returned (static: cloned after every replay)
+    t_dev: torch.Tensor     # the sigma table on the device
+    token: object           # launch-table slots and plan pins of the capture (ops.release_capture)
+    w_dev: object           # the guidance weight the graph reads, or None for an unguided solve
+    guide: object           # the guide network (kept alive: the key holds its id); None for none or 'unconditional'
+    state: object           # the mode's device state: _ChurnState, _MultistepState, _NllState or None
+    cond: object            # static _Conditioning, or None
+    rest: object            # static _Restoration, or None
+
+
+class _Mode(NamedTuple):
+    """what a captured entry runs, built by the entry point that knows it (solve, invert, log_likelihood)"""
+    key: tuple              # what the mode appends to the graph key
+    state: object           # () -> the entry's own device state, written for this call; or None
+    loop: object            # (entry) -> the result, run on the entry's static tensors
+    rewrite: object         # (state) -> None: rewrite that state host to device before a replay
+
+
 def _release_solves(per_model: dict):
     try:
         for ent in per_model.values():
-            ops.release_capture(ent[5])
+            ops.release_capture(ent.token)
         per_model.clear()
     except Exception:       # noqa: BLE001  (interpreter shutdown)
         pass
@@ -81,11 +129,9 @@ class LinearDegradation:
 
     def measure(self, image) -> torch.Tensor:
         """y = A image (ops.degrade), fp32.  ``image``: a floating-point GPU tensor [B, C, H, W]."""
-        if not isinstance(image, torch.Tensor) or not image.dtype.is_floating_point:
-            raise ValueError("LinearDegradation.measure: image must be a floating-point tensor")
+        _check_float("LinearDegradation.measure", "image", image)
         self.measurement_shape(image.shape)
-        if not image.is_cuda:
-            raise RuntimeError("tinyedm_amd.LinearDegradation: image must be a GPU tensor (there is no CPU path)")
+        _check_gpu("LinearDegradation", "image", image)
         return ops.degrade(image.float().contiguous(), self.scale, self.gray)
 
     def pinv(self, y, channels: int) -> torch.Tensor:
@@ -100,8 +146,7 @@ class LinearDegradation:
         if tuple(y.shape) != self.measurement_shape(shape):
             raise ValueError(f"LinearDegradation.pinv: y of shape {tuple(y.shape)} is no measurement of a "
                              f"{channels}-channel image")
-        if not y.is_cuda:
-            raise RuntimeError("tinyedm_amd.LinearDegradation: y must be a GPU tensor (there is no CPU path)")
+        _check_gpu("LinearDegradation", "y", y)
         return ops.project_denoised(torch.zeros(shape, device=y.device), y.float().contiguous(), self.scale, self.gray)
 
 
@@ -235,15 +280,13 @@ class DeterministicSolver:
     def _conditioning(self, x0, start_step, image, mask):
         """Validate start_step / image / mask of a solve against x0 on the host (shapes, dtypes and devices: nothing is
         read from a device) and return (start, image, mask as uint8 [B or 1, H*W]); None for the plain solve."""
-        if isinstance(start_step, bool) or not isinstance(start_step, int) or not 0 <= start_step < self.num_steps:
-            raise ValueError(f"solve: start_step must be an integer in [0, {self.num_steps - 1}], got {start_step!r}")
+        _check_step("solve", "start_step", start_step, self.num_steps)
         if mask is not None and image is None:
             raise ValueError("solve: mask needs image (the known pixels)")
         if image is None and start_step == 0:
             return None
         if image is not None:
-            if not isinstance(image, torch.Tensor) or not image.dtype.is_floating_point:
-                raise ValueError("solve: image must be a floating-point tensor")
+            _check_float("solve", "image", image)
             if tuple(image.shape) != tuple(x0.shape):
                 raise ValueError(f"solve: image must have x0's shape {tuple(x0.shape)}, got {tuple(image.shape)}")
         if mask is not None:
@@ -279,8 +322,7 @@ class DeterministicSolver:
         if mask is not None:
             raise ValueError("solve: mask (inpainting by replacement) and measurement (restoration) are two "
                              "conditionings; their combination is not implemented")
-        if not isinstance(measurement, torch.Tensor) or not measurement.dtype.is_floating_point:
-            raise ValueError("solve: measurement must be a floating-point tensor")
+        _check_float("solve", "measurement", measurement)
         if x0.dim() != 4:
             raise ValueError(f"solve: a measurement needs x0 of shape [B, C, H, W], got {tuple(x0.shape)}")
         shape = degradation.measurement_shape(x0.shape)
@@ -340,47 +382,50 @@ class DeterministicSolver:
         return self.guide(x, sigma, class_labels).float().contiguous()
 
     # ------------------------------------------------------------------ eager
+    def _evaluate(self, model, x, sigma, class_labels, guided: bool, w_dev, rest):
+        """One network evaluation at (x, sigma): (D, Dg).  Dg is the guide's evaluation when this one is guided and the
+        update kernel is to mix it in; with a restoration the projection has mixed it already and D is the projected
+        (and mixed) evaluation, for the unguided update."""
+        D = model(x, sigma, class_labels).float().contiguous()
+        Dg = self._guide_eval(model, x, sigma, class_labels) if guided else None
+        if rest is not None:
+            return rest.project(D, Dg, w_dev), None
+        return D, Dg
+
+    def _step(self, evaluate, x1, i, ts, t_dev, guided, w_dev, state):
+        """step i of the loop, t_i -> t_{i+1}: Euler and, but for the last step, the Heun correction"""
+        x, t0, s0 = self._step_start(x1, i, ts, t_dev, state)
+        t1 = ts[i + 1]
+        D, Dg = evaluate(x, s0, guided[2 * i])
+        dx, x1 = ops.heun_euler(x, D, t0, t1) if Dg is None else ops.heun_euler_guided(x, D, Dg, w_dev, t0, t1)
+        if i < self.num_steps - 1:
+            D1, Dg1 = evaluate(x1, t_dev[i + 1], guided[2 * i + 1])
+            x1 = ops.heun_correct(x, dx, x1, D1, t0, t1) if Dg1 is None else \
+                ops.heun_correct_guided(x, dx, x1, D1, Dg1, w_dev, t0, t1)
+        return x1
+
     def _loop(self, model, x0, class_labels, t_dev, guided, w_dev, state=None, cond=None, rest=None):
         ts = self.t_steps.tolist()
         k = 0 if cond is None else cond.start
         masked = cond is not None and cond.mask is not None
-        x1 = ops.scale_f32(x0, ts[0]) if cond is None else ops.state_init(x0, ts[k], cond.image)
+
+        def evaluate(x, sigma, flag):
+            return self._evaluate(model, x, sigma, class_labels, flag, w_dev, rest)
+        x = ops.scale_f32(x0, ts[0]) if cond is None else ops.state_init(x0, ts[k], cond.image)
         for i in range(k, self.num_steps):
             if masked:
-                x1 = self._blend(x1, cond, ts[i], i)
-            x, t0, s0 = self._step_start(x1, i, ts, t_dev, state)
-            t1 = ts[i + 1]
-            D = model(x, s0, class_labels).float().contiguous()
-            if rest is not None:        # the projected (and mixed) evaluation, then the unguided update
-                D = rest.project(D, self._guide_eval(model, x, s0, class_labels) if guided[2 * i] else None, w_dev)
-                dx, x1 = ops.heun_euler(x, D, t0, t1)
-            elif guided[2 * i]:
-                Dg = self._guide_eval(model, x, s0, class_labels)
-                dx, x1 = ops.heun_euler_guided(x, D, Dg, w_dev, t0, t1)
-            else:
-                dx, x1 = ops.heun_euler(x, D, t0, t1)
-            if i < self.num_steps - 1:
-                D1 = model(x1, t_dev[i + 1], class_labels).float().contiguous()
-                if rest is not None:
-                    D1 = rest.project(D1, self._guide_eval(model, x1, t_dev[i + 1], class_labels)
-                                      if guided[2 * i + 1] else None, w_dev)
-                    x1 = ops.heun_correct(x, dx, x1, D1, t0, t1)
-                elif guided[2 * i + 1]:
-                    Dg1 = self._guide_eval(model, x1, t_dev[i + 1], class_labels)
-                    x1 = ops.heun_correct_guided(x, dx, x1, D1, Dg1, w_dev, t0, t1)
-                else:
-                    x1 = ops.heun_correct(x, dx, x1, D1, t0, t1)
+                x = self._blend(x, cond, ts[i], i)
+            x = self._step(evaluate, x, i, ts, t_dev, guided, w_dev, state)
         if masked:
-            x1 = self._blend(x1, cond, 0.0, self.num_steps)
-        return x1
+            x = self._blend(x, cond, 0.0, self.num_steps)
+        return x
 
     @torch.no_grad()
     def solve(self, model, x0, class_labels=None, graph: bool = False, *, start_step: int = 0, image=None, mask=None,
               degradation=None, measurement=None):
         cond = self._conditioning(x0, start_step, image, mask)
         rest = self._restoration(x0, mask, degradation, measurement)
-        if not x0.is_cuda:
-            raise RuntimeError("tinyedm_amd.DeterministicSolver: x0 must be a GPU tensor (there is no CPU path)")
+        _check_gpu("DeterministicSolver", "x0", x0)
         guided = self.guided_evaluations()
         if any(guided):
             self._check_guide(model, x0.device, class_labels)
@@ -394,14 +439,18 @@ class DeterministicSolver:
                                  ops.churn_record(self.seed, self.solve_index, x0.device) if masked else None)
         if rest is not None:
             rest = _Restoration(rest[0].scale, rest[0].gray, rest[1].float().contiguous())
+        start = 0 if cond is None else cond.start
         if not graph:
             t_dev = self.t_steps.to(x0.device)
             w_dev = torch.full((1,), float(self.guidance), device=x0.device) if any(guided) else None
-            state = self._solve_state(x0, 0 if cond is None else cond.start)
+            state = self._solve_state(x0, start)
             out = self._loop(model, x0, class_labels, t_dev, guided, w_dev, state, cond, rest).to(in_dtype)
             self._solve_done(masked)
             return out
-        out = self._solve_graphed(model, x0, class_labels, guided, cond, rest=rest).to(in_dtype)
+        mode = _Mode(self._graph_key_extra(start), lambda: self._solve_state(x0, start),
+                     lambda e: self._loop(model, e.x, e.labels, e.t_dev, guided, e.w_dev, e.state, e.cond, e.rest),
+                     self._write_solve_state)
+        out = self._solve_graphed(model, x0, class_labels, mode, guided, cond, rest).to(in_dtype)
         # the Heun kernels leave a bit in the device health word when the state went non-finite: a replay that ran
         # with corrupted arguments fails HERE, loudly (one host sync per solve of 2N-1 network evaluations)
         ops.check_health(x0.device, "DeterministicSolver.solve(graph=True)")
@@ -432,17 +481,16 @@ class DeterministicSolver:
         ``solve``'s x0: ``solve(model, invert(model, img, end_step=k), start_step=k)`` closes the loop.  Only D_main is
         evaluated: guided inversion is not implemented, ``guide`` and ``guidance`` are ignored here."""
         self._check_invert()
-        if isinstance(end_step, bool) or not isinstance(end_step, int) or not 0 <= end_step < self.num_steps:
-            raise ValueError(f"invert: end_step must be an integer in [0, {self.num_steps - 1}], got {end_step!r}")
-        if not isinstance(image, torch.Tensor) or not image.dtype.is_floating_point:
-            raise ValueError("invert: image must be a floating-point tensor")
-        if not image.is_cuda:
-            raise RuntimeError("tinyedm_amd.DeterministicSolver: image must be a GPU tensor (there is no CPU path)")
+        _check_step("invert", "end_step", end_step, self.num_steps)
+        _check_float("invert", "image", image)
+        _check_gpu("DeterministicSolver", "image", image)
         in_dtype = image.dtype
         image = image.float().contiguous()
         if not graph:
             return self._invert_loop(model, image, class_labels, self.t_steps.to(image.device), end_step).to(in_dtype)
-        out = self._solve_graphed(model, image, class_labels, (), None, end_step).to(in_dtype)
+        mode = _Mode(("invert", end_step), lambda: None,
+                     lambda e: self._invert_loop(model, e.x, e.labels, e.t_dev, end_step), lambda state: None)
+        out = self._solve_graphed(model, image, class_labels, mode).to(in_dtype)
         ops.check_health(image.device, "DeterministicSolver.invert(graph=True)")
         return out
 
@@ -460,6 +508,10 @@ class DeterministicSolver:
             raise ValueError(f"log_likelihood: delta must be finite and > 0, got {delta!r}")
         t = self.t_steps[:self.num_steps].double()
         return (d * (t * t + float(sigma_data) ** 2).sqrt()).float().tolist()
+
+    def _nll_state(self, image) -> _NllState:
+        return _NllState(ops.churn_record(self.seed, self.solve_index, image.device),
+                         torch.zeros(image.shape[0], dtype=torch.float64, device=image.device))
 
     def _nll_loop(self, model, image, class_labels, t_dev, end_step, K, hs, state):
         ts = self.t_steps.tolist()
@@ -502,15 +554,12 @@ class DeterministicSolver:
         implemented, ``guide`` and ``guidance`` are ignored here, as in ``invert``.  With ``return_latent`` the result
         is (logp, latent), latent the unit-scale x_k / t_k that ``invert`` returns, bit for bit."""
         self._check_invert()
-        if isinstance(end_step, bool) or not isinstance(end_step, int) or not 0 <= end_step < self.num_steps:
-            raise ValueError(f"log_likelihood: end_step must be an integer in [0, {self.num_steps - 1}], got "
-                             f"{end_step!r}")
+        _check_step("log_likelihood", "end_step", end_step, self.num_steps)
         if isinstance(num_probes, bool) or not isinstance(num_probes, int) or \
                 not 1 <= num_probes <= ops.NLL_MAX_PROBES:
             raise ValueError(f"log_likelihood: num_probes must be an integer in [1, {ops.NLL_MAX_PROBES}], got "
                              f"{num_probes!r}")
-        if not isinstance(image, torch.Tensor) or not image.dtype.is_floating_point:
-            raise ValueError("log_likelihood: image must be a floating-point tensor")
+        _check_float("log_likelihood", "image", image)
         if image.dim() < 2 or image.numel() == 0:
             raise ValueError(f"log_likelihood: image must be a non-empty [B, ...] tensor, got {tuple(image.shape)}")
         if self.num_steps >= ops.NLL_MAX_STEPS:
@@ -518,35 +567,33 @@ class DeterministicSolver:
         self._check_stream()
         owner = getattr(model, "__self__", model)
         hs = self.probe_widths(getattr(owner, "sigma_data", 0.5))
-        if isinstance(owner, torch.nn.Module):
-            for m in owner.modules():
-                if getattr(m, "eval_dtype", None) == "bf16":
-                    raise ValueError("log_likelihood: the network evaluates in bf16; a difference quotient needs the fp32 "
-                                     "evaluation path (set_eval_dtype('f32x3') or 'f32')")
-                if hasattr(m, "eval_dtype") and m.training:
-                    raise ValueError("log_likelihood: the network is in training mode; call model.eval()")
-        if not image.is_cuda:
-            raise RuntimeError("tinyedm_amd.DeterministicSolver: image must be a GPU tensor (there is no CPU path)")
+        for m, eval_dtype in _denoisers(owner):
+            if eval_dtype == "bf16":
+                raise ValueError("log_likelihood: the network evaluates in bf16; a difference quotient needs the fp32 "
+                                 "evaluation path (set_eval_dtype('f32x3') or 'f32')")
+            if m.training:
+                raise ValueError("log_likelihood: the network is in training mode; call model.eval()")
+        _check_gpu("DeterministicSolver", "image", image)
         in_dtype = image.dtype
         image = image.float().contiguous()
         if class_labels is not None:        # one label row per row of the evaluation batch
             class_labels = class_labels.repeat(1 + 2 * num_probes, *([1] * (class_labels.dim() - 1)))
         if not graph:
-            state = _NllState(ops.churn_record(self.seed, self.solve_index, image.device),
-                              torch.zeros(image.shape[0], dtype=torch.float64, device=image.device))
             logp, latent = self._nll_loop(model, image, class_labels, self.t_steps.to(image.device), end_step,
-                                          num_probes, hs, state)
+                                          num_probes, hs, self._nll_state(image))
         else:
-            logp, latent = self._solve_graphed(model, image, class_labels, (), None, None,
-                                               (end_step, num_probes, float(self.delta), hs))
+            mode = _Mode(("nll", end_step, num_probes, float(self.delta)), lambda: self._nll_state(image),
+                         lambda e: self._nll_loop(model, e.x, e.labels, e.t_dev, end_step, num_probes, hs, e.state),
+                         lambda state: ops.churn_record(self.seed, self.solve_index, out=state.rec))
+            logp, latent = self._solve_graphed(model, image, class_labels, mode)
             ops.check_health(image.device, "DeterministicSolver.log_likelihood(graph=True)")
         self.solve_index += 1
         return (logp, latent.to(in_dtype)) if return_latent else logp
 
     # ------------------------------------------------------------------ hipGraph
-    def _solve_graphed(self, model, x0, class_labels, guided, cond=None, invert_to=None, nll=None, rest=None):
-        """replay (after capturing, the first time) the solve, or with invert_to = its end step the inversion of x0, or
-        with nll = (end step, probes, delta, probe widths) its likelihood"""
+    def _solve_graphed(self, model, x0, class_labels, mode: _Mode, guided=(), cond=None, rest=None):
+        """replay (after capturing, the first time) what ``mode`` describes on x0: the solve, the inversion or the
+        likelihood"""
         # graphs are cached PER MODEL OBJECT (weakly: a new model allocated at a dead one's address must not replay the
         # dead one's graph, which id(model) as a key allowed)
         owner = getattr(model, "__self__", model)        # a bound method is a fresh object per access: key on its object
@@ -558,9 +605,7 @@ class DeterministicSolver:
         # the evaluation precision of the denoiser(s) is part of the key: set_eval_dtype() between two solves must not
         # replay a graph captured with the other path's kernels
         def eval_dtypes(net):
-            if not isinstance(net, torch.nn.Module):
-                return ()
-            return tuple(getattr(m, "eval_dtype", None) for m in net.modules() if hasattr(m, "eval_dtype"))
+            return tuple(d for _, d in _denoisers(net))
         key = (tuple(x0.shape), None if class_labels is None else tuple(class_labels.shape), x0.device.index,
                eval_dtypes(owner))
         # a guided solve also keys on the guide (the entry holds it, so its id cannot be reused while the graph that
@@ -573,95 +618,56 @@ class DeterministicSolver:
             key += ((UNCONDITIONAL,), guided)
         elif guide is not None:
             key += (id(guide), eval_dtypes(guide), guided)
-        if nll is not None:
-            key += ("nll",) + nll[:3]
-        elif invert_to is not None:
-            key += ("invert", invert_to)
-        else:
-            key += self._graph_key_extra(0 if cond is None else cond.start)
+        key += mode.key
         if cond is not None:        # (the plain solve keeps the key it always had)
             key += ("conditioned", cond.start, cond.image is not None,
                     None if cond.mask is None else tuple(cond.mask.shape))
         if rest is not None:        # the measurement itself is the entry's static copy: a new y replays the same graph
             key += ("restore", rest.scale, rest.gray, tuple(rest.y.shape))
-        ent = per_model.get(key)
-        if ent is None:
+        ent = ops.lru_get(per_model, key)
+        fresh = ent is None
+        if fresh:
             _runtime_env.require_graph_replay_safe("DeterministicSolver.solve(graph=True)")
-            t_dev = self.t_steps.to(x0.device)
-            w_dev = None if guide is None else torch.full((1,), float(self.guidance), device=x0.device)
-            if _is_unconditional(guide):
-                guide = None
-            if nll is not None:
-                state = _NllState(ops.churn_record(self.seed, self.solve_index, x0.device),
-                                  torch.zeros(x0.shape[0], dtype=torch.float64, device=x0.device))
-            else:
-                state = None if invert_to is not None else self._solve_state(x0, 0 if cond is None else cond.start)
-            sx = x0.clone()
-            sl = None if class_labels is None else class_labels.clone()
-            # the entry's own image, mask and noise record: copied / rewritten before every replay, as sx and sl are
-            sc = None if cond is None else _Conditioning(cond.start, *(None if v is None else v.clone()
-                                                                      for v in cond[1:]))
-            sr = None if rest is None else rest._replace(y=rest.y.clone())
-            if nll is not None:
-                def loop():
-                    return self._nll_loop(model, sx, sl, t_dev, nll[0], nll[1], nll[3], state)
-            elif invert_to is not None:
-                def loop():
-                    return self._invert_loop(model, sx, sl, t_dev, invert_to)
-            else:
-                def loop():
-                    return self._loop(model, sx, sl, t_dev, guided, w_dev, state, sc, sr)
+            # the entry's own tensors: x, labels, image, mask, noise record and y are copied before every replay
+            ent = _Captured(
+                graph=torch.cuda.CUDAGraph(), x=x0.clone(), labels=None if class_labels is None else class_labels.clone(),
+                out=None, t_dev=self.t_steps.to(x0.device), token=None,
+                w_dev=None if guide is None else torch.full((1,), float(self.guidance), device=x0.device),
+                guide=None if _is_unconditional(guide) else guide, state=mode.state(),
+                cond=None if cond is None else _Conditioning(cond.start, *(None if v is None else v.clone()
+                                                                           for v in cond[1:])),
+                rest=None if rest is None else rest._replace(y=rest.y.clone()))
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):          # warm-up outside capture (weight packs, lazy inits)
-                loop()
+                mode.loop(ent)
             torch.cuda.current_stream().wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            ops.capture_begin()
-            ok = False
-            try:
-                with torch.cuda.graph(g):
-                    out = loop()
-                ok = True
-            finally:
-                token = ops.capture_end()
-                if not ok:
-                    ops.release_capture(token)
-            while len(per_model) >= self.MAX_GRAPHS:         # (dict order = least recently used first)
-                old = per_model.pop(next(iter(per_model)))
-                torch.cuda.synchronize()
-                ops.release_capture(old[5])
-            ent = per_model[key] = (g, sx, sl, out, t_dev, token, w_dev, guide, state, sc, sr)
-        else:
-            per_model[key] = per_model.pop(key)              # most recently used last
-            if nll is not None:
-                ops.churn_record(self.seed, self.solve_index, out=ent[8].rec)
-            else:
-                self._write_solve_state(ent[8])
-        g, sx, sl, out, _, _, w_dev, _, _, sc, sr = ent
-        if sr is not None:
-            sr.y.copy_(rest.y)
-        if sc is not None:
-            if sc.image is not None:
-                sc.image.copy_(cond.image)
-            if sc.mask is not None:
-                sc.mask.copy_(cond.mask)
-                sc.rec.copy_(cond.rec)
+            with ops.capturing(ent.graph) as capture:
+                out = mode.loop(ent)
+            ent = ent._replace(out=out, token=capture.token)
+            ops.lru_put(per_model, key, ent, self.MAX_GRAPHS)
         # the captured evaluations read the persistent eval-mode weight packs: refresh them (a no-op unless the
         # master weights changed since the last solve: optimizer steps, EMA swap, load_state_dict) before replaying
-        from .networks import Denoiser
-        for net in (model, guide):
-            if isinstance(net, torch.nn.Module):
-                for m in net.modules():
-                    if isinstance(m, Denoiser) and not m.training:
-                        m._prep_all()
-        if w_dev is not None:
-            w_dev.fill_(float(self.guidance))
-        sx.copy_(x0)
-        if sl is not None:
-            sl.copy_(class_labels)
-        g.replay()
-        return tuple(o.clone() for o in out) if isinstance(out, tuple) else out.clone()
+        for net in (model, ent.guide):
+            for m, _ in _denoisers(net):
+                if not m.training:
+                    m._prep_all()
+        # what a replay reads that this call sets: the mode's state (a fresh entry's was written when it was made), the
+        # guidance weight, and every per-call input as (the entry's static tensor, this call's value)
+        if not fresh:
+            mode.rewrite(ent.state)
+        if ent.w_dev is not None:
+            ent.w_dev.fill_(float(self.guidance))
+        inputs = [(ent.x, x0), (ent.labels, class_labels)]
+        if ent.rest is not None:
+            inputs.append((ent.rest.y, rest.y))
+        if ent.cond is not None:
+            inputs += [(ent.cond.image, cond.image), (ent.cond.mask, cond.mask), (ent.cond.rec, cond.rec)]
+        for static, value in inputs:
+            if static is not None:
+                static.copy_(value)
+        ent.graph.replay()
+        return tuple(o.clone() for o in ent.out) if isinstance(ent.out, tuple) else ent.out.clone()
 
 
 class ChurnSchedule(NamedTuple):
@@ -724,8 +730,7 @@ class StochasticSolver(DeterministicSolver):
             raise ValueError(f"StochasticSolver: S_noise must be finite and >= 0, got {self.S_noise}")
         if not 0.0 <= S_min <= S_max:
             raise ValueError(f"StochasticSolver: needs 0 <= S_min <= S_max, got S_min={self.S_min}, S_max={self.S_max}")
-        _check_uint(self.seed, 64, "seed")
-        _check_uint(self.solve_index, 32, "solve_index")
+        self._check_stream()
         t = self.t_steps[:-1].double()
         g = min(S_churn / self.num_steps, math.sqrt(2.0) - 1.0)
         gamma = ((t >= S_min) & (t <= S_max)).double() * g
@@ -815,8 +820,7 @@ class MultistepSolver(DeterministicSolver):
         start_step are those of a full solve; such a solve does not run them)"""
         _check_multistep(self.num_steps, self.order)
         N, order = self.num_steps, int(self.order)
-        if isinstance(start_step, bool) or not isinstance(start_step, int) or not 0 <= start_step < N:
-            raise ValueError(f"MultistepSolver: start_step must be an integer in [0, {N - 1}], got {start_step!r}")
+        _check_step("MultistepSolver", "start_step", start_step, N)
         sig = self.t_steps.double().tolist()                # fp64 from the fp32 table
         lam = [-math.log(v) for v in sig[:N]]               # lambda_N = +inf
         steps = []
@@ -872,25 +876,10 @@ class MultistepSolver(DeterministicSolver):
         L = int(self.order) if self.order > 1 else 0
         return _MultistepState(tuple(torch.empty_like(x0) for _ in range(L)), steps)
 
-    def _loop(self, model, x0, class_labels, t_dev, guided, w_dev, state=None, cond=None, rest=None):
-        hist, N = state.hist, self.num_steps
+    def _step(self, evaluate, x, i, ts, t_dev, guided, w_dev, state):
+        hist, (k, a, c0, c1, c2) = state.hist, state.steps[i]
         L = len(hist)
-        ts = self.t_steps.tolist()
-        start = 0 if cond is None else cond.start
-        masked = cond is not None and cond.mask is not None
-        x = ops.scale_f32(x0, self.t_steps[0].item()) if cond is None else ops.state_init(x0, ts[start], cond.image)
-        for i, (k, a, c0, c1, c2) in enumerate(state.steps):
-            if i < start:
-                continue
-            if masked:
-                x = self._blend(x, cond, ts[i], i)
-            D = model(x, t_dev[i], class_labels).float().contiguous()
-            Dg = self._guide_eval(model, x, t_dev[i], class_labels) if guided[i] else None
-            if rest is not None:        # m_i is the projected (and mixed) evaluation; the history stores it
-                D, Dg = rest.project(D, Dg, w_dev), None
-            x = ops.dpm_multistep(x, D, a, c0, c1, c2, Dg=Dg, w_dev=None if Dg is None else w_dev,
-                                  m1=hist[(i - 1) % L] if k >= 2 else None, m2=hist[(i - 2) % L] if k >= 3 else None,
-                                  m_out=hist[i % L] if L and i < N - 1 else None)
-        if masked:
-            x = self._blend(x, cond, 0.0, N)
-        return x
+        D, Dg = evaluate(x, t_dev[i], guided[i])    # with a restoration m_i is the projected (and mixed) evaluation
+        return ops.dpm_multistep(x, D, a, c0, c1, c2, Dg=Dg, w_dev=None if Dg is None else w_dev,
+                                 m1=hist[(i - 1) % L] if k >= 2 else None, m2=hist[(i - 2) % L] if k >= 3 else None,
+                                 m_out=hist[i % L] if L and i < self.num_steps - 1 else None)
