@@ -191,7 +191,7 @@ static int pick_lpp(int C) {
 
 extern "C" int edm_pixelnorm_silu_fwd(const void* x, void* xn, void* a, float* dsave, long P, int C,
                                       hipStream_t st) {
-  EDM_REQUIRE(P > 0 && C > 0 && C % 8 == 0 && C <= 1024, "pixelnorm_silu_fwd: bad P=%ld C=%d", P, C);
+  EDM_REQUIRE(P > 0 && P < (1L << 31) && C > 0 && C % 8 == 0 && C <= 1024, "pixelnorm_silu_fwd: bad P=%ld C=%d", P, C);
   int lpp = pick_lpp(C);
   int gpw = 64 / lpp;
   int grid = grid_for(P, 4 * gpw);
@@ -236,7 +236,7 @@ extern "C" int edm_pool_pixelnorm_silu_bwd(const void* xn, const float* dsave, c
 
 extern "C" int edm_pixelnorm_silu_bwd(const void* xn, const float* dsave, const void* gxn, float gxn_scale,
                                       const void* ga, const void* gadd, void* gx, long P, int C, hipStream_t st) {
-  EDM_REQUIRE(P > 0 && C > 0 && C % 8 == 0 && C <= 1024, "pixelnorm_silu_bwd: bad P=%ld C=%d", P, C);
+  EDM_REQUIRE(P > 0 && P < (1L << 31) && C > 0 && C % 8 == 0 && C <= 1024, "pixelnorm_silu_bwd: bad P=%ld C=%d", P, C);
   int lpp = pick_lpp(C);
   int gpw = 64 / lpp;
   int grid = grid_for(P, 4 * gpw);
