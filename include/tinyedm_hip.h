@@ -60,6 +60,12 @@ int edm_conv_igemm_v6(const void* X, const void* Wp, void* Y, const void* R, flo
  * -3 for shapes it does not cover */
 int edm_conv_igemm_s(const void* X, const void* Wp, void* Y, const void* R, float alpha, float beta, int B, int H,
                      int W, int Cin, int Cout, int taps, edm_stream_t stream);
+/* Which of the four kernels above runs a convolution of this shape: host logic only (no device call, no edm_init needed),
+ * the plan the fused entry points below launch from and the Python side asks for.  Returns the kernel id of
+ * edm_conv_igemm_o in the low byte (1 edm_conv_igemm, 2 _v2, 5 _s, 6 _v6) and, for kernel 6, the channel width of its
+ * tiles (128 or 64) in the next byte.  force: 0 = chosen per shape; 1 / 2 / 5 / 6 = that generation where it covers the
+ * shape, kernel 1 where it does not (EDM_IGEMM of the Python side; the fused entry points always plan with 0). */
+int edm_conv_plan(int B, int H, int W, int Cin, int Cout, int taps, int force);
 /* Same operation with an OUTPUT DESCRIPTOR -- how torch.cat((input, skip * gate)) (networks.py:311) and its backward stop
  * being copies: Y rows have stride ldY elements (0 = Cout: Y may be the left column block of the next block's
  * concatenated operand); Ysilu (optional) receives mp_silu(Y) at the same offsets of a second buffer with the same stride

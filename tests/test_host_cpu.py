@@ -427,3 +427,64 @@ def test_linear_plan_puts_the_named_shapes_on_their_branches():
     from tinyedm_amd import _lib
     with pytest.raises(_lib.HipKernelError):
         ops.linear_plan("fwd", 0, 1, 1)
+
+
+_PLAN_OF_SUFFIX = {"": 1, "_v2": 2, "_s": 5, "_v6": 6 | 128 << 8, "_v6s": 6 | 64 << 8}     # profile-key suffix -> edm_conv_plan
+
+
+def test_conv_plan_reproduces_the_parent_commits_python_dispatch():
+    """conv_dispatch.hip edm_conv_plan (host logic; the plan the library launches from and ops asks for) against
+    tests/conv_plan_parent.json: what the pure-Python ops._igemm_entry / _v4_suffix / uses_s_kernel of the commit named
+    there decided, for force 0 / 1 / 2 / 5 / 6, on every 3x3 and 1x1 layer shape (forward and dgrad) of the shipped configs
+    at batch 128 / 256 / 512 and on both sides of every threshold.  Every row, no row skipped; and ops, which now asks the
+    plan, still names the same entry point, profile key and fragment-major layers."""
+    import json
+    from tinyedm_amd import _lib, ops
+    table = json.load(open(os.path.join(ROOT, "tests", "conv_plan_parent.json")))
+    assert re.fullmatch(r"[0-9a-f]{40}", table["parent"]) and 400 <= len(table["rows"]) <= 2000
+    plan = _lib.lib().edm_conv_plan
+    old, checked = ops.IGEMM_VERSION, 0
+    try:
+        for B, H, W, Cin, Cout, taps, uses_s, *suffixes in table["rows"]:
+            npix = B * H * W
+            for force, suffix in zip((0, 1, 2, 5, 6), suffixes):
+                want = _PLAN_OF_SUFFIX[suffix]
+                got = plan(B, H, W, Cin, Cout, taps, force)
+                assert got == want, (B, H, W, Cin, Cout, taps, force, got, want)
+                ops.IGEMM_VERSION = force
+                p = ops._conv_plan(B, H, W, Cin, Cout, taps, force)
+                assert ops._KERNEL_ID[ops._igemm_entry(npix, W, Cout, taps, Cin)] == want & 0xff
+                assert ops._conv_key(p, taps) == ("conv3x3_igemm" if taps == 9 else "conv1x1_igemm") + suffix
+                if taps == 9:
+                    assert ops.uses_s_kernel(B, H, W, Cin, Cout) == bool(uses_s and force == 0)
+                checked += 1
+    finally:
+        ops.IGEMM_VERSION = old
+    assert checked == 5 * len(table["rows"])
+
+
+def test_conv_plan_puts_the_named_shapes_on_their_branches():
+    from tinyedm_amd import _lib
+    plan = _lib.lib().edm_conv_plan
+    v6, v6s = 6 | 128 << 8, 6 | 64 << 8
+    assert plan(128, 32, 32, 256, 256, 9, 0) == v6                 # 512 tiles of 512x128
+    assert plan(128, 16, 16, 256, 256, 9, 0) == v6s                # 128 of those, but 256 tiles of 512x64
+    assert plan(128, 8, 8, 256, 256, 9, 0) == 5                    # 64 x 4 tiles of 128x64
+    assert plan(128, 64, 64, 192, 192, 9, 0) == v6s                # fills the chip, but 128-wide tiles would be 1/4 padding
+    assert plan(128, 32, 32, 32, 256, 9, 0) == 1                   # conv_in: Cin = 32
+    assert plan(128, 32, 32, 256, 512, 1, 0) == 2                  # 512 x 4 tiles of 256x128
+    assert plan(2, 8, 8, 64, 64, 9, 0) == 1
+    # forced generations fall back to kernel 1 where they do not cover the shape
+    assert plan(128, 32, 32, 32, 256, 9, 6) == 1 and plan(128, 32, 32, 256, 256, 9, 5) == 1
+    assert plan(2, 8, 8, 256, 64, 9, 5) == 5 and plan(2, 8, 8, 64, 64, 9, 6) == v6s and plan(2, 8, 8, 64, 64, 1, 2) == 2
+
+
+def test_conv_plan_reports_the_width_that_launches_under_EDM_V6_NARROW():
+    """EDM_V6_NARROW=0 (the round-5 width rule) is read once per process, in the one place the width is decided"""
+    import subprocess
+    import sys
+    from tinyedm_amd import _lib
+    code = "import ctypes, sys; print(ctypes.CDLL(sys.argv[1]).edm_conv_plan(128, 64, 64, 192, 192, 9, 0))"
+    env = dict(os.environ, EDM_V6_NARROW="0")
+    out = subprocess.run([sys.executable, "-c", code, _lib.LIB_PATH], env=env, capture_output=True, text=True, check=True).stdout
+    assert int(out) == 6 | 128 << 8

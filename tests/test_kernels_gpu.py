@@ -376,6 +376,34 @@ def test_conv_output_descriptor(ops, B, H, W, Cin, Cout, taps, version):
         ops.IGEMM_VERSION = old
 
 
+@pytest.mark.parametrize("B,H,W,Cin,Cout,taps,kid,width", [
+    (16, 32, 32, 64, 512, 9, 6, 64),       # 128 tiles of 512x128, 256 of 512x64: k_conv3x3_v6, narrow
+    (16, 8, 8, 256, 1024, 9, 5, 0),        # 8 x 16 tiles of 128x64: k_conv3x3_s
+    (2, 8, 8, 64, 64, 9, 1, 0),            # fills nothing: k_conv_igemm
+    (256, 32, 32, 64, 128, 1, 2, 0),       # 1024 tiles of 256x128: k_conv_igemm2
+])
+def test_automatic_conv_plan_is_what_runs(ops, B, H, W, Cin, Cout, taps, kid, width):
+    """the smallest shapes on each branch of the automatic edm_conv_plan: ops names the planned kernel's entry point, and the
+    automatic launch is that kernel's result bit for bit"""
+    from tinyedm_amd import _lib
+    plan = _lib.lib().edm_conv_plan(B, H, W, Cin, Cout, taps, 0)
+    assert (plan & 0xff, plan >> 8) == (kid, width)
+    g = torch.Generator().manual_seed(B + Cin + Cout + taps)
+    x = torch.randn(B, H, W, Cin, generator=g).to(torch.bfloat16).to(DEV)
+    wp = (torch.randn(taps, Cout, Cin, generator=g) / math.sqrt(Cin * taps)).to(torch.bfloat16).to(DEV)
+    old = ops.IGEMM_VERSION
+    try:
+        ops.IGEMM_VERSION = 0
+        assert ops._KERNEL_ID[ops._igemm_entry(B * H * W, W, Cout, taps, Cin)] == kid
+        y_auto = ops.conv_igemm(x, wp, taps)
+        ops.IGEMM_VERSION = kid
+        assert ops._KERNEL_ID[ops._igemm_entry(B * H * W, W, Cout, taps, Cin)] == kid
+        y_forced = ops.conv_igemm(x, wp, taps)
+    finally:
+        ops.IGEMM_VERSION = old
+    assert torch.equal(y_auto, y_forced)
+
+
 @pytest.mark.parametrize("B,H,W,Ci,Cs", [(2, 8, 8, 64, 128), (3, 5, 7, 192, 192), (128, 32, 32, 256, 256)])
 def test_skip_half_kernels_match_the_concat_kernels(ops, B, H, W, Ci, Cs):
     """edm_skip_half_fwd / _bwd (the skip half of the decoder's concatenated operands, the half of d loss / d cat that

@@ -5,21 +5,73 @@
 #include "common.h"
 #include <stdlib.h>
 
-int edm_conv_igemm_v1_ex(const void* X, const void* Wp, void* Y, const void* R, float alpha, float beta, int B, int H,
-                         int W, int Cin, int Cout, int taps, const ModEpilogue& mod, hipStream_t st);
-int edm_conv_igemm_v2_ex(const void* X, const void* Wp, void* Y, const void* R, float alpha, float beta, int B, int H,
-                         int W, int Cin, int Cout, int taps, const ModEpilogue& mod, hipStream_t st);
-int edm_conv_igemm_v6_ex(const void* X, const void* Wp, void* Y, const void* R, float alpha, float beta, int B, int H,
-                         int W, int Cin, int Cout, int taps, const ModEpilogue& mod, hipStream_t st);
-// conv_igemm5.hip: small feature maps (reduction split over the waves of a workgroup)
-bool edm_conv_s_worthwhile(long npix, int W, int Cin, int Cout);
-int edm_conv_igemm_s_ex(const void* X, const void* Wp, void* Y, const void* R, float alpha, float beta, int B, int H,
-                        int W, int Cin, int Cout, int taps, const ModEpilogue& mod, hipStream_t st);
+// the kernels' launch functions (conv_igemm.hip, conv_igemm2.hip, conv_igemm5.hip: small feature maps, conv_igemm6.hip)
+typedef int conv_ex_fn(const void* X, const void* Wp, void* Y, const void* R, float alpha, float beta, int B, int H, int W,
+                       int Cin, int Cout, int taps, const ModEpilogue& mod, hipStream_t st);
+conv_ex_fn edm_conv_igemm_v1_ex, edm_conv_igemm_v2_ex, edm_conv_igemm_s_ex, edm_conv_igemm_v6_ex;
+// what each kernel covers and where it pays off: defined beside the kernel, used by its _ex function and by the plan
+bool edm_conv_v2_covers(int W, int taps);
+bool edm_conv_v2_worthwhile(long npix, int Cout);
+bool edm_conv_s_covers(int W, int Cin, int taps);
+bool edm_conv_s_worthwhile(long npix, int Cout);
+bool edm_conv_v6_covers(int W, int Cin, int taps);
+bool edm_conv_tall_worthwhile(long npix, int Cout);
+bool edm_conv_v6_wide(long npix, int Cout);
 
-// the static-schedule kernel pays off when it can give every CU a tile: >= 512 tiles of 512x128, or >= 256 of 512x64
-bool edm_conv_tall_worthwhile(long npix, int Cout) {
-  const long tm = (npix + 511) / 512;
-  return tm * ((Cout + 127) / 128) >= 512 || tm * ((Cout + 63) / 64) >= 256;
+// Which kernel runs a convolution of this shape (host logic only).  Low byte: the kernel id of edm_conv_igemm_o; next byte,
+// kernel 6 only: the channel width of its tiles (128 or 64).  force: 0 = per shape, from the microbenchmarks
+// (tools/microbench_conv.py; conv_in, Cin = 32, stays on kernel 1: 37 us there, 47 on the retired tall-tile k_conv_igemm3);
+// 1 / 2 / 5 / 6 = that generation (the tests force each) where it covers the shape, else kernel 1.
+extern "C" int edm_conv_plan(int B, int H, int W, int Cin, int Cout, int taps, int force) {
+  const long npix = (long)B * H * W;
+  const int v6 = 6 | ((edm_conv_v6_wide(npix, Cout) ? 128 : 64) << 8);
+  if (force == 1) return 1;
+  if (force == 2) return edm_conv_v2_covers(W, taps) ? 2 : 1;
+  if (force == 5) return edm_conv_s_covers(W, Cin, taps) ? 5 : 1;
+  if (force == 6) return edm_conv_v6_covers(W, Cin, taps) ? v6 : 1;
+  if (taps != 9) return edm_conv_v2_worthwhile(npix, Cout) ? 2 : 1;
+  if (edm_conv_v6_covers(W, Cin, taps) && edm_conv_tall_worthwhile(npix, Cout)) return v6;
+  if (edm_conv_s_covers(W, Cin, taps) && edm_conv_s_worthwhile(npix, Cout)) return 5;
+  return 1;
+}
+
+// Launch the planned kernel.  fall_back: one that answers EDM_ERR_UNSUPPORTED (an epilogue it does not have on this shape)
+// hands the launch to kernel 1, which has every epilogue.
+static int run_conv(int plan, bool fall_back, const void* X, const void* Wp, void* Y, const void* R, float alpha, float beta,
+                    int B, int H, int W, int Cin, int Cout, int taps, const ModEpilogue& mod, hipStream_t st) {
+  int rc;
+  switch (plan & 0xff) {
+    case 1: return edm_conv_igemm_v1_ex(X, Wp, Y, R, alpha, beta, B, H, W, Cin, Cout, taps, mod, st);
+    case 2: rc = edm_conv_igemm_v2_ex(X, Wp, Y, R, alpha, beta, B, H, W, Cin, Cout, taps, mod, st); break;
+    case 5: rc = edm_conv_igemm_s_ex(X, Wp, Y, R, alpha, beta, B, H, W, Cin, Cout, taps, mod, st); break;
+    case 6: rc = edm_conv_igemm_v6_ex(X, Wp, Y, R, alpha, beta, B, H, W, Cin, Cout, taps, mod, st); break;
+    // (only edm_conv_igemm_o hands over an id that did not come from edm_conv_plan: the message names it)
+    default: edm_set_error("conv_igemm_o: unknown kernel id %d", plan & 0xff); return EDM_ERR_ARG;
+  }
+  if (rc != EDM_ERR_UNSUPPORTED || !fall_back) return rc;
+  return edm_conv_igemm_v1_ex(X, Wp, Y, R, alpha, beta, B, H, W, Cin, Cout, taps, mod, st);
+}
+// the fused 3x3 entry points: a fragment-major pack is read by kernel 5 alone, every other launch follows the automatic plan
+static int run_conv3x3(int wfrag, const void* X, const void* Wp, void* Y, float alpha, int B, int H, int W, int Cin, int Cout,
+                       const ModEpilogue& mod, hipStream_t st) {
+  return run_conv(wfrag ? 5 : edm_conv_plan(B, H, W, Cin, Cout, 9, 0), !wfrag, X, Wp, Y, nullptr, alpha, 0.0f, B, H, W, Cin,
+                  Cout, 9, mod, st);
+}
+// operand groups of the fused epilogues (common.h ModEpilogue)
+static void set_modulation(ModEpilogue& mod, const float* lin, long lin_stride, const float* gain) {
+  mod.lin = lin;
+  mod.lin_stride = lin_stride;
+  mod.gain = gain;
+}
+static void set_dropout(ModEpilogue& mod, float pdrop, unsigned long long seed, unsigned sub, unsigned step, const void* dyn,
+                        int marks) {
+  mod.pdrop = pdrop;
+  mod.seed_lo = (uint32_t)seed;
+  mod.seed_hi = (uint32_t)(seed >> 32);
+  mod.sub = sub;
+  mod.step = step;
+  mod.dyn = (const StepParams*)dyn;
+  mod.u_marks = (marks && pdrop > 0.f) ? 1 : 0;
 }
 
 // Y = alpha * conv(X, Wp) + beta * R with an OUTPUT DESCRIPTOR (same operand contract as edm_conv_igemm otherwise):
@@ -27,8 +79,8 @@ bool edm_conv_tall_worthwhile(long npix, int Cout) {
 //   Ysilu  optional: mp_silu(Y) (of the bf16-rounded result) at the same offsets of a second buffer with the same stride;
 //   Yb     optional: output channels >= split go to Yb[pixel * ldYb + channel - split] instead (split % 8 == 0);
 //   wfrag  the pack is fragment-major (edm_weight_prep_multi, bits 8 / 9 of a record's taps field): kernel 5 only;
-//   kernel which generation runs: 1 = k_conv_igemm, 2 = k_conv_igemm2, 5 = k_conv3x3_s, 6 = k_conv3x3_v6 (the caller picks
-//          per shape exactly as for the plain entry points; -3 = shape not covered by that generation).
+//   kernel which generation runs: 1 = k_conv_igemm, 2 = k_conv_igemm2, 5 = k_conv3x3_s, 6 = k_conv3x3_v6 (the caller asks
+//          edm_conv_plan, as for the plain entry points; -3 = shape not covered by that generation).
 // Used by the decoder blocks: the producer of a block's `input` writes it (and mp_silu of it) into the left half of the
 // next block's concatenated operands, and the 1x1 dgrad that produces d loss / d cat writes its two halves to the
 // gradient of `input` and to the raw gradient of the gated skip (reference: networks.py:306-316 and its autograd).
@@ -52,13 +104,7 @@ extern "C" int edm_conv_igemm_o(const void* X, const void* Wp, void* Y, long ldY
   mod.split = split;
   mod.wfrag = wfrag;
   EDM_REQUIRE(!wfrag || kernel == 5, "conv_igemm_o: a fragment-major pack (wfrag) is read by kernel 5 (k_conv3x3_s) only");
-  switch (kernel) {
-    case 1: return edm_conv_igemm_v1_ex(X, Wp, Y, R, alpha, beta, B, H, W, Cin, Cout, taps, mod, st);
-    case 2: return edm_conv_igemm_v2_ex(X, Wp, Y, R, alpha, beta, B, H, W, Cin, Cout, taps, mod, st);
-    case 5: return edm_conv_igemm_s_ex(X, Wp, Y, R, alpha, beta, B, H, W, Cin, Cout, taps, mod, st);
-    case 6: return edm_conv_igemm_v6_ex(X, Wp, Y, R, alpha, beta, B, H, W, Cin, Cout, taps, mod, st);
-    default: edm_set_error("conv_igemm_o: unknown kernel id %d", kernel); return EDM_ERR_ARG;
-  }
+  return run_conv(kernel, false, X, Wp, Y, R, alpha, beta, B, H, W, Cin, Cout, taps, mod, st);
 }
 
 // Folded skip projection (round 6; k_conv3x3_v6<..., FOLD>, common.h ModEpilogue::X2):
@@ -72,8 +118,8 @@ extern "C" int edm_conv_igemm_o(const void* X, const void* Wp, void* Y, long ldY
 // EDM_ERR_UNSUPPORTED (-3) otherwise and the caller keeps the two launches.
 extern "C" int edm_conv3x3_fold_supported(int B, int H, int W, int Cin, int Cout, int C2) {
   const long npix = (long)B * H * W;
-  return B > 0 && H > 0 && W > 0 && npix < (1L << 31) && Cin > 0 && Cin % 64 == 0 && Cin * 2 + 64 <= 4096 && Cout > 0 &&
-         Cout % 8 == 0 && C2 > 0 && C2 % 64 == 0 && 512 + 2 * (W + 1) <= 5 * 128 - 49 && edm_conv_tall_worthwhile(npix, Cout);
+  return B > 0 && H > 0 && W > 0 && npix < (1L << 31) && edm_conv_v6_covers(W, Cin, 9) && Cout > 0 && Cout % 8 == 0 &&
+         C2 > 0 && C2 % 64 == 0 && 512 + 2 * (W + 1) <= 5 * 128 - 49 && edm_conv_tall_worthwhile(npix, Cout);
 }
 extern "C" int edm_conv3x3_fold(const void* X, const void* Wp, const void* X2, long ldX2, const void* W2p, int C2, void* Y,
                                 long ldY, void* Ysilu, float alpha3, float alpha1, int B, int H, int W, int Cin, int Cout,
@@ -142,15 +188,13 @@ static int split_conv_impl(const void* Xp, const void* Wp3, float* Y, void* Ypai
   mod.Yb = (bf16*)Ysilu_pairs;
   mod.ldY = ld_pairs;
   mod.ldYb = lo_off;
-  mod.lin = lin;
-  mod.gain = gain;
-  mod.lin_stride = lin_stride;
+  set_modulation(mod, lin, lin_stride, gain);
   mod.HW = H * W;
   mod.ldX = 2 * C;
   mod.kwrap = C / 32;
   const int K = 3 * C;
   const long npix = (long)B * H * W;
-  if (taps == 9 && C % 64 == 0 && W <= 64 && edm_conv_tall_worthwhile(npix, Cout)) {
+  if (edm_conv_v6_covers(W, K, taps) && edm_conv_tall_worthwhile(npix, Cout)) {
     ModEpilogue m6 = mod;
     m6.wfrag = split_epi_unstaged();     // (A/B switch of the staged fp32 epilogue; not a weight-pack matter here)
     const int rc = edm_conv_igemm_v6_ex(Xp, Wp3, Y, R, alpha, beta, B, H, W, K, Cout, 9, m6, st);
@@ -166,7 +210,7 @@ static int split_conv_impl(const void* Xp, const void* Wp3, float* Y, void* Ypai
   const char* const e_fast = getenv("EDM_SPLIT_FAST");
   const char* const e_v2 = getenv("EDM_SPLIT_V2");
   const bool fast = !(e_fast && e_fast[0] == '0'), v2 = e_v2 && e_v2[0] == '1';
-  if (fast && taps == 9 && edm_conv_s_worthwhile(npix, W, K, Cout)) {
+  if (fast && edm_conv_s_covers(W, K, taps) && edm_conv_s_worthwhile(npix, Cout)) {
     const int rc = edm_conv_igemm_s_ex(Xp, Wp3, Y, R, alpha, beta, B, H, W, K, Cout, 9, mod, st);
     if (rc != EDM_ERR_UNSUPPORTED) return rc;
   }
@@ -213,8 +257,7 @@ extern "C" int edm_split_conv_fold(const void* Xp, const void* Wp3, const void* 
 //   a2 = dropout(mp_silu(u * (lin[b,:]*gain + 1)))     -> Y2 (bf16)   [same values as edm_mod_silu_drop_fwd on u]
 // mark_dropped != 0: the elements of Y the dropout removed are written as NaN (bf16 | 0x7FFF) instead of u -- their value is
 // never needed again, and edm_conv3x3_modbwd(u_marked = 1) / edm_mod_silu_drop_bwd then read the mask from U.
-// Picks the static-schedule kernel (k_conv3x3_v6) for layers that give every CU a tall tile, the split-K small-map kernel
-// (k_conv3x3_s) for 8x8-class layers and the 128x128-tile kernel otherwise.
+// Runs on the kernel edm_conv_plan names for the shape (wfrag: on k_conv3x3_s).
 extern "C" int edm_conv3x3_mod(const void* X, const void* Wp, void* Y, void* Y2, const float* lin, long lin_stride,
                                const float* gain, float pdrop, unsigned long long seed, unsigned sub, unsigned step,
                                int mark_dropped, int B, int H, int W, int Cin, int Cout, const void* dyn, int wfrag,
@@ -222,20 +265,13 @@ extern "C" int edm_conv3x3_mod(const void* X, const void* Wp, void* Y, void* Y2,
   EDM_REQUIRE(X && Wp && Y2 && lin && gain, "conv3x3_mod: null pointer");
   EDM_REQUIRE(B > 0 && H > 0 && W > 0 && Cout > 0 && Cout % 8 == 0 && lin_stride >= Cout && pdrop >= 0.f && pdrop < 1.f,
               "conv3x3_mod: bad args");
-  ModEpilogue mod{lin, gain, (bf16*)Y2, lin_stride, H * W, pdrop, (uint32_t)seed, (uint32_t)(seed >> 32), sub, step,
-                  nullptr, nullptr, nullptr, 0.f, 0, (const StepParams*)dyn, 0, (mark_dropped && pdrop > 0.f) ? 1 : 0};
+  ModEpilogue mod{};
+  mod.Y2 = (bf16*)Y2;
+  mod.HW = H * W;
+  set_modulation(mod, lin, lin_stride, gain);
+  set_dropout(mod, pdrop, seed, sub, step, dyn, mark_dropped);
   mod.wfrag = wfrag;
-  if (wfrag)      // fragment-major pack: the caller has established that this shape runs on k_conv3x3_s
-    return edm_conv_igemm_s_ex(X, Wp, Y, nullptr, 1.0f, 0.0f, B, H, W, Cin, Cout, 9, mod, st);
-  if (edm_conv_tall_worthwhile((long)B * H * W, Cout)) {
-    const int rc = edm_conv_igemm_v6_ex(X, Wp, Y, nullptr, 1.0f, 0.0f, B, H, W, Cin, Cout, 9, mod, st);
-    if (rc != EDM_ERR_UNSUPPORTED) return rc;
-  }
-  if (edm_conv_s_worthwhile((long)B * H * W, W, Cin, Cout)) {
-    const int rc = edm_conv_igemm_s_ex(X, Wp, Y, nullptr, 1.0f, 0.0f, B, H, W, Cin, Cout, 9, mod, st);
-    if (rc != EDM_ERR_UNSUPPORTED) return rc;
-  }
-  return edm_conv_igemm_v1_ex(X, Wp, Y, nullptr, 1.0f, 0.0f, B, H, W, Cin, Cout, 9, mod, st);
+  return run_conv3x3(wfrag, X, Wp, Y, 1.0f, B, H, W, Cin, Cout, mod, st);
 }
 
 // Backward counterpart: the dgrad of a block's second 3x3 conv with the modulation backward fused into its epilogue
@@ -257,19 +293,17 @@ extern "C" int edm_conv3x3_modbwd(const void* dY, const void* Wd, float alpha, c
                   (gm_stride == 0 || gm_stride >= Cout),
               "conv3x3_modbwd: bad args");
   if ((H * W) % 32 != 0) return EDM_ERR_UNSUPPORTED;
-  ModEpilogue mod{lin, gain, (bf16*)GR, lin_stride, H * W, pdrop, (uint32_t)seed, (uint32_t)(seed >> 32), sub, step,
-                  (const bf16*)U, gm, nullptr, 0.f, 1, (const StepParams*)dyn, gm_stride, (u_marked && pdrop > 0.f) ? 1 : 0};
+  ModEpilogue mod{};
+  mod.mode = 1;
+  mod.Y2 = (bf16*)GR;
+  mod.HW = H * W;
+  mod.U = (const bf16*)U;
+  mod.gm = gm;
+  mod.gm_stride = gm_stride;
+  set_modulation(mod, lin, lin_stride, gain);
+  set_dropout(mod, pdrop, seed, sub, step, dyn, u_marked);
   mod.wfrag = wfrag;
-  if (wfrag) return edm_conv_igemm_s_ex(dY, Wd, nullptr, nullptr, alpha, 0.0f, B, H, W, Cin, Cout, 9, mod, st);
-  if (edm_conv_tall_worthwhile((long)B * H * W, Cout)) {
-    const int rc = edm_conv_igemm_v6_ex(dY, Wd, nullptr, nullptr, alpha, 0.0f, B, H, W, Cin, Cout, 9, mod, st);
-    if (rc != EDM_ERR_UNSUPPORTED) return rc;
-  }
-  if (edm_conv_s_worthwhile((long)B * H * W, W, Cin, Cout)) {
-    const int rc = edm_conv_igemm_s_ex(dY, Wd, nullptr, nullptr, alpha, 0.0f, B, H, W, Cin, Cout, 9, mod, st);
-    if (rc != EDM_ERR_UNSUPPORTED) return rc;
-  }
-  return edm_conv_igemm_v1_ex(dY, Wd, nullptr, nullptr, alpha, 0.0f, B, H, W, Cin, Cout, 9, mod, st);
+  return run_conv3x3(wfrag, dY, Wd, nullptr, alpha, B, H, W, Cin, Cout, mod, st);
 }
 
 // dgrad of a block's FIRST 3x3 conv with the mp_silu backward of the block input fused into its epilogue
@@ -280,17 +314,13 @@ extern "C" int edm_conv3x3_silubwd(const void* dY, const void* Wd, const void* X
                                    void* GX, int B, int H, int W, int Cin, int Cout, int wfrag, hipStream_t st) {
   EDM_REQUIRE(dY && Wd && Xpre && GX, "conv3x3_silubwd: null pointer");
   EDM_REQUIRE(B > 0 && H > 0 && W > 0 && Cout > 0 && Cout % 8 == 0, "conv3x3_silubwd: bad args");
-  ModEpilogue mod{nullptr, nullptr, (bf16*)GX, 0, H * W, 0.f, 0u, 0u, 0u, 0u, (const bf16*)Xpre, nullptr, (const bf16*)ADD,
-                  add_scale, 2, nullptr};
+  ModEpilogue mod{};
+  mod.mode = 2;
+  mod.Y2 = (bf16*)GX;
+  mod.HW = H * W;
+  mod.U = (const bf16*)Xpre;
+  mod.ADD = (const bf16*)ADD;
+  mod.add_scale = add_scale;
   mod.wfrag = wfrag;
-  if (wfrag) return edm_conv_igemm_s_ex(dY, Wd, nullptr, nullptr, 1.0f, 0.0f, B, H, W, Cin, Cout, 9, mod, st);
-  if (edm_conv_tall_worthwhile((long)B * H * W, Cout)) {
-    const int rc = edm_conv_igemm_v6_ex(dY, Wd, nullptr, nullptr, 1.0f, 0.0f, B, H, W, Cin, Cout, 9, mod, st);
-    if (rc != EDM_ERR_UNSUPPORTED) return rc;
-  }
-  if (edm_conv_s_worthwhile((long)B * H * W, W, Cin, Cout)) {
-    const int rc = edm_conv_igemm_s_ex(dY, Wd, nullptr, nullptr, 1.0f, 0.0f, B, H, W, Cin, Cout, 9, mod, st);
-    if (rc != EDM_ERR_UNSUPPORTED) return rc;
-  }
-  return edm_conv_igemm_v1_ex(dY, Wd, nullptr, nullptr, 1.0f, 0.0f, B, H, W, Cin, Cout, 9, mod, st);
+  return run_conv3x3(wfrag, dY, Wd, nullptr, 1.0f, B, H, W, Cin, Cout, mod, st);
 }

@@ -304,6 +304,11 @@ extern "C" int edm_conv_igemm_v2_ablate(const void* X, const void* Wp, void* Y, 
   return EDM_OK;
 }
 
+// Shapes this kernel covers, and the 1x1 layers it pays off on: those that give every CU four of its 256x128 tiles
+// (edm_conv_plan, conv_dispatch.hip; a 3x3 layer only runs here when the generation is forced).
+bool edm_conv_v2_covers(int W, int taps) { return taps == 1 || W <= 64; }
+bool edm_conv_v2_worthwhile(long npix, int Cout) { return ((npix + BM - 1) / BM) * ((Cout + BN - 1) / BN) >= 1024; }
+
 // Same contract as edm_conv_igemm (conv_igemm.hip); returns EDM_ERR_UNSUPPORTED for shapes it does not cover so the
 // dispatcher can fall back to generation 1.
 int edm_conv_igemm_v2_ex(const void* X, const void* Wp, void* Y, const void* R, float alpha, float beta, int B, int H,
@@ -315,7 +320,7 @@ int edm_conv_igemm_v2_ex(const void* X, const void* Wp, void* Y, const void* R, 
   EDM_REQUIRE(B > 0 && H > 0 && W > 0 && (long)B * H * W < (1L << 31), "conv_igemm_v2: bad B/H/W");
   EDM_REQUIRE(taps == 1 || taps == 9, "conv_igemm_v2: taps must be 1 or 9");
   EDM_REQUIRE(Cin > 0 && Cin % 32 == 0 && Cout > 0 && Cout % 8 == 0, "conv_igemm_v2: Cin %% 32, Cout %% 8 required");
-  if (taps == 9 && W > 64) return EDM_ERR_UNSUPPORTED;
+  if (!edm_conv_v2_covers(W, taps)) return EDM_ERR_UNSUPPORTED;
   EDM_ZERO_PAGE(zero_page_, "conv_igemm_v2");
   (void)zero_page_;
   const int Npix = B * H * W;

@@ -390,19 +390,24 @@ void launch5(const void* X, const void* Wp, void* Y, const void* R, float alpha,
 
 }  // namespace
 
+// Shapes this kernel covers (3x3 only; a row of Cin channels must fit the zero page): edm_conv_igemm_s_ex returns
+// EDM_ERR_UNSUPPORTED (-3) otherwise, and edm_conv_plan (conv_dispatch.hip) does not plan it.
+bool edm_conv_s_covers(int W, int Cin, int taps) {
+  return taps == 9 && Cin > 0 && Cin % 256 == 0 && W <= 16 && Cin * 2 + 64 <= 4096;
+}
 // small feature maps whose pixel count cannot give every CU one of the larger tiles
-bool edm_conv_s_worthwhile(long npix, int W, int Cin, int Cout) {
+bool edm_conv_s_worthwhile(long npix, int Cout) {
   const long tiles = ((npix + BM - 1) / BM) * ((Cout + BNW - 1) / BNW);
-  return W <= 16 && Cin % 256 == 0 && tiles >= 128 && tiles <= 1024;
+  return tiles >= 128 && tiles <= 1024;
 }
 
-// 3x3 only; same contract as edm_conv_igemm; EDM_ERR_UNSUPPORTED (-3) for shapes it does not cover.
+// same contract as edm_conv_igemm; EDM_ERR_UNSUPPORTED (-3) for shapes, and epilogues on them, that it does not cover.
 int edm_conv_igemm_s_ex(const void* X, const void* Wp, void* Y, const void* R, float alpha, float beta, int B, int H,
                         int W, int Cin, int Cout, int taps, const ModEpilogue& mod, hipStream_t st) {
   EDM_REQUIRE(X && Wp && (Y || mod.Y2), "conv_igemm_s: null pointer");
   EDM_REQUIRE(B > 0 && H > 0 && W > 0 && (long)B * H * W < (1L << 31), "conv_igemm_s: bad B/H/W");
   EDM_REQUIRE(Cout > 0 && Cout % 8 == 0, "conv_igemm_s: Cout %% 8 required");
-  if (taps != 9 || Cin <= 0 || Cin % 256 != 0 || W > 16 || Cin * 2 + 64 > 4096) return EDM_ERR_UNSUPPORTED;
+  if (!edm_conv_s_covers(W, Cin, taps)) return EDM_ERR_UNSUPPORTED;
   if (mod.mode == 1 && (H * W) % 32 != 0) return EDM_ERR_UNSUPPORTED;
   // split-bf16 form: the hi / lo halves of X must be whole rounds of 4 chunks (C % 128 == 0)
   if (mod.mode == 4 && (mod.wfrag || mod.kwrap % 4 != 0)) return EDM_ERR_UNSUPPORTED;

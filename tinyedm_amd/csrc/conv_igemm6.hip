@@ -622,28 +622,38 @@ void launch6(const void* X, const void* Wp, void* Y, const void* R, float alpha,
 
 // Shapes this kernel covers: those of edm_conv_igemm_v4_ex with 49 spare zero rows in the slab buffer (any W <= 64: the
 // static border forms need W = 32 / 64 with images aligned to the tiles, or 16x16 images; everything else takes the
-// per-lane validity bits).  Returns EDM_ERR_UNSUPPORTED (-3) otherwise.
+// per-lane validity bits; a row of Cin channels must fit the zero page).  edm_conv_igemm_v6_ex returns
+// EDM_ERR_UNSUPPORTED (-3) otherwise, and edm_conv_plan (conv_dispatch.hip) does not plan it.
+bool edm_conv_v6_covers(int W, int Cin, int taps) {
+  static_assert(BM + 2 * (64 + 1) <= 6 * 128 - 49, "W <= 64 fits the 6-slot slab");
+  return taps == 9 && Cin > 0 && Cin % 64 == 0 && Cin * 2 + 64 <= ZERO_PAGE && W <= 64;
+}
+static bool fills_chip_128(long npix, int Cout) { return ((npix + BM - 1) / BM) * ((Cout + 127) / 128) >= 512; }
+// the static-schedule kernel pays off when it can give every CU a tile: >= 512 tiles of 512x128, or >= 256 of 512x64
+bool edm_conv_tall_worthwhile(long npix, int Cout) {
+  return fills_chip_128(npix, Cout) || ((npix + BM - 1) / BM) * ((Cout + 63) / 64) >= 256;
+}
+// 128-channel tiles when they fill the chip -- unless they would mostly multiply padding: Cout = 192 (the 64x64 layers of
+// the default ImageNet Denoiser) is 1.5 tiles of 128 but 3 of 64, and the 64-channel form's lower matrix-pipe occupancy
+// (69 % against 80 %, profiles/r05_v6_timeline_16x16.txt) costs less than a quarter of the MFMAs spent on zeros (round 6;
+// EDM_V6_NARROW=0: the round-5 rule)
+bool edm_conv_v6_wide(long npix, int Cout) {
+  static const bool narrow_ok = !(getenv("EDM_V6_NARROW") && getenv("EDM_V6_NARROW")[0] == '0');
+  const int pad4 = (Cout + 127) / 128 * 128, pad2 = (Cout + 63) / 64 * 64;
+  return fills_chip_128(npix, Cout) && !(narrow_ok && pad2 * 80 < pad4 * 69);
+}
 int edm_conv_igemm_v6_ex(const void* X, const void* Wp, void* Y, const void* R, float alpha, float beta, int B, int H,
                          int W, int Cin, int Cout, int taps, const ModEpilogue& mod, hipStream_t st) {
   EDM_REQUIRE(X && Wp && (Y || mod.Y2), "conv_igemm_v6: null pointer");
   EDM_REQUIRE(!mod.wfrag || mod.mode == 4, "conv_igemm_v6: fragment-major weight packs are read by k_conv3x3_s only");
   EDM_REQUIRE(B > 0 && H > 0 && W > 0 && (long)B * H * W < (1L << 31), "conv_igemm_v6: bad B/H/W");
   EDM_REQUIRE(Cout > 0 && Cout % 8 == 0, "conv_igemm_v6: Cout %% 8 required");
-  if (taps != 9 || Cin <= 0 || Cin % 64 != 0 || Cin * 2 + 64 > ZERO_PAGE || W > 64) return EDM_ERR_UNSUPPORTED;
+  if (!edm_conv_v6_covers(W, Cin, taps)) return EDM_ERR_UNSUPPORTED;
   EDM_ZERO_PAGE(zero_page_, "conv_igemm_v6");
   (void)zero_page_;
   const int Npix = B * H * W;
-  const int xrows = BM + 2 * (W + 1);
-  const bool nx5 = xrows <= 5 * 128 - 49;
-  if (!nx5 && xrows > 6 * 128 - 49) return EDM_ERR_UNSUPPORTED;
-  const long tiles4 = (long)((Npix + BM - 1) / BM) * ((Cout + 127) / 128);
-  // 128-channel tiles when they fill the chip -- unless they would mostly multiply padding: Cout = 192 (the 64x64 layers of
-  // the default ImageNet Denoiser) is 1.5 tiles of 128 but 3 of 64, and the 64-channel form's lower matrix-pipe occupancy
-  // (69 % against 80 %, profiles/r05_v6_timeline_16x16.txt) costs less than a quarter of the MFMAs spent on zeros (round 6;
-  // EDM_V6_NARROW=0: the round-5 rule)
-  static const bool narrow_ok = !(getenv("EDM_V6_NARROW") && getenv("EDM_V6_NARROW")[0] == '0');
-  const int pad4 = (Cout + 127) / 128 * 128, pad2 = (Cout + 63) / 64 * 64;
-  const bool wide = tiles4 >= 512 && !(narrow_ok && pad2 * 80 < pad4 * 69);
+  const bool nx5 = BM + 2 * (W + 1) <= 5 * 128 - 49;
+  const bool wide = edm_conv_v6_wide(Npix, Cout);
   // images aligned to the 512-pixel tiles (W = 32 / 64), or 16x16 images (two per tile): border handling without
   // per-fragment instructions
   const int wb = ((H * W) % BM == 0 && (W == 32 || W == 64)) ? W / 16 : (H == 16 && W == 16) ? 1 : 0;

@@ -6,6 +6,7 @@ Layout conventions: activations are NHWC bf16 tensors of shape (B, H, W, C) (con
 """
 import contextlib
 import ctypes
+import functools
 import math
 import os
 import types
@@ -846,68 +847,48 @@ def nhwc_bf16_to_nchw(x):
 IGEMM_VERSION = int(os.environ.get("EDM_IGEMM", "0"))
 
 
-def _igemm_entry(npix, W, Cout, taps, Cin=0):
-    if taps == 9 and W > 64:
-        return "edm_conv_igemm"
-    if IGEMM_VERSION == 1:
-        return "edm_conv_igemm"
-    if IGEMM_VERSION == 2:
-        return "edm_conv_igemm_v2"
-    if IGEMM_VERSION == 6:
-        ok = taps == 9 and Cin % 64 == 0 and Cin <= 2016 and W <= 64
-        return "edm_conv_igemm_v6" if ok else "edm_conv_igemm"
-    if IGEMM_VERSION == 5:
-        return "edm_conv_igemm_s" if (taps == 9 and Cin % 256 == 0 and Cin <= 2016 and W <= 16) else "edm_conv_igemm"
-    # per-shape choice from the microbenchmarks (tools/microbench_conv.py): the LDS-DMA tall-tile kernels only pay
-    # off when they still give every CU >= 2 tiles; small feature maps keep the 128x128 register-staged kernel.
-    if taps == 9:
-        tm = (npix + 511) // 512
-        tiles3 = tm * ((Cout + 127) // 128)
-        v6_ok = Cin % 64 == 0 and Cin <= 2016 and W <= 64
-        if tiles3 >= 512:
-            return "edm_conv_igemm_v6" if v6_ok else "edm_conv_igemm"    # (conv_in, Cin = 32: 37 us there; the tall-tile
-                                                                             #  k_conv_igemm3 it used to take needed 47 and was retired)
-        if v6_ok and tm * ((Cout + 63) // 64) >= 256:     # 512x64 tiles of the same kernel (16x16 layers at batch 128)
-            return "edm_conv_igemm_v6"
-        ts = ((npix + 127) // 128) * ((Cout + 63) // 64)
-        if W <= 16 and Cin % 256 == 0 and Cin <= 2016 and 128 <= ts <= 1024:   # small maps: K split over the waves
-            return "edm_conv_igemm_s"
-        return "edm_conv_igemm"
-    tiles2 = ((npix + 255) // 256) * ((Cout + 127) // 128)
-    return "edm_conv_igemm_v2" if tiles2 >= 1024 else "edm_conv_igemm"
+# kernel ids of edm_conv_igemm_o / edm_conv_plan (include/tinyedm_hip.h)
+_KERNEL_ID = {"edm_conv_igemm": 1, "edm_conv_igemm_v2": 2, "edm_conv_igemm_s": 5, "edm_conv_igemm_v6": 6}
+_ENTRY = {kid: entry for entry, kid in _KERNEL_ID.items()}
 
 
-def uses_s_kernel(npix, W, Cin, Cout):
+@functools.lru_cache(maxsize=None)
+def _conv_plan(B, H, W, Cin, Cout, taps, force):
+    """edm_conv_plan: the kernel the library runs this shape on (id in the low byte, tile width of kernel 6 in the next).
+    Asked once per shape and generation, and not through _lib.call: a host query is no launch (_lib.N_CALLS)."""
+    return _lib.lib().edm_conv_plan(B, H, W, Cin, Cout, taps, force)
+
+
+def _igemm_entry(npix, W, Cout, taps, Cin):
+    """entry point of the kernel that runs npix = B * H * W pixels in rows of W (tests and tools ask by pixel count: the
+    plan is asked for one image of npix // W rows; the launching functions below pass their real B and H)"""
+    return _ENTRY[_conv_plan(1, npix // W, W, Cin, Cout, taps, IGEMM_VERSION) & 0xff]
+
+
+def uses_s_kernel(B, H, W, Cin, Cout):
     """the default dispatch runs a 3x3 conv of this shape on k_conv3x3_s (the 8x8 layers' kernel) AND that kernel can take
     a fragment-major weight pack for it (networks._PrepPlan writes one for such layers)"""
     return (IGEMM_VERSION == 0 and Cout % 64 == 0 and Cin % 32 == 0
-            and _igemm_entry(npix, W, Cout, 9, Cin) == "edm_conv_igemm_s")
+            and _conv_plan(B, H, W, Cin, Cout, 9, 0) & 0xff == 5)
 
 
-def _wfrag(wp, entry, who):
+def _wfrag(wp, plan, who):
     """1 when wp is a fragment-major pack (tagged by the plan that wrote it); such a pack is only valid on k_conv3x3_s"""
     if not getattr(wp, "_edm_frag", False):
         return 0
-    if entry != "edm_conv_igemm_s":
-        raise ValueError(f"{who}: a fragment-major weight pack reached a shape that does not run on k_conv3x3_s ({entry})")
+    if plan & 0xff != 5:
+        raise ValueError(f"{who}: a fragment-major weight pack reached a shape that does not run on k_conv3x3_s ({_ENTRY[plan & 0xff]})")
     return 1
 
 
 V46 = "_v6"     # profile-key suffix of the static-schedule 3x3 kernel (its 32x32x16 predecessor, "_v4", was retired in round 4)
-# kernel ids of edm_conv_igemm_o (include/tinyedm_hip.h)
-_KERNEL_ID = {"edm_conv_igemm": 1, "edm_conv_igemm_v2": 2, "edm_conv_igemm_s": 5, "edm_conv_igemm_v6": 6}
 
 
-def _v4_suffix(entry, npix, Cout):
-    """profile-key suffix naming the kernel that runs: _v6 = k_conv3x3_v6 with 512x128 tiles, _v6s = the same kernel with
-    512x64 tiles (16x16 layers), _s = k_conv3x3_s (8x8 layers)"""
-    if entry == "edm_conv_igemm_s":
-        return "_s"
-    if entry != "edm_conv_igemm_v6":
-        return entry[len("edm_conv_igemm"):]
-    pad4, pad2 = (Cout + 127) // 128 * 128, (Cout + 63) // 64 * 64     # (conv_igemm6.hip: narrow tiles when 128 would mostly pad)
-    wide = ((npix + 511) // 512) * ((Cout + 127) // 128) >= 512 and not pad2 * 80 < pad4 * 69
-    return V46 if wide else V46 + "s"
+def _conv_key(plan, taps=9, tail=""):
+    """profile key naming the kernel that runs ("conv3x3_igemm_v6", "conv1x1_igemm", ...): _v6 = k_conv3x3_v6 with 512x128
+    tiles, _v6s = the same kernel with 512x64 tiles (16x16 layers), _s = k_conv3x3_s (8x8 layers), _v2 = k_conv_igemm2"""
+    suffix = {1: "", 2: "_v2", 5: "_s", 6: V46 if plan >> 8 == 128 else V46 + "s"}[plan & 0xff]
+    return ("conv3x3_igemm" if taps == 9 else "conv1x1_igemm") + suffix + tail
 
 
 def conv_igemm(x, wp, taps, residual=None, alpha=1.0, beta=0.0, out=None, silu_out=None, split=None):
@@ -926,19 +907,15 @@ def conv_igemm(x, wp, taps, residual=None, alpha=1.0, beta=0.0, out=None, silu_o
     if residual is not None:
         _chk(residual, bf16, "residual", (B, H, W, Cout))
     npix = B * H * W
-    entry = _igemm_entry(npix, W, Cout, taps, Cin)
-    # profile key names the kernel generation that runs ("conv3x3_igemm_v6", "conv1x1_igemm", ...)
-    pname = ("conv3x3_igemm" if taps == 9 else "conv1x1_igemm") + _v4_suffix(entry, npix, Cout)
+    plan = _conv_plan(B, H, W, Cin, Cout, taps, IGEMM_VERSION)
+    pname = _conv_key(plan, taps)
     nbytes = 2.0 * (npix * (Cin + Cout * ((2 if residual is not None else 1) + (1 if silu_out is not None else 0))) + wp.numel())
-    wfrag = _wfrag(wp, entry, "conv_igemm")
+    wfrag = _wfrag(wp, plan, "conv_igemm")
     if out is None and silu_out is None and split is None and not wfrag:
         y = torch.empty(B, H, W, Cout, device=x.device, dtype=bf16)
         with _prof(pname, 2.0 * npix * Cin * Cout * taps, nbytes):
-            _lib.call(entry, _p(x), _p(wp), _p(y), _p(residual), float(alpha), float(beta), B, H, W, Cin, Cout, taps, _stream())
+            _lib.call(_ENTRY[plan & 0xff], _p(x), _p(wp), _p(y), _p(residual), float(alpha), float(beta), B, H, W, Cin, Cout, taps, _stream())
         return y
-    kid = _KERNEL_ID.get(entry)
-    if kid is None:
-        raise ValueError(f"conv_igemm: {entry} has no output-descriptor form (shape B={B} H={H} W={W} Cin={Cin} Cout={Cout})")
     ld, ya, yb, ldb, c = 0, None, None, 0, 0
     if split is not None:
         if out is not None or silu_out is not None:
@@ -958,7 +935,7 @@ def conv_igemm(x, wp, taps, residual=None, alpha=1.0, beta=0.0, out=None, silu_o
         ya = out
     with _prof(pname, 2.0 * npix * Cin * Cout * taps, nbytes):
         _lib.call("edm_conv_igemm_o", _p(x), _p(wp), _p(ya), ld, _p(silu_out), _p(yb), ldb, c, _p(residual), float(alpha),
-                  float(beta), B, H, W, Cin, Cout, taps, kid, wfrag, _stream())
+                  float(beta), B, H, W, Cin, Cout, taps, plan & 0xff, wfrag, _stream())
     return (ya, yb) if split is not None else out
 
 
@@ -991,8 +968,7 @@ def conv3x3_fold(x, wp, x2, w2p, alpha3, alpha1, out=None, silu_out=None):
     if silu_out is not None and _row_view(silu_out, B, H, W, Cout, "silu_out") != ld:
         raise ValueError("conv3x3_fold: out and silu_out must have the same row stride")
     npix = B * H * W
-    pname = "conv3x3_igemm" + _v4_suffix("edm_conv_igemm_v6", npix, Cout) + "_fold"
-    with _prof(pname, 2.0 * npix * Cout * (9 * Cin + C2),
+    with _prof(_conv_key(_conv_plan(B, H, W, Cin, Cout, 9, 6), tail="_fold"), 2.0 * npix * Cout * (9 * Cin + C2),
                2.0 * (npix * (Cin + C2 + Cout * (2 if silu_out is not None else 1)) + wp.numel() + w2p.numel())):
         _lib.call("edm_conv3x3_fold", _p(x), _p(wp), _p(x2), C2, _p(w2p), C2, _p(out), ld, _p(silu_out), float(alpha3),
                   float(alpha1), B, H, W, Cin, Cout, _stream())
@@ -1027,11 +1003,10 @@ def conv3x3_mod(x, wp, lin, gain, pdrop, seed, sub, step, want_u=True, dyn=None,
     u = torch.empty(B, H, W, Cout, device=x.device, dtype=bf16) if want_u else None
     a2 = torch.empty(B, H, W, Cout, device=x.device, dtype=bf16)
     npix = B * H * W
-    entry = _igemm_entry(npix, W, Cout, 9, Cin)
-    pname = "conv3x3_igemm" + (_v4_suffix(entry, npix, Cout) if entry in ("edm_conv_igemm_v6", "edm_conv_igemm_s") else "")
-    with _prof(pname, 2.0 * npix * Cin * Cout * 9, 2.0 * (npix * (Cin + Cout * (2 if want_u else 1)) + wp.numel())):
+    plan = _conv_plan(B, H, W, Cin, Cout, 9, 0)      # (the fused entry points launch from the automatic plan)
+    with _prof(_conv_key(plan), 2.0 * npix * Cin * Cout * 9, 2.0 * (npix * (Cin + Cout * (2 if want_u else 1)) + wp.numel())):
         _lib.call("edm_conv3x3_mod", _p(x), _p(wp), _p(u), _p(a2), _p(lin), ls, _p(gain), float(pdrop), int(seed),
-                  int(sub), int(step), int(bool(mark_dropped)), B, H, W, Cin, Cout, _dyn(dyn), _wfrag(wp, entry, "conv3x3_mod"),
+                  int(sub), int(step), int(bool(mark_dropped)), B, H, W, Cin, Cout, _dyn(dyn), _wfrag(wp, plan, "conv3x3_mod"),
                   _stream())
     return u, a2
 
@@ -1066,12 +1041,11 @@ def conv3x3_modbwd(gout, wd, alpha, r1, lin, gain, pdrop, seed, sub, step, glin_
         gs = _lin_view(glin, B, Cout, "glin")
         ggain = zeros_f32((), r1.device) if ggain_out is None else _chk(ggain_out, f32, "ggain_out", ())
     npix = B * H * W
-    entry = _igemm_entry(npix, W, Cout, 9, Cin)
-    pname = "conv3x3_igemm" + (_v4_suffix(entry, npix, Cout) if entry in ("edm_conv_igemm_v6", "edm_conv_igemm_s") else "") + "_modbwd"
-    with _prof(pname, 2.0 * npix * Cin * Cout * 9, 2.0 * (npix * (Cin + 2 * Cout) + wd.numel())):
+    plan = _conv_plan(B, H, W, Cin, Cout, 9, 0)      # (the fused entry points launch from the automatic plan)
+    with _prof(_conv_key(plan, tail="_modbwd"), 2.0 * npix * Cin * Cout * 9, 2.0 * (npix * (Cin + 2 * Cout) + wd.numel())):
         _lib.call("edm_conv3x3_modbwd", _p(gout), _p(wd), float(alpha), _p(r1), _p(lin), ls, _p(gain), _p(gr), _p(gm), gms,
                   float(pdrop), int(seed), int(sub), int(step), int(bool(u_marked)), B, H, W, Cin, Cout, _dyn(dyn),
-                  _wfrag(wd, entry, "conv3x3_modbwd"), _stream())
+                  _wfrag(wd, plan, "conv3x3_modbwd"), _stream())
     if gm_out is not None:
         return gr, None, None
     _lib.call("edm_mod_finish", _p(gm), _p(lin), ls, _p(gain), _p(glin), gs, _p(ggain), B, Cout, _stream())
@@ -1104,12 +1078,11 @@ def conv3x3_silubwd(g, wd, xpre, gextra=None, extra_scale=1.0):
         _chk(gextra, bf16, "gextra", xpre.shape)
     gx = torch.empty_like(xpre)
     npix = B * H * W
-    entry = _igemm_entry(npix, W, Cout, 9, Cin)
-    pname = "conv3x3_igemm" + (_v4_suffix(entry, npix, Cout) if entry in ("edm_conv_igemm_v6", "edm_conv_igemm_s") else "") + "_silubwd"
-    with _prof(pname, 2.0 * npix * Cin * Cout * 9,
+    plan = _conv_plan(B, H, W, Cin, Cout, 9, 0)      # (the fused entry points launch from the automatic plan)
+    with _prof(_conv_key(plan, tail="_silubwd"), 2.0 * npix * Cin * Cout * 9,
                2.0 * (npix * (Cin + Cout * (3 if gextra is not None else 2)) + wd.numel())):
         _lib.call("edm_conv3x3_silubwd", _p(g), _p(wd), _p(xpre), _p(gextra), float(extra_scale), _p(gx), B, H, W, Cin,
-                  Cout, _wfrag(wd, entry, "conv3x3_silubwd"), _stream())
+                  Cout, _wfrag(wd, plan, "conv3x3_silubwd"), _stream())
     return gx
 
 
