@@ -393,6 +393,12 @@ int edm_embed_combine_fwd(const float* emb_sigma, const float* wcls_hat, const l
                           edm_stream_t stream);
 int edm_embed_combine_bwd(const float* gout, const float* pre, const long long* labels, float add_factor, int K,
                           float* gemb_sigma, float* gwcls_hat, int B, int E, const int* drop, edm_stream_t stream);
+/* augment-label conditioning (EDM, Karras et al. 2022, App. F.2 -- no reference call site): emb_sigma [B][E] +=
+ * aug [B][K] . w_hat [E][K]^T in place (k ascending; an all-zero row changes nothing), before edm_embed_combine_fwd; and
+ * gw_hat [E][K] = gemb_sigma^T . aug, summed over b in ascending order (deterministic, no atomics), overwritten. */
+int edm_aug_embed_fwd(float* emb_sigma, const float* aug, const float* w_hat, int B, int E, int K, edm_stream_t stream);
+int edm_aug_embed_wgrad(const float* gemb_sigma, const float* aug, float* gw_hat, int B, int E, int K,
+                        edm_stream_t stream);
 
 /* ---------------------------------------------------------------- step level (edm.py:84-93, 212; metric.py:8-18; edm.py:251; ema.py:137-140; solvers.py:49-57) */
 int edm_diffuse(const float* clean, float* noisy, float* sigma, float P_mean, float P_std, int B, long CHW,
@@ -602,6 +608,17 @@ int edm_f32_nhwc_to_nchw(const float* x, float* y, int B, int C, int HW, edm_str
 int edm_u8_gather_normalize(const void* data, const long* index, float* out, int B, int C, int H, int W, long n_images,
                             float mean, float stdv, int flip, unsigned long long seed, unsigned epoch,
                             edm_stream_t stream);
+/* edm_u8_gather_normalize with the non-leaking augmentation of EDM composed into the gather (Karras et al. 2022,
+ * "Elucidating the Design Space of Diffusion-Based Generative Models", App. F.2 -- the reference has no call site): the
+ * exact, pixel-permuting subset xflip, yflip, whole-pixel translation (border reflected without edge repeat), rot90.
+ * Each op of aug_ops (bit 0 xflip, 1 yflip, 2 translate, 3 rot90) is enabled per sample iff its Philox word < aug_thr
+ * (round(p * 2^32), at most 2^32); `flip` keeps its meaning and is applied first.  aug [B][6] fp32 receives the augment
+ * labels (xflip, yflip, sx / W, sy / H, cos(k pi/2) - 1, sin(k pi/2)); zeros for a disabled op.  rot90 with H != W:
+ * status -3 (unsupported), nothing is launched.  The word -> draw mapping is written down at aug_draw in csrc/data.hip. */
+int edm_u8_gather_augment_normalize(const void* data, const long* index, float* out, int B, int C, int H, int W,
+                                    long n_images, float mean, float stdv, int flip, unsigned long long seed,
+                                    unsigned epoch, unsigned long long aug_thr, int aug_ops, float* aug,
+                                    edm_stream_t stream);
 /* (x*scale + offset).clip(0,255) -> uint8, layout preserved (cifar10datamodule.py:34-35: scale 127.5, offset 128) */
 int edm_denormalize_u8(const float* x, void* out, long n, float scale, float offset, edm_stream_t stream);
 /* clamp(pred*std[c]*2 + mean[c], 0, 1)*255 -> uint8 NHWC (callbacks.py:126-156, PreditionWriter) */

@@ -96,6 +96,8 @@ SIGNATURES = {
     "edm_fourier_fwd": [P, I, P, P, P, I, I, P],
     "edm_embed_combine_fwd": [P, P, P, F, I, P, P, I, I, U64, U64, U, P, P, P, P],
     "edm_embed_combine_bwd": [P, P, P, F, I, P, P, I, I, P, P],
+    "edm_aug_embed_fwd": [P, P, P, I, I, I, P],
+    "edm_aug_embed_wgrad": [P, P, P, I, I, I, P],
     # optim.hip
     "edm_diffuse": [P, P, P, F, F, I, L, U64, U, P, P],
     "edm_diffuse_given": [P, P, P, P, P, F, F, I, L, P],
@@ -150,6 +152,7 @@ SIGNATURES = {
     "edm_f32_nhwc_to_nchw": [P, P, I, I, I, P],
     # data.hip
     "edm_u8_gather_normalize": [P, P, P, I, I, I, I, L, F, F, I, U64, U, P],
+    "edm_u8_gather_augment_normalize": [P, P, P, I, I, I, I, L, F, F, I, U64, U, U64, I, P, P],
     "edm_denormalize_u8": [P, P, L, F, F, P],
     "edm_prediction_to_u8_nhwc": [P, P, I, I, I, I, P, P, P],
 }

@@ -196,6 +196,30 @@ __global__ void k_embed_combine_bwd(const float* __restrict__ gout, const float*
   ges[i] = g;
 }
 
+// Augment-label conditioning (EDM, Karras et al. 2022, App. F.2): es[b][e] += sum_k a[b][k] * w[e][k], in place on the
+// output of the sigma Linear, k ascending -- an all-zero label row leaves es as it is.  K is the handful of augment labels
+// (6): one thread per output element, no GEMM.
+__global__ void k_aug_embed_fwd(float* __restrict__ es, const float* __restrict__ a, const float* __restrict__ w, int B,
+                                int E, int K) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * E) return;
+  const int b = i / E, e = i % E;
+  float acc = 0.f;
+  for (int k = 0; k < K; ++k) acc += a[b * K + k] * w[(long)e * K + k];
+  es[i] += acc;
+}
+// gw[e][k] = sum_b ges[b][e] * a[b][k]: one thread per weight element, b ascending -- a fixed order (no atomics), so an
+// eager and a replayed step give the same bits
+__global__ void k_aug_embed_wgrad(const float* __restrict__ ges, const float* __restrict__ a, float* __restrict__ gw,
+                                  int B, int E, int K) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= E * K) return;
+  const int e = i / K, k = i % K;
+  float acc = 0.f;
+  for (int b = 0; b < B; ++b) acc += ges[(long)b * E + e] * a[b * K + k];
+  gw[i] = acc;
+}
+
 }  // namespace
 
 // Y[M,N] = X[M,K] W[N,K]^T   (weight-normalised Linear with the effective fp32 weight)
@@ -254,5 +278,24 @@ extern "C" int edm_embed_combine_bwd(const float* gout, const float* pre, const 
   hipLaunchKernelGGL(k_embed_combine_bwd, dim3((B * E + 255) / 256), dim3(256), 0, st, gout, pre, labels, add_factor, K,
                      gemb_sigma, gwcls_hat, B, E, drop);
   EDM_CHECK_LAUNCH("embed_combine_bwd");
+  return EDM_OK;
+}
+
+// Augment labels a [B][K] through the effective weight w_hat [E][K] of Embedding.aug_embed, added in place to emb_sigma
+// [B][E] (the output of edm_linear_fwd) before edm_embed_combine_fwd; and the weight gradient of that product.
+extern "C" int edm_aug_embed_fwd(float* emb_sigma, const float* aug, const float* w_hat, int B, int E, int K,
+                                 hipStream_t st) {
+  EDM_REQUIRE(emb_sigma && aug && w_hat && B > 0 && E > 0 && K > 0 && (long)B * E <= 0x7fffffffL, "aug_embed_fwd: bad args");
+  hipLaunchKernelGGL(k_aug_embed_fwd, dim3((B * E + 255) / 256), dim3(256), 0, st, emb_sigma, aug, w_hat, B, E, K);
+  EDM_CHECK_LAUNCH("aug_embed_fwd");
+  return EDM_OK;
+}
+// gw_hat [E][K] is overwritten
+extern "C" int edm_aug_embed_wgrad(const float* gemb_sigma, const float* aug, float* gw_hat, int B, int E, int K,
+                                   hipStream_t st) {
+  EDM_REQUIRE(gemb_sigma && aug && gw_hat && B > 0 && E > 0 && K > 0 && (long)E * K <= 0x7fffffffL,
+              "aug_embed_wgrad: bad args");
+  hipLaunchKernelGGL(k_aug_embed_wgrad, dim3((E * K + 255) / 256), dim3(256), 0, st, gemb_sigma, aug, gw_hat, B, E, K);
+  EDM_CHECK_LAUNCH("aug_embed_wgrad");
   return EDM_OK;
 }

@@ -2,6 +2,9 @@
 288 GB of HBM: the whole dataset is loaded ONCE, kept resident on the device as uint8 (CIFAR-10: 150 MB, MNIST:
 47 MB) or as fp32 latents, and every batch is one gather kernel (`edm_u8_gather_normalize`: index -> x/255 ->
 flip -> normalise, csrc/data.hip) -- no worker processes, no pinned staging buffers, no H2D copy per step.
+With ``augment_prob > 0`` the train loader's gather is `edm_u8_gather_augment_normalize`: the non-leaking augmentation of
+EDM (Karras et al. 2022, App. F.2; the exact ops xflip, yflip, whole-pixel translation, rot90) as index arithmetic inside
+the same launch, and its batches are (x, y, augment_labels) for ``Embedding(augment_dim=6)``.
 The on-disk formats are read directly (torchvision is not a dependency): `cifar-10-batches-py` pickles, MNIST
 idx-ubyte files, per-sample `.npy` latents.
 
@@ -197,9 +200,11 @@ class _ResidentLoader:
     """Batches gathered on the device from a resident uint8 dataset; shuffled per epoch with torch.randperm
     (same permutation on every rank), each rank taking its `rank::world` share (DistributedSampler semantics)."""
 
-    def __init__(self, data_u8, labels, batch_size, shuffle, flip, seed, mean, std, rank=None, world=None):
+    def __init__(self, data_u8, labels, batch_size, shuffle, flip, seed, mean, std, rank=None, world=None,
+                 augment_prob=0.0, augment_ops=()):
         self.data, self.labels, self.batch_size = data_u8, labels, batch_size
         self.shuffle, self.flip, self.seed, self.mean, self.std = shuffle, flip, seed, mean, std
+        self.augment_prob, self.augment_ops = float(augment_prob), tuple(augment_ops)
         self.rank, self.world = _rank_world(rank, world)
         self.epoch = 0
 
@@ -212,6 +217,12 @@ class _ResidentLoader:
                             self.data.device)
         for bi in range(len(self)):
             idx = order[bi * self.batch_size:(bi + 1) * self.batch_size].contiguous()
+            if self.augment_prob > 0:       # same seed / epoch words as the flip; the draws have a counter tag of their own
+                x, aug = ops.u8_gather_augment_normalize(self.data, idx, self.mean, self.std, flip=self.flip,
+                                                         seed=self.seed + 7919 * self.rank, epoch=self.epoch * 65536 + bi,
+                                                         p=self.augment_prob, ops=self.augment_ops)
+                yield x, self.labels[idx], aug
+                continue
             x = ops.u8_gather_normalize(self.data, idx, self.mean, self.std, flip=self.flip,
                                         seed=self.seed + 7919 * self.rank, epoch=self.epoch * 65536 + bi)
             yield x, self.labels[idx]
@@ -220,11 +231,23 @@ class _ResidentLoader:
 
 class AbstractDataModule:
     """Constructor / property surface of datamodules/abstract_datamodule.py:6-67 (num_workers is accepted and
-    ignored: there are no worker processes)."""
+    ignored: there are no worker processes).
 
-    def __init__(self, data_dir, batch_size: int, num_workers: int = 0, device: str | None = None, seed: int = 42):
+    ``augment_prob`` / ``augment_ops`` (extensions of the image datamodules): non-leaking augmentation of the TRAIN loader,
+    each op applied per sample with probability augment_prob; its batches are then (x, y, augment_labels (B, 6))."""
+
+    AUGMENT_OPS = ("xflip", "yflip", "translate", "rot90")
+
+    def __init__(self, data_dir, batch_size: int, num_workers: int = 0, device: str | None = None, seed: int = 42,
+                 augment_prob: float = 0.0, augment_ops=AUGMENT_OPS):
         self.data_dir, self.batch_size, self.num_workers = data_dir, batch_size, num_workers
         self.device, self.seed = device, seed
+        self.augment_prob, self.augment_ops = float(augment_prob), tuple(augment_ops)
+        if not 0.0 <= self.augment_prob <= 1.0:
+            raise ValueError(f"augment_prob must be in [0, 1], got {augment_prob}")
+        unknown = [o for o in self.augment_ops if o not in self.AUGMENT_OPS]
+        if unknown:
+            raise ValueError(f"unknown augment_ops {unknown}: expected a subset of {self.AUGMENT_OPS}")
         self.train_dataset = self.val_dataset = self.test_dataset = None
         self.mean, self.std, self.flip = 0.5, 0.5, False
 
@@ -235,16 +258,19 @@ class AbstractDataModule:
         pass
 
     def _resident(self, x, y):
+        if self.augment_prob > 0 and "rot90" in self.augment_ops and x.shape[-2] != x.shape[-1]:
+            raise ValueError(f"augment_ops: rot90 needs square images, the set is {x.shape[-2]} x {x.shape[-1]}")
         dev = self._dev()
         return torch.from_numpy(np.ascontiguousarray(x)).to(dev), torch.from_numpy(y).to(dev)
 
-    def _loader(self, ds, shuffle, flip):
+    def _loader(self, ds, shuffle, flip, augment=False):
         if ds is None:
             raise RuntimeError("call setup() first")
-        return _ResidentLoader(ds[0], ds[1], self.batch_size, shuffle, flip, self.seed, self.mean, self.std)
+        return _ResidentLoader(ds[0], ds[1], self.batch_size, shuffle, flip, self.seed, self.mean, self.std,
+                               augment_prob=self.augment_prob if augment else 0.0, augment_ops=self.augment_ops)
 
     def train_dataloader(self):
-        return self._loader(self.train_dataset, True, self.flip)
+        return self._loader(self.train_dataset, True, self.flip, augment=True)
 
     def val_dataloader(self):
         return self._loader(self.val_dataset, False, self.flip)
@@ -264,8 +290,9 @@ class CIFAR10DataModule(AbstractDataModule):
     classes = ["airplane", "automobile", "bird", "cat", "deer", "dog", "frog", "horse", "ship", "truck"]
 
     def __init__(self, data_dir: str = "datasets/cifar", image_size: int = 32, batch_size: int = 16, num_workers: int = 16,
-                 device: str | None = None, seed: int = 42):
-        super().__init__(data_dir, batch_size, num_workers, device, seed)
+                 device: str | None = None, seed: int = 42, augment_prob: float = 0.0,
+                 augment_ops=AbstractDataModule.AUGMENT_OPS):
+        super().__init__(data_dir, batch_size, num_workers, device, seed, augment_prob, augment_ops)
         if image_size != 32:
             raise ValueError("CIFAR10DataModule: only the native image_size 32 is supported")
         self.img_size, self.flip = image_size, True
@@ -290,8 +317,9 @@ class MNISTDataModule(AbstractDataModule):
     classes = [str(i) for i in range(10)]
 
     def __init__(self, batch_size: int, num_workers: int = 0, image_size: int = 28, data_dir: str = "datasets/mnist",
-                 device: str | None = None, seed: int = 42):
-        super().__init__(data_dir, batch_size, num_workers, device, seed)
+                 device: str | None = None, seed: int = 42, augment_prob: float = 0.0,
+                 augment_ops=AbstractDataModule.AUGMENT_OPS):
+        super().__init__(data_dir, batch_size, num_workers, device, seed, augment_prob, augment_ops)
         if image_size != 28:
             raise ValueError("MNISTDataModule: only the native image_size 28 is supported")
 

@@ -127,10 +127,20 @@ class EDM(LightningModule):
 
     # ------------------------------------------------------------------ steps (edm.py:205-248)
     def _loss(self, batch, metric, training: bool):
-        clean_image, class_label = batch
+        if len(batch) not in (2, 3):
+            raise ValueError(f"EDM: a batch is (images, labels) or (images, labels, augment_labels), got {len(batch)} elements")
+        clean_image, class_label, *augment = batch
+        augment_labels = augment[0] if augment else None
+        if augment_labels is not None and getattr(self.embedding, "augment_dim", 0) == 0:
+            # augmenting without telling the network is the leak non-leaking augmentation exists to prevent
+            raise ValueError("EDM: the batch carries augment labels but embedding.augment_dim is 0: build the Embedding "
+                             "with augment_dim=6, or set the datamodule's augment_prob to 0")
         class_label = class_label if self.conditional else None
         noisy_image, sigma = self.diffuser(clean_image)
-        fourier_embedding, embedding = self.embedding(sigma, class_label)
+        if augment_labels is None:
+            fourier_embedding, embedding = self.embedding(sigma, class_label)
+        else:
+            fourier_embedding, embedding = self.embedding(sigma, class_label, augment_labels)
         denoised_image = self.denoiser(noisy_image, sigma, embedding)
         if not (training and self.u is not None) and hasattr(metric, "forward_sigma"):
             return metric.forward_sigma(sigma, self.sigma_data, denoised_image, clean_image)   # lambda(sigma) in-kernel
@@ -187,9 +197,15 @@ class EDM(LightningModule):
         return LambdaLR(optimizer, lambda s: EDM.lr_lambda(s, rampup_steps, steady_steps))
 
     # ------------------------------------------------------------------ inference (edm.py:280-303)
-    def forward(self, noisy_image: Tensor, sigma: Tensor, class_label: Tensor | None = None) -> Tensor:
+    def forward(self, noisy_image: Tensor, sigma: Tensor, class_label: Tensor | None = None,
+                augment_labels: Tensor | None = None) -> Tensor:
+        """augment_labels (extension): the solvers, predict_step and generate pass none -- "not augmented", the all-zero
+        label vector of an Embedding(augment_dim > 0)"""
         class_label = class_label if self.conditional else None
-        _, embedding = self.embedding(sigma, class_label)
+        if augment_labels is None:
+            _, embedding = self.embedding(sigma, class_label)
+        else:
+            _, embedding = self.embedding(sigma, class_label, augment_labels)
         return self.denoiser(noisy_image, sigma, embedding)
 
     def predict_step(self, batch: Any, batch_idx: int, dataloader_idx: int | None = None):

@@ -72,6 +72,7 @@ class _CapturedStep(NamedTuple):
     y: object               # ... and of its labels, or None
     loss: torch.Tensor      # static: rewritten by every replay
     token: object           # launch-table slots and plan pins of the capture (ops.release_capture)
+    aug: object = None      # static copy of the batch's augment labels (a 3-element batch), or None
 
 
 class CapturedTrainStep:
@@ -205,8 +206,11 @@ class CapturedTrainStep:
         return ent
 
     def __call__(self, batch):
-        x, y = batch
+        x, y, *rest = batch
+        a = rest[0] if rest else None       # augment labels of a (x, y, aug) batch
         key = (tuple(x.shape), x.dtype, None if y is None else (tuple(y.shape), y.dtype))
+        if a is not None:                   # (a 2-element batch keeps the key it always had)
+            key += ((tuple(a.shape), a.dtype),)
         self._upload()
         networks.rng.dyn = self.params.dev
         try:
@@ -226,6 +230,8 @@ class CapturedTrainStep:
                 ent.x.copy_(x, non_blocking=True)
                 if ent.y is not None:
                     ent.y.copy_(y, non_blocking=True)
+                if ent.aug is not None:
+                    ent.aug.copy_(a, non_blocking=True)
                 ent.graph.replay()
         finally:
             networks.rng.dyn = None
@@ -234,9 +240,10 @@ class CapturedTrainStep:
         return loss
 
     def _capture(self, batch):
-        x, y = batch
+        x, y, *rest = batch
         sx = x.clone()
         sy = None if y is None else y.clone()
+        sa = rest[0].clone() if rest and rest[0] is not None else None
         snap = self._snapshot()
         torch.cuda.synchronize()
         mode = "global"
@@ -255,7 +262,7 @@ class CapturedTrainStep:
         try:
             # (a failed capture leaves no graph: capturing() gives its launch-table slots back)
             with ops.capturing(graph, stream=self.stream, capture_error_mode=mode) as capture:
-                loss = self.model.training_step((sx, sy), 0)
+                loss = self.model.training_step((sx, sy) if sa is None else (sx, sy, sa), 0)
                 _backward(self.model, loss)     # the reducer's hooks fork the comm stream off the capture stream ...
                 if self.reducer is not None:
                     self.reducer.finish()       # ... and this joins it: the all-reduces are nodes of the graph
@@ -268,7 +275,7 @@ class CapturedTrainStep:
         finally:
             networks.WGRAD_STREAM = side
             self._restore(snap)
-        return graph, sx, sy, loss, capture.token
+        return graph, sx, sy, loss, capture.token, sa
 
     def _drop(self, key):
         ops.drop_capture(self._graphs, key)

@@ -731,13 +731,15 @@ class FourierEmbedding(nn.Module):
 
 class _EmbeddingFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, sigma, labels, w_sigma, w_cls, mod: "Embedding"):
+    def forward(ctx, sigma, labels, w_sigma, w_cls, mod: "Embedding", aug=None, w_aug=None):
         ctx.set_materialize_grads(False)
-        B = max(sigma.numel(), labels.numel() if labels is not None else 1)
+        B = max(sigma.numel(), labels.numel() if labels is not None else 1, aug.shape[0] if aug is not None else 1)
         four = ops.fourier_fwd(sigma, mod.fourier_embed.freqs, mod.fourier_embed.phases, B)
         wsh = mod.sigma_embed.packs()[2]
         wch = mod.class_embed.linear.packs()[2] if labels is not None else None
         es = ops.linear_fwd(four, wsh)
+        if aug is not None:         # augment labels: es += aug . w_aug_hat^T (a plain add, as in EDM), before the combine
+            ops.aug_embed_fwd(es, aug, mod.aug_embed.packs()[2])
         drop = None
         if labels is not None and mod.training and mod.label_dropout > 0:
             # label dropout: the per-sample mask is drawn in the combine kernel from the Diffuser's (seed, step)
@@ -745,7 +747,7 @@ class _EmbeddingFn(torch.autograd.Function):
                                                    seed=rng.seed, step=rng.step, dyn=rng.dyn)
         else:
             pre, out = ops.embed_combine_fwd(es, wch, labels, mod.add_factor)
-        ctx.mod, ctx.labels, ctx.drop = mod, labels, drop
+        ctx.mod, ctx.labels, ctx.drop, ctx.aug = mod, labels, drop, aug
         mod.last_label_drop = drop
         ctx.save_for_backward(four, pre)
         ctx.mark_non_differentiable(four)
@@ -760,7 +762,11 @@ class _EmbeddingFn(torch.autograd.Function):
         dws = ops.linear_wgrad(ges, four)
         gws = mod.sigma_embed.finish_grad(dws.view(1, 1, *dws.shape))
         gwc = mod.class_embed.linear.finish_grad(gwch.view(1, 1, *gwch.shape)) if gwch is not None else None
-        return None, None, gws, gwc, None
+        gwa = None
+        if ctx.aug is not None and ctx.needs_input_grad[6]:
+            dwa = ops.aug_embed_wgrad(ges, ctx.aug)
+            gwa = mod.aug_embed.finish_grad(dwa.view(1, 1, *dwa.shape))
+        return None, None, gws, gwc, None, None, gwa
 
 
 class Embedding(nn.Module):
@@ -770,13 +776,23 @@ class Embedding(nn.Module):
     p -- its embedding is the label-free one, ``forward(sigma, None)`` -- so that the same network can serve as its own
     unconditional guide (classifier-free guidance, ``guide="unconditional"`` of the solvers).  The per-sample choice is
     drawn in the combine kernel from the Philox stream of the Diffuser's (seed, step); ``last_label_drop`` holds the
-    int32 mask of the last training forward (None when nothing was dropped).  eval() and label-free calls never drop."""
+    int32 mask of the last training forward (None when nothing was dropped).  eval() and label-free calls never drop.
 
-    _local_extensions = ("label_dropout",)      # not in the reference's signature: left out of deinstantiate at default
+    ``augment_dim`` (extension, default 0): the length of the augment-label vector of non-leaking augmentation (Karras et
+    al. 2022, EDM, App. F.2; 6 for the datamodules' ops).  With augment_dim > 0 the module owns ``aug_embed``, a Linear
+    from the labels to the embedding whose output is ADDED to the sigma Linear's before the combine:
+    ``forward(sigma, labels, augment_labels)``.  ``augment_labels=None`` (every sampling call) skips the path -- it is
+    what an all-zero label vector, "not augmented", computes."""
+
+    _local_extensions = ("label_dropout", "augment_dim")    # not in the reference's signature: left out of deinstantiate at default
 
     def __init__(self, fourier_dim: int, embedding_dim: int, num_classes: int | None = None, add_factor: float = 0.5,
-                 label_dropout: float = 0.0):
+                 label_dropout: float = 0.0, augment_dim: int = 0):
         super().__init__()
+        augment_dim = int(augment_dim)
+        if augment_dim < 0:
+            raise ValueError(f"Embedding: augment_dim must be >= 0, got {augment_dim}")
+        self.augment_dim = augment_dim
         label_dropout = float(label_dropout)
         if not 0.0 <= label_dropout <= 1.0:
             raise ValueError(f"Embedding: label_dropout must be in [0, 1], got {label_dropout}")
@@ -795,8 +811,14 @@ class Embedding(nn.Module):
         if num_classes is not None and num_classes != -1:
             self.class_embed = ClassEmbedding(num_classes, embedding_dim)
             self.class_embed.linear.weight._edm_late = True
+        self.aug_embed = None
+        if augment_dim > 0:
+            self.aug_embed = Linear(augment_dim, embedding_dim)
+            self.aug_embed.weight._edm_late = True
 
-    def forward(self, sigmas: Tensor, class_labels: Tensor | None = None):
+    def forward(self, sigmas: Tensor, class_labels: Tensor | None = None, augment_labels: Tensor | None = None):
+        if augment_labels is not None and self.aug_embed is None:
+            raise ValueError("augment_labels is not None, but augment_dim is 0. ")
         if class_labels is not None and self.class_embed is None:
             raise ValueError("class_labels is not None, but num_classes is None. ")
         if not sigmas.is_cuda:
@@ -808,7 +830,15 @@ class Embedding(nn.Module):
             if sigma.numel() not in (1, labels.numel()):
                 raise ValueError("sigma and class_labels batch sizes differ")
         w_cls = self.class_embed.linear.weight if labels is not None else None
-        four, out = _EmbeddingFn.apply(sigma, labels, self.sigma_embed.weight, w_cls, self)
+        aug = w_aug = None
+        if augment_labels is not None:
+            aug = augment_labels.detach().to(sigma.device).float().contiguous()
+            if aug.dim() != 2 or aug.shape[1] != self.augment_dim:
+                raise ValueError(f"augment_labels must have shape (B, {self.augment_dim}), got {tuple(aug.shape)}")
+            if sigma.numel() not in (1, aug.shape[0]) or (labels is not None and labels.numel() != aug.shape[0]):
+                raise ValueError("sigma / class_labels and augment_labels batch sizes differ")
+            w_aug = self.aug_embed.weight
+        four, out = _EmbeddingFn.apply(sigma, labels, self.sigma_embed.weight, w_cls, self, aug, w_aug)
         if sigmas.numel() == 1:
             four = four[:1]
         return four, out

@@ -1478,6 +1478,38 @@ def embed_combine_bwd(gout, pre, labels, add_factor, wcls_shape, *, drop=None):
     return ges, gw
 
 
+def aug_embed_fwd(emb_sigma, aug, w_hat):
+    """emb_sigma (B,E) += aug (B,K) @ w_hat (E,K)^T, IN PLACE (returns emb_sigma): the augment-label conditioning of
+    Embedding(augment_dim=K), added to the output of the sigma Linear before embed_combine_fwd.  An all-zero row of aug
+    leaves its row of emb_sigma unchanged."""
+    _chk(emb_sigma, f32, "emb_sigma")
+    if emb_sigma.dim() != 2:
+        raise ValueError("aug_embed_fwd: emb_sigma must be (B, E)")
+    B, E = emb_sigma.shape
+    _chk(aug, f32, "aug")
+    if aug.dim() != 2 or aug.shape[0] != B:
+        raise ValueError(f"aug_embed_fwd: aug must be ({B}, K), got {tuple(aug.shape)}")
+    K = aug.shape[1]
+    _chk(w_hat, f32, "w_hat", (E, K))
+    _lib.call("edm_aug_embed_fwd", _p(emb_sigma), _p(aug), _p(w_hat), B, E, K, _stream())
+    return emb_sigma
+
+
+def aug_embed_wgrad(gemb_sigma, aug):
+    """-> gw_hat (E,K) = gemb_sigma (B,E)^T @ aug (B,K), summed over b in ascending order (bit-reproducible)."""
+    _chk(gemb_sigma, f32, "gemb_sigma")
+    if gemb_sigma.dim() != 2:
+        raise ValueError("aug_embed_wgrad: gemb_sigma must be (B, E)")
+    B, E = gemb_sigma.shape
+    _chk(aug, f32, "aug")
+    if aug.dim() != 2 or aug.shape[0] != B:
+        raise ValueError(f"aug_embed_wgrad: aug must be ({B}, K), got {tuple(aug.shape)}")
+    K = aug.shape[1]
+    gw = torch.empty(E, K, device=gemb_sigma.device, dtype=f32)
+    _lib.call("edm_aug_embed_wgrad", _p(gemb_sigma), _p(aug), _p(gw), B, E, K, _stream())
+    return gw
+
+
 # ------------------------------------------------------------------ step-level kernels
 def diffuse(clean, P_mean, P_std, seed, step, dyn=None):
     _chk(clean, f32, "clean")
@@ -2295,6 +2327,42 @@ def u8_gather_normalize(data, index, mean=0.5, std=0.5, flip=False, seed=0, epoc
     _lib.call("edm_u8_gather_normalize", _p(data), _p(index), _p(out), B, C, H, W, N, float(mean), float(std),
               int(bool(flip)), int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF, _stream())
     return out
+
+
+AUGMENT_OPS = ("xflip", "yflip", "translate", "rot90")      # bit i of the op mask; also the order they are applied in
+AUGMENT_DIM = 6                                             # (xflip, yflip, sx/W, sy/H, cos(k pi/2) - 1, sin(k pi/2))
+
+
+def augment_op_mask(names) -> int:
+    """op names -> the 4-bit mask of edm_u8_gather_augment_normalize"""
+    mask = 0
+    for n in names:
+        if n not in AUGMENT_OPS:
+            raise ValueError(f"unknown augmentation op {n!r}: expected a subset of {AUGMENT_OPS}")
+        mask |= 1 << AUGMENT_OPS.index(n)
+    return mask
+
+
+def u8_gather_augment_normalize(data, index, mean=0.5, std=0.5, flip=False, seed=0, epoch=0, *, p=0.0,
+                                ops=AUGMENT_OPS):
+    """u8_gather_normalize with the non-leaking augmentation (EDM, App. F.2; exact subset) composed into the gather ->
+    (x fp32 (B,C,H,W), aug fp32 (B,6)).  Each op of `ops` is applied per sample with probability p (a 32-bit threshold,
+    label_drop_threshold: p = 0 never, p = 1 always); aug holds the parameters of what was applied, zeros otherwise."""
+    _chk(data, torch.uint8, "data")
+    _chk(index, torch.int64, "index")
+    if data.dim() != 4 or index.dim() != 1:
+        raise ValueError("u8_gather_augment_normalize: data must be (N,C,H,W), index (B,)")
+    if not 0.0 <= float(p) <= 1.0:
+        raise ValueError(f"u8_gather_augment_normalize: p must be in [0, 1], got {p}")
+    mask = augment_op_mask(ops) if not isinstance(ops, int) else int(ops)
+    N, C, H, W = data.shape
+    B = index.shape[0]
+    out = torch.empty(B, C, H, W, device=data.device, dtype=f32)
+    aug = torch.empty(B, AUGMENT_DIM, device=data.device, dtype=f32)
+    _lib.call("edm_u8_gather_augment_normalize", _p(data), _p(index), _p(out), B, C, H, W, N, float(mean), float(std),
+              int(bool(flip)), int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF, label_drop_threshold(p), mask,
+              _p(aug), _stream())
+    return out, aug
 
 
 def denormalize_u8(x, scale=127.5, offset=128.0):
