@@ -530,6 +530,31 @@ int edm_heun_correct_div(const float* E, const float* dx, const float* E1, const
                          double* part, double* L, unsigned* health, edm_stream_t stream);
 int edm_nll_prior(const float* x, float t, int B, long CHW, double* part, double* L, unsigned* health,
                   edm_stream_t stream);
+/* Loss by noise level (tinyedm_amd/evaluate.py): the denoising error of held-out images at fixed noise levels with fixed
+ * noise, a number that is the same for the same checkpoint on every run.
+ * edm_eval_diffuse: noisy_b = clean_b + sigma_b * n as one fma per element, sigma_b = sigmas[level[b]], and
+ *   sigma_out[b] = sigma_b.  clean / noisy: contiguous [B, CHW] fp32; ids: DEVICE uint32 [B], the image's index in the
+ *   evaluation set; level: DEVICE int32 [B] with 0 <= level[b] < L; sigmas: DEVICE float [L], 1 <= L <= 65535; sigma_out:
+ *   DEVICE float [B].  n ~ N(0, 1) is drawn in the kernel and belongs to the image, not to the row: element j of sample b
+ *   is normal j % 4 of one Philox4x32-10 call with counter (j / 4, ids[b], 0x45560000 ^ level[b], draw) and key
+ *   (seed_lo, seed_hi), Box-Muller of words (0, 1) and (2, 3) as edm_heun_churn.  level < 65536, so the tag differs from
+ *   the churn's 0x43480000, the blend's 0x49500000, the probes' 0x4E4C0000 + (ev << 16) and edm_diffuse's 0xD1FF / 0x5167.
+ *   rec is the churn's DEVICE record {seed_lo, seed_hi, draw, 0}, read at run time.  The noise of an (id, level, draw)
+ *   does not depend on B, on the row, on the other rows or on the memory path (dwordx4 when CHW % 4 == 0 and clean, noisy
+ *   are 16-byte aligned, else element by element with the same bits).  The caller validates level; the kernel uses no
+ *   unchecked value as an index: a level outside [0, L) gives that row sigma = NaN and sets the health bit.  Same health
+ *   bit as the Heun updates when an output is non-finite.
+ * edm_eval_sqerr: se[b] = sum_j ((double)D_bj - (double)clean_bj)^2, D / clean contiguous [B, CHW] fp32, B <= 65535; se
+ *   is a DEVICE fp64 [B] slice, WRITTEN (it may point into a larger result matrix).  Order-fixed, no floating-point
+ *   atomics: per-(sample, chunk) fp64 partials go to `part`, a DEVICE workspace of B * EDM_NLL_MAX_CHUNKS doubles, and a
+ *   one-thread-per-sample finish launch adds them in index order.  A sample's chunking depends on CHW alone, so se[b] is
+ *   bit-identical whatever B, the row or the memory path (dwordx4 when CHW % 4 == 0 and D, clean are 16-byte aligned).
+ *   Same health bit when se[b] is non-finite. */
+int edm_eval_diffuse(const float* clean, const unsigned* ids, const int* level, const float* sigmas, int L,
+                     const void* rec, int B, long CHW, float* noisy, float* sigma_out, unsigned* health,
+                     edm_stream_t stream);
+int edm_eval_sqerr(const float* D, const float* clean, int B, long CHW, double* part, double* se, unsigned* health,
+                   edm_stream_t stream);
 int edm_scale_f32(const float* x, float s, float* y, long n, edm_stream_t stream);
 
 /* ---------------------------------------------------------------- reference-precision evaluation (eval_f32.hip)

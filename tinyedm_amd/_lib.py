@@ -118,6 +118,8 @@ SIGNATURES = {
     "edm_heun_euler_div": [P, P, F, F, F, F, P, I, I, I, L, P, P, P, P, P, P],
     "edm_heun_correct_div": [P, P, P, P, F, F, F, F, P, I, I, I, I, L, P, P, P, P, P],
     "edm_nll_prior": [P, F, I, L, P, P, P, P],
+    "edm_eval_diffuse": [P, P, P, P, I, P, I, L, P, P, P, P],
+    "edm_eval_sqerr": [P, P, I, L, P, P, P, P],
     "edm_scale_f32": [P, F, P, L, P],
     # restore.hip
     "edm_degrade": [P, P, I, I, I, I, I, I, P],

@@ -248,3 +248,60 @@ class ModelCheckpoint:
     def on_train_epoch_end(self, trainer, pl_module):
         if self.save_on_train_epoch_end:
             self._maybe_save(trainer, pl_module)
+
+
+class LossByNoiseLevel:
+    """Every ``every_n_epochs`` validation epochs: the denoising loss of the first ``num_images`` validation images at
+    fixed noise levels with fixed noise (evaluate.NoiseLevelEvaluator; ``evaluator_kwargs`` are its constructor's), under
+    the weights validation is using (the EMA callback has them swapped in at this hook).  Logs ``val_expected_loss`` (the
+    mean loss over explicit ``sigmas``, which have no expected loss) and ``val_loss_sigma/<level>``.  Unlike ``val_loss``
+    the numbers depend on the weights alone: the images, the levels and the noise are the same at every epoch.
+    Additive: nothing runs unless the callback is configured."""
+
+    def __init__(self, num_images: int = 1024, every_n_epochs: int = 1, **evaluator_kwargs):
+        from .evaluate import NoiseLevelEvaluator
+        for name, v in (("num_images", num_images), ("every_n_epochs", every_n_epochs)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"LossByNoiseLevel: {name} must be an integer >= 1, got {v!r}")
+        self.num_images, self.every_n_epochs = num_images, every_n_epochs
+        self.evaluator = NoiseLevelEvaluator(**evaluator_kwargs)
+        self.images = self.labels = self.ids = self.last = None
+
+    def _take(self, trainer, pl_module):
+        """the first num_images of the validation set, once: unflipped from a resident dataset, else from its loader"""
+        dm = getattr(trainer, "datamodule", None)
+        ds = getattr(dm, "val_dataset", None)
+        if ds is not None and isinstance(ds[0], torch.Tensor) and ds[0].dtype == torch.uint8:
+            n = min(self.num_images, ds[0].shape[0])
+            self.images = ops.u8_gather_normalize(ds[0], torch.arange(n, device=ds[0].device), dm.mean, dm.std)
+            self.labels = ds[1][:n]
+            return
+        if dm is None or not hasattr(dm, "val_dataloader"):
+            raise RuntimeError("LossByNoiseLevel: the trainer has no datamodule with a val_dataloader")
+        xs, ys, have = [], [], 0
+        for batch in dm.val_dataloader():
+            xs.append(batch[0].float())
+            ys.append(batch[1])
+            have += batch[0].shape[0]
+            if have >= self.num_images:
+                break
+        self.images = torch.cat(xs)[:self.num_images].to(pl_module.device).contiguous()
+        self.labels = torch.cat(ys)[:self.num_images].to(pl_module.device)
+
+    def on_validation_epoch_end(self, trainer, pl_module):
+        if trainer.current_epoch % self.every_n_epochs != 0:
+            return
+        if self.images is None:
+            self._take(trainer, pl_module)
+            world, rank = getattr(trainer, "world_size", 1), getattr(trainer, "global_rank", 0)
+            if world > 1:       # every rank took the same images: each keeps its share, the evaluator merges the sums
+                keep = torch.arange(self.images.shape[0], device=self.images.device) % world == rank
+                self.ids = torch.arange(self.images.shape[0])[keep.cpu()]
+                self.images, self.labels = self.images[keep].contiguous(), self.labels[keep]
+        labels = self.labels if getattr(pl_module, "conditional", False) else None
+        res = self.evaluator.evaluate(pl_module, self.images, labels, self.ids)
+        self.last = res
+        total = res["expected_loss"] if res["expected_loss"] is not None else res["mean_loss"]
+        for name, v in [("val_expected_loss", total)] + [(f"val_loss_sigma/{l}", v) for l, v in enumerate(res["loss"])]:
+            pl_module.log(name, v)
+            trainer.callback_metrics[name] = float(v)

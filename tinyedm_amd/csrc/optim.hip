@@ -753,6 +753,79 @@ inline int nll_chunks(long CHW) {
   const long c = ((CHW + 3) / 4 + 255) / 256;
   return (int)(c < NLL_MAX_CHUNKS ? c : NLL_MAX_CHUNKS);
 }
+// Loss by noise level (evaluate.py): noisy_b = clean_b + sigma_b * n with sigma_b = sigmas[level[b]] and n ~ N(0, 1) that
+// belongs to the IMAGE ids[b], not to the row b: element j = 4q + k of sample b takes normal k of
+//   philox4x32_10(ctr = (q, ids[b], 0x45560000 ^ level[b], draw), key = (seed_lo, seed_hi)),
+// Box-Muller of words (0, 1) and (2, 3) as k_heun_churn; rec = {seed_lo, seed_hi, draw, 0} is the churn's device record.
+// level < 65536 keeps the tag's high half 0x4556 apart from 0x4348 (churn), 0x4950 (blend), 0x4E4C / 0x4E4D (likelihood
+// probes) and from the 16-bit tags 0xD1FF / 0x5167 (high half 0).  The noise of (id, level, draw) depends neither on B,
+// on the row, on the row's neighbours nor on the memory path.  A level outside [0, L) is never used as an index: the
+// sample's sigma and outputs become NaN and the health bit is set (ops refuses such a level before the launch).
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_eval_diffuse(const float* __restrict__ clean, const uint32_t* __restrict__ ids,
+                                                      const int* __restrict__ level, const float* __restrict__ sigmas,
+                                                      int L, const uint32_t* __restrict__ rec, int B, long CHW,
+                                                      float* __restrict__ noisy, float* __restrict__ sigma_out,
+                                                      unsigned* __restrict__ health) {
+  const uint32_t seed_lo = rec[0], seed_hi = rec[1], draw = rec[2];
+  const long nq = (CHW + 3) / 4, total = (long)B * nq;
+  bool bad = false;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const long b = i / nq, q = i - b * nq, e = b * CHW + 4 * q;
+    const int lv = level[b];
+    const bool lv_ok = lv >= 0 && lv < L;
+    const float s = lv_ok ? sigmas[lv] : __builtin_nanf("");
+    if (q == 0) sigma_out[b] = s;
+    bad |= !lv_ok;
+    const Philox4 r = philox4x32_10((uint32_t)q, ids[b], 0x45560000u ^ (uint32_t)lv, draw, seed_lo, seed_hi);
+    float nn[4], xv[4], ov[4];
+    box_muller(r.x, r.y, nn[0], nn[1]);
+    box_muller(r.z, r.w, nn[2], nn[3]);
+    const int m = VEC ? 4 : (int)(CHW - 4 * q < 4 ? CHW - 4 * q : 4);
+    nll_load4<VEC>(clean + e, m, xv);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      ov[k] = fmaf(s, nn[k], xv[k]);
+      bad |= k < m && !(fabsf(ov[k]) <= 3.0e38f);
+    }
+    nll_store4<VEC>(noisy + e, m, ov);
+  }
+  if (health && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(health, 2u);
+}
+// part[b][chunk] = this chunk's share of sum_j ((double)D_bj - (double)clean_bj)^2.  The difference of two fp32 values
+// is exact in fp64.  grid (nll_chunks(CHW), B): a sample's chunking, and with it the order of every add, depends on CHW
+// alone, so se[b] has the same bits whatever B, the row or the memory path (the padding of a partial quad adds +0.0).
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_eval_sqerr(const float* __restrict__ D, const float* __restrict__ clean,
+                                                    long CHW, double* __restrict__ part) {
+  const long nq = (CHW + 3) / 4, b = blockIdx.y;
+  double acc = 0.0;
+  for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
+    const int m = VEC ? 4 : (int)(CHW - 4 * q < 4 ? CHW - 4 * q : 4);
+    float dv[4], cv[4];
+    nll_load4<VEC>(D + b * CHW + 4 * q, m, dv);
+    nll_load4<VEC>(clean + b * CHW + 4 * q, m, cv);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const double d = (double)dv[k] - (double)cv[k];
+      acc = fma(d, d, acc);
+    }
+  }
+  nll_block_partial(acc, part + b * NLL_MAX_CHUNKS + blockIdx.x);
+}
+// se[b] = part[b][0] + part[b][1] + ... in index order (written, not accumulated); health bit 1 on a non-finite se
+__global__ __launch_bounds__(64) void k_eval_sqerr_finish(const double* __restrict__ part, int chunks, int B,
+                                                          double* __restrict__ se, unsigned* __restrict__ health) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  bool bad = false;
+  if (b < B) {
+    double s = 0.0;
+    for (int c = 0; c < chunks; ++c) s += part[(long)b * NLL_MAX_CHUNKS + c];
+    se[b] = s;
+    bad = !(fabs(s) <= 1.0e300);
+  }
+  if (health && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(health, 2u);
+}
 __global__ void k_scale_f32(const float* __restrict__ x, float s, float* __restrict__ y, long n) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) y[i] = x[i] * s;
 }
@@ -924,6 +997,38 @@ extern "C" int edm_heun_churn(const float* x, float c, const void* rec, int step
   hipLaunchKernelGGL(k_heun_churn, dim3(grid_for((long)B * ((CHW + 3) / 4), 256)), dim3(256), 0, st, x, c,
                      (const uint32_t*)rec, (uint32_t)step, B, CHW, x_hat, vec, health);
   EDM_CHECK_LAUNCH("heun_churn");
+  return EDM_OK;
+}
+// ids [B] uint32, level [B] int32, sigmas [L] float: DEVICE arrays; rec: the churn's device record with the draw in word 2
+extern "C" int edm_eval_diffuse(const float* clean, const unsigned* ids, const int* level, const float* sigmas, int L,
+                                const void* rec, int B, long CHW, float* noisy, float* sigma_out, unsigned* health,
+                                hipStream_t st) {
+  EDM_REQUIRE(clean && ids && level && sigmas && rec && noisy && sigma_out && B > 0 && CHW > 0 && L >= 1 && L <= 65535,
+              "eval_diffuse: bad args (1 <= L <= 65535)");
+  EDM_REQUIRE((CHW + 3) / 4 <= 0xFFFFFFFFL, "eval_diffuse: CHW / 4 must fit the 32-bit Philox counter word");
+  const dim3 grid(grid_for((long)B * ((CHW + 3) / 4), 256)), block(256);
+  if (CHW % 4 == 0 && aligned16({clean, noisy}))
+    hipLaunchKernelGGL(k_eval_diffuse<true>, grid, block, 0, st, clean, (const uint32_t*)ids, level, sigmas, L,
+                       (const uint32_t*)rec, B, CHW, noisy, sigma_out, health);
+  else
+    hipLaunchKernelGGL(k_eval_diffuse<false>, grid, block, 0, st, clean, (const uint32_t*)ids, level, sigmas, L,
+                       (const uint32_t*)rec, B, CHW, noisy, sigma_out, health);
+  EDM_CHECK_LAUNCH("eval_diffuse");
+  return EDM_OK;
+}
+// part: device workspace of B * EDM_NLL_MAX_CHUNKS doubles; se: device fp64 [B], written
+extern "C" int edm_eval_sqerr(const float* D, const float* clean, int B, long CHW, double* part, double* se,
+                              unsigned* health, hipStream_t st) {
+  EDM_REQUIRE(D && clean && part && se && B > 0 && B <= 65535 && CHW > 0, "eval_sqerr: bad args (B <= 65535)");
+  const int chunks = nll_chunks(CHW);
+  const dim3 grid(chunks, B), block(256);
+  if (CHW % 4 == 0 && aligned16({D, clean}))
+    hipLaunchKernelGGL(k_eval_sqerr<true>, grid, block, 0, st, D, clean, CHW, part);
+  else
+    hipLaunchKernelGGL(k_eval_sqerr<false>, grid, block, 0, st, D, clean, CHW, part);
+  EDM_CHECK_LAUNCH("eval_sqerr");
+  hipLaunchKernelGGL(k_eval_sqerr_finish, dim3((B + 63) / 64), dim3(64), 0, st, (const double*)part, chunks, B, se, health);
+  EDM_CHECK_LAUNCH("eval_sqerr (finish)");
   return EDM_OK;
 }
 // Dg and w both given (guided) or both null; m2 needs m1; m_out nullable.  x_out and m_out alias no operand.

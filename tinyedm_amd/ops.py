@@ -1993,6 +1993,71 @@ def nll_prior(x, t, L):
     return L
 
 
+EVAL_MAX_LEVELS = 65535         # a level is the low half of the Philox tag 0x45560000 ^ level
+
+
+def _chk_eval(t, dtype, name, shape=None, device=None):
+    """_chk for the loss-by-noise-level ops: every bad operand is a ValueError"""
+    try:
+        _chk(t, dtype, name, shape)
+    except (TypeError, RuntimeError) as e:
+        raise ValueError(str(e)) from None
+    if device is not None and t.device != device:
+        raise ValueError(f"{name}: expected a tensor on {device}, got {t.device}")
+
+
+def eval_diffuse(clean, ids, level, sigmas, rec, check_levels=True):
+    """noisy_b = clean_b + sigmas[level[b]] * n with n ~ N(0, 1) drawn in the kernel for the IMAGE ids[b]: the noise depends
+    only on (seed, draw, ids[b], level[b], element), not on the batch or the row.  clean: contiguous fp32 [B, ...]; ids:
+    uint32 [B]; level: int32 [B] with values in [0, L); sigmas: fp32 [L], L <= 65535; rec: ops.churn_record(seed, draw).
+    Returns (noisy, sigma [B] fp32).  The level range is checked on the host before the launch (one device read);
+    check_levels=False is for a caller that built `level` itself from values it has already checked."""
+    _chk_eval(clean, f32, "clean")
+    if clean.dim() < 2 or clean.numel() == 0:
+        raise ValueError(f"clean: expected a non-empty [B, ...] tensor, got {tuple(clean.shape)}")
+    B = clean.shape[0]
+    _chk_eval(ids, torch.uint32, "ids", (B,), clean.device)
+    _chk_eval(level, torch.int32, "level", (B,), clean.device)
+    _chk_eval(sigmas, f32, "sigmas", None, clean.device)
+    if sigmas.dim() != 1 or not 1 <= sigmas.numel() <= EVAL_MAX_LEVELS:
+        raise ValueError(f"sigmas: expected 1 to {EVAL_MAX_LEVELS} levels in a 1-d tensor, got {tuple(sigmas.shape)}")
+    try:
+        _churn_rec(rec, clean)
+    except (TypeError, RuntimeError) as e:
+        raise ValueError(str(e)) from None
+    L = sigmas.numel()
+    if check_levels:
+        lo, hi = (int(v) for v in torch.aminmax(level))
+        if lo < 0 or hi >= L:
+            raise ValueError(f"level: values must be in [0, {L}), got [{lo}, {hi}]")
+    noisy = torch.empty_like(clean)
+    sigma = torch.empty(B, dtype=f32, device=clean.device)
+    _lib.call("edm_eval_diffuse", _p(clean), _p(ids), _p(level), _p(sigmas), L, _p(rec), B, clean.numel() // B,
+              _p(noisy), _p(sigma), _p(health(clean.device)), _stream())
+    return noisy, sigma
+
+
+def eval_sqerr(D, clean, out=None):
+    """se[b] = sum_j ((double)D_bj - (double)clean_bj)^2 in fp64, summed in an order that depends on the sample size
+    alone: the bits of se[b] do not depend on the batch.  D, clean: contiguous fp32 [B, ...], B <= 65535; out: a
+    contiguous fp64 [B] tensor (a slice of a result matrix) that is written, or None to allocate."""
+    _chk_eval(clean, f32, "clean")
+    if clean.dim() < 2 or clean.numel() == 0:
+        raise ValueError(f"clean: expected a non-empty [B, ...] tensor, got {tuple(clean.shape)}")
+    _chk_eval(D, f32, "D", clean.shape, clean.device)
+    B = clean.shape[0]
+    if B > 65535:
+        raise ValueError(f"eval_sqerr takes at most 65535 samples per call, got {B}")
+    if out is None:
+        out = torch.empty(B, dtype=torch.float64, device=clean.device)
+    else:
+        _chk_eval(out, torch.float64, "out", (B,), clean.device)
+    part = torch.empty(B * NLL_MAX_CHUNKS, dtype=torch.float64, device=clean.device)
+    _lib.call("edm_eval_sqerr", _p(D), _p(clean), B, clean.numel() // B, _p(part), _p(out), _p(health(clean.device)),
+              _stream())
+    return out
+
+
 def scale_f32(x, s):
     _chk(x, f32, "x")
     y = torch.empty_like(x)
