@@ -650,6 +650,30 @@ int edm_denormalize_u8(const float* x, void* out, long n, float scale, float off
 int edm_prediction_to_u8_nhwc(const float* pred, void* out, int B, int C, int H, int W, const float* mean,
                               const float* stdv, edm_stream_t stream);
 
+/* ---------------------------------------------------------------- exact nearest neighbours of uint8 images (csrc/neighbors.hip) */
+/* For every query row the k reference rows with the smallest key (d2, reference index), d2 = sum_j (q_j - r_j)^2 as an exact
+ * integer (int8 MFMA on the rows shifted by 128, int32 accumulation); ties in distance go to the lower index, so the result
+ * is unique and independent of tiling, split count and chunking.  Limits, status -1 otherwise: 1 <= D <= 32768 (then
+ * 65025 D < 2^31), 1 <= k <= 32, k <= R (k <= R - 1 with exclude_self), R <= 2^31 - 128.
+ * edm_u8_knn_splits: the number of shares of the R axis the library would give a Q x R search (host logic only).
+ * edm_u8_norms: norms[row] = sum_j (x_j - 128)^2 of x u8 [n_rows][D], the row norms edm_u8_knn_partial takes; once per set.
+ * edm_u8_knn_partial: queries u8 [Q][D], refs u8 [R][D], row-contiguous at any byte alignment (16-byte loads when both bases
+ *   are 16-byte aligned and D % 16 == 0, element loads otherwise; same results), qnorms [Q] and rnorms [R] their
+ *   edm_u8_norms.  Writes keys [splits][Q][k]: uint64 d2 << 32 | (ref_base + reference row), each list ascending, unused
+ *   slots all-ones.  `splits` is the caller's choice in [1, 1024].  exclude_self skips the reference whose reported index
+ *   equals the query row.  partial != 0 waives k <= R for a chunk of a larger reference set that the caller has checked as
+ *   a whole.  Further limits: Q <= 65535 * 128, ref_base + R <= 2^31 - 128 (row numbers of the last tile stay ints).
+ * edm_knn_merge: keys [n_lists][Q][k] (the splits of one call, or of every chunk of a chunked search, end to end) ->
+ *   dist uint32 [Q][k], idx int32 [Q][k], ascending by key.  Each query needs k non-empty keys across its lists.  No atomics
+ *   anywhere; every output element is written by ordinary stores. */
+int edm_u8_knn_splits(long Q, long R);
+int edm_u8_norms(const void* x, long n_rows, int D, int* norms, edm_stream_t stream);
+int edm_u8_knn_partial(const void* queries, const void* refs, long Q, long R, int D, int k, int exclude_self, long ref_base,
+                       int partial, int splits, const int* qnorms, const int* rnorms, unsigned long long* keys,
+                       edm_stream_t stream);
+int edm_knn_merge(const unsigned long long* keys, int n_lists, long Q, int k, unsigned* dist, int* idx,
+                  edm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -157,6 +157,11 @@ SIGNATURES = {
     "edm_u8_gather_augment_normalize": [P, P, P, I, I, I, I, L, F, F, I, U64, U, U64, I, P, P],
     "edm_denormalize_u8": [P, P, L, F, F, P],
     "edm_prediction_to_u8_nhwc": [P, P, I, I, I, I, P, P, P],
+    # neighbors.hip
+    "edm_u8_knn_splits": [L, L],
+    "edm_u8_norms": [P, L, I, P, P],
+    "edm_u8_knn_partial": [P, P, L, L, I, I, I, L, I, I, P, P, P, P],
+    "edm_knn_merge": [P, I, L, I, P, P, P],
 }
 # include/tinyedm_hip_diag.h: tools-only entry points, bound on demand by call()
 DIAG_SIGNATURES = {
@@ -170,7 +175,8 @@ _RET = {"edm_last_error": ctypes.c_char_p, "edm_v6_persistent_launches": ctypes.
         "edm_skip_gate_wgrad_multi_table_bytes": ctypes.c_long, "edm_skip_gate_fwd_multi_table_bytes": ctypes.c_long, "edm_skip_gate_bwd_multi_table_bytes": ctypes.c_long,
         "edm_conv_wgrad_1x1_group_table_bytes": ctypes.c_long, "edm_wgrad_finish_multi_table_bytes": ctypes.c_long}
 _NO_STATUS = {"edm_skip_gate_bwd_multi_table_bytes", "edm_skip_gate_fwd_multi_table_bytes", "edm_v6_persistent_launches", "edm_conv3x3_fold_supported", "edm_conv_plan", "edm_skip_gate_wgrad_multi_table_bytes", "edm_version", "edm_graph_replay_safe", "edm_last_error", "edm_conv_wgrad_nsplit", "edm_conv_wgrad_1x1_nsplit", "edm_conv_wgrad_1x1_nsplit_grouped", "edm_wgrad3_workspace", "edm_wgrad3_table_bytes", "edm_wgrad3_max_layers",
-              "edm_conv_wgrad_1x1_group_table_bytes", "edm_wgrad_finish_multi_table_bytes", "edm_attention_qkv_supported"}
+              "edm_conv_wgrad_1x1_group_table_bytes", "edm_wgrad_finish_multi_table_bytes", "edm_attention_qkv_supported",
+              "edm_u8_knn_splits"}
 
 _lib = None
 

@@ -2447,3 +2447,85 @@ def prediction_to_u8_nhwc(pred, mean, std):
     out = torch.empty(B, H, W, C, device=pred.device, dtype=torch.uint8)
     _lib.call("edm_prediction_to_u8_nhwc", _p(pred), _p(out), B, C, H, W, _p(mean), _p(std), _stream())
     return out
+
+
+# ------------------------------------------------------------------ exact nearest neighbours (csrc/neighbors.hip)
+KNN_MAX_K = 32
+KNN_MAX_D = 32768            # 65025 * D < 2^31: every distance fits the high word of a key
+KNN_MAX_SPLITS = 1024
+KNN_MAX_Q = 65535 * 128      # one grid row per 128 queries
+KNN_MAX_R = 2 ** 31 - 128    # row numbers of the last 128-reference tile stay 32-bit ints
+
+
+def _knn_rows(t, name):
+    _chk(t, torch.uint8, name)
+    if t.dim() < 2 or t.numel() == 0:
+        raise ValueError(f"{name}: expected a non-empty [N, ...] tensor, got {tuple(t.shape)}")
+    return t.view(t.shape[0], -1)
+
+
+def knn_check(Q, R, D, k, exclude_self=False):
+    """the limits of a search of Q queries against R references of D elements, as the library states them"""
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"u8_knn: k must be an integer in [1, {KNN_MAX_K}], got {k!r}")
+    if not 1 <= D <= KNN_MAX_D:
+        raise ValueError(f"u8_knn: rows must hold 1 to {KNN_MAX_D} elements, got {D}")
+    if not 1 <= Q <= KNN_MAX_Q:
+        raise ValueError(f"u8_knn: expected 1 to {KNN_MAX_Q} queries, got {Q}")
+    if not 1 <= R <= KNN_MAX_R:
+        raise ValueError(f"u8_knn: expected 1 to 2^31 - 128 references, got {R}")
+    if k > R - (1 if exclude_self else 0):
+        raise ValueError(f"u8_knn: k = {k} needs at least that many references"
+                         f"{' besides the query itself' if exclude_self else ''}, got R = {R}")
+
+
+def u8_knn_splits(Q, R) -> int:
+    """the split count of the R axis the library picks for a Q x R search"""
+    return int(_lib.call("edm_u8_knn_splits", int(Q), int(R)))
+
+
+def u8_knn(queries, refs, k, exclude_self=False, splits=None, *, ref_chunk=None, out=None):
+    """The k nearest rows of refs (uint8 [R, ...]) for every row of queries (uint8 [Q, ...], same trailing shape; inputs of
+    any rank >= 2 are taken as [N, D]) by exact squared pixel distance, ties to the lower index ->
+    (dist int64 [Q, k], idx int64 [Q, k]), ascending by (dist, idx).  exclude_self: refs is the query set itself and row i
+    is not its own neighbour.  splits forces the number of shares of the R axis (None: the library's plan), ref_chunk
+    searches the references that many rows at a time (None: all at once); every share of every chunk leaves a sorted key
+    list and one merge launch folds them, so the result depends on neither.  out=(uint32 [Q, k], int32 [Q, k]): the
+    kernel's own result types are written there and returned."""
+    q2, r2 = _knn_rows(queries, "queries"), _knn_rows(refs, "refs")
+    if queries.shape[1:] != refs.shape[1:]:
+        raise ValueError(f"u8_knn: queries {tuple(queries.shape[1:])} and refs {tuple(refs.shape[1:])} differ in shape")
+    if refs.device != queries.device:
+        raise ValueError(f"u8_knn: queries on {queries.device}, refs on {refs.device}")
+    (Q, D), R = q2.shape, r2.shape[0]
+    knn_check(Q, R, D, k, exclude_self)
+    if ref_chunk is not None and (isinstance(ref_chunk, bool) or not isinstance(ref_chunk, int) or ref_chunk < 1):
+        raise ValueError(f"u8_knn: ref_chunk must be None or an integer >= 1, got {ref_chunk!r}")
+    chunk = R if ref_chunk is None else min(ref_chunk, R)
+    bounds = [(a, min(a + chunk, R)) for a in range(0, R, chunk)]
+    if splits is None:
+        shares = [u8_knn_splits(Q, b - a) for a, b in bounds]
+    elif isinstance(splits, bool) or not isinstance(splits, int) or not 1 <= splits <= KNN_MAX_SPLITS:
+        raise ValueError(f"u8_knn: splits must be an integer in [1, {KNN_MAX_SPLITS}], got {splits!r}")
+    else:
+        shares = [splits] * len(bounds)
+    dev = queries.device
+    if out is None:
+        dist = torch.empty(Q, k, dtype=torch.uint32, device=dev)
+        idx = torch.empty(Q, k, dtype=torch.int32, device=dev)
+    else:
+        dist, idx = out
+        _chk(dist, torch.uint32, "out[0]", (Q, k))
+        _chk(idx, torch.int32, "out[1]", (Q, k))
+    norms = torch.empty(Q + R, dtype=torch.int32, device=dev)
+    qn, rn = norms[:Q], norms[Q:]
+    _lib.call("edm_u8_norms", _p(q2), Q, D, _p(qn), _stream())
+    _lib.call("edm_u8_norms", _p(r2), R, D, _p(rn), _stream())
+    keys = torch.empty(sum(shares), Q, k, dtype=torch.uint64, device=dev)
+    at = 0
+    for (a, b), s in zip(bounds, shares):
+        _lib.call("edm_u8_knn_partial", _p(q2), _p(r2[a:b]), Q, b - a, D, k, int(bool(exclude_self)), a,
+                  int(len(bounds) > 1), s, _p(qn), _p(rn[a:b]), _p(keys[at:at + s]), _stream())
+        at += s
+    _lib.call("edm_knn_merge", _p(keys), at, Q, k, _p(dist), _p(idx), _stream())
+    return (dist, idx) if out is not None else (dist.to(torch.int64), idx.to(torch.int64))
