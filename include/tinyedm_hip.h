@@ -644,6 +644,18 @@ int edm_u8_gather_augment_normalize(const void* data, const long* index, float* 
                                     long n_images, float mean, float stdv, int flip, unsigned long long seed,
                                     unsigned epoch, unsigned long long aug_thr, int aug_ops, float* aug,
                                     edm_stream_t stream);
+/* edm_u8_gather_augment_normalize followed by the continuous ops of the same pipe: zoom, rotate, stretch, shift (the
+ * project's own definition: 2x upsampling with the sym6 low-pass taps over a reflected border, a bilinear warp on the 2x
+ * grid, 2x downsampling with the same taps; DESIGN.md, "Continuous augmentation"; draws and labels at
+ * k_u8_gather_warp_normalize in csrc/data.hip).  warp_ops: bit 0 zoom, 1 rotate, 2 stretch, 3 shift, enabled per sample
+ * like the exact ops.  aug [B][13] fp32: the six labels above, then (n_s, cos(theta) - 1, sin(theta), n_a cos(phi),
+ * n_a sin(phi), n_x, n_y).  theta [B][6] fp32 (may be null) receives each sample's 2x3 matrix on the 2x grid.  A sample with
+ * no continuous op enabled is edm_u8_gather_augment_normalize's bit for bit.  H or W outside 2 .. 64, or rot90 with
+ * H != W: status -3 (unsupported), nothing is launched.  An out-of-range index entry skips that sample's rows. */
+int edm_u8_gather_augment_warp_normalize(const void* data, const long* index, float* out, int B, int C, int H, int W,
+                                         long n_images, float mean, float stdv, int flip, unsigned long long seed,
+                                         unsigned epoch, unsigned long long aug_thr, int aug_ops, int warp_ops,
+                                         float* aug, float* theta, edm_stream_t stream);
 /* (x*scale + offset).clip(0,255) -> uint8, layout preserved (cifar10datamodule.py:34-35: scale 127.5, offset 128) */
 int edm_denormalize_u8(const float* x, void* out, long n, float scale, float offset, edm_stream_t stream);
 /* clamp(pred*std[c]*2 + mean[c], 0, 1)*255 -> uint8 NHWC (callbacks.py:126-156, PreditionWriter) */

@@ -155,6 +155,7 @@ SIGNATURES = {
     # data.hip
     "edm_u8_gather_normalize": [P, P, P, I, I, I, I, L, F, F, I, U64, U, P],
     "edm_u8_gather_augment_normalize": [P, P, P, I, I, I, I, L, F, F, I, U64, U, U64, I, P, P],
+    "edm_u8_gather_augment_warp_normalize": [P, P, P, I, I, I, I, L, F, F, I, U64, U, U64, I, I, P, P, P],
     "edm_denormalize_u8": [P, P, L, F, F, P],
     "edm_prediction_to_u8_nhwc": [P, P, I, I, I, I, P, P, P],
     # neighbors.hip

@@ -201,10 +201,11 @@ class _ResidentLoader:
     (same permutation on every rank), each rank taking its `rank::world` share (DistributedSampler semantics)."""
 
     def __init__(self, data_u8, labels, batch_size, shuffle, flip, seed, mean, std, rank=None, world=None,
-                 augment_prob=0.0, augment_ops=()):
+                 augment_prob=0.0, augment_ops=(), augment_warp_ops=()):
         self.data, self.labels, self.batch_size = data_u8, labels, batch_size
         self.shuffle, self.flip, self.seed, self.mean, self.std = shuffle, flip, seed, mean, std
         self.augment_prob, self.augment_ops = float(augment_prob), tuple(augment_ops)
+        self.augment_warp_ops = tuple(augment_warp_ops)
         self.rank, self.world = _rank_world(rank, world)
         self.epoch = 0
 
@@ -217,6 +218,13 @@ class _ResidentLoader:
                             self.data.device)
         for bi in range(len(self)):
             idx = order[bi * self.batch_size:(bi + 1) * self.batch_size].contiguous()
+            if self.augment_prob > 0 and self.augment_warp_ops:     # the exact ops, then the continuous ones: 13 labels
+                x, aug = ops.u8_gather_augment_warp_normalize(self.data, idx, self.mean, self.std, flip=self.flip,
+                                                              seed=self.seed + 7919 * self.rank,
+                                                              epoch=self.epoch * 65536 + bi, p=self.augment_prob,
+                                                              ops=self.augment_ops, warp_ops=self.augment_warp_ops)
+                yield x, self.labels[idx], aug
+                continue
             if self.augment_prob > 0:       # same seed / epoch words as the flip; the draws have a counter tag of their own
                 x, aug = ops.u8_gather_augment_normalize(self.data, idx, self.mean, self.std, flip=self.flip,
                                                          seed=self.seed + 7919 * self.rank, epoch=self.epoch * 65536 + bi,
@@ -234,12 +242,16 @@ class AbstractDataModule:
     ignored: there are no worker processes).
 
     ``augment_prob`` / ``augment_ops`` (extensions of the image datamodules): non-leaking augmentation of the TRAIN loader,
-    each op applied per sample with probability augment_prob; its batches are then (x, y, augment_labels (B, 6))."""
+    each op applied per sample with probability augment_prob; its batches are then (x, y, augment_labels (B, 6)).
+    ``augment_warp_ops`` (default none): the continuous ops of the same pipe -- zoom, rotate, stretch, shift -- applied after
+    the exact ones with the same probability; the batches then carry 13 labels (``Embedding(augment_dim=13)``)."""
 
     AUGMENT_OPS = ("xflip", "yflip", "translate", "rot90")
+    AUGMENT_WARP_OPS = ("zoom", "rotate", "stretch", "shift")
+    AUGMENT_WARP_SIZES = (2, 64)        # the resampling kernel's range of image sides
 
     def __init__(self, data_dir, batch_size: int, num_workers: int = 0, device: str | None = None, seed: int = 42,
-                 augment_prob: float = 0.0, augment_ops=AUGMENT_OPS):
+                 augment_prob: float = 0.0, augment_ops=AUGMENT_OPS, augment_warp_ops=()):
         self.data_dir, self.batch_size, self.num_workers = data_dir, batch_size, num_workers
         self.device, self.seed = device, seed
         self.augment_prob, self.augment_ops = float(augment_prob), tuple(augment_ops)
@@ -248,6 +260,10 @@ class AbstractDataModule:
         unknown = [o for o in self.augment_ops if o not in self.AUGMENT_OPS]
         if unknown:
             raise ValueError(f"unknown augment_ops {unknown}: expected a subset of {self.AUGMENT_OPS}")
+        self.augment_warp_ops = tuple(augment_warp_ops)
+        unknown = [o for o in self.augment_warp_ops if o not in self.AUGMENT_WARP_OPS]
+        if unknown:
+            raise ValueError(f"unknown augment_warp_ops {unknown}: expected a subset of {self.AUGMENT_WARP_OPS}")
         self.train_dataset = self.val_dataset = self.test_dataset = None
         self.mean, self.std, self.flip = 0.5, 0.5, False
 
@@ -260,6 +276,10 @@ class AbstractDataModule:
     def _resident(self, x, y):
         if self.augment_prob > 0 and "rot90" in self.augment_ops and x.shape[-2] != x.shape[-1]:
             raise ValueError(f"augment_ops: rot90 needs square images, the set is {x.shape[-2]} x {x.shape[-1]}")
+        lo, hi = self.AUGMENT_WARP_SIZES
+        if self.augment_prob > 0 and self.augment_warp_ops and not all(lo <= n <= hi for n in x.shape[-2:]):
+            raise ValueError(f"augment_warp_ops: images of {lo} .. {hi} pixels a side only, the set is "
+                             f"{x.shape[-2]} x {x.shape[-1]}")
         dev = self._dev()
         return torch.from_numpy(np.ascontiguousarray(x)).to(dev), torch.from_numpy(y).to(dev)
 
@@ -267,7 +287,8 @@ class AbstractDataModule:
         if ds is None:
             raise RuntimeError("call setup() first")
         return _ResidentLoader(ds[0], ds[1], self.batch_size, shuffle, flip, self.seed, self.mean, self.std,
-                               augment_prob=self.augment_prob if augment else 0.0, augment_ops=self.augment_ops)
+                               augment_prob=self.augment_prob if augment else 0.0, augment_ops=self.augment_ops,
+                               augment_warp_ops=self.augment_warp_ops)
 
     def train_dataloader(self):
         return self._loader(self.train_dataset, True, self.flip, augment=True)
@@ -291,8 +312,8 @@ class CIFAR10DataModule(AbstractDataModule):
 
     def __init__(self, data_dir: str = "datasets/cifar", image_size: int = 32, batch_size: int = 16, num_workers: int = 16,
                  device: str | None = None, seed: int = 42, augment_prob: float = 0.0,
-                 augment_ops=AbstractDataModule.AUGMENT_OPS):
-        super().__init__(data_dir, batch_size, num_workers, device, seed, augment_prob, augment_ops)
+                 augment_ops=AbstractDataModule.AUGMENT_OPS, augment_warp_ops=()):
+        super().__init__(data_dir, batch_size, num_workers, device, seed, augment_prob, augment_ops, augment_warp_ops)
         if image_size != 32:
             raise ValueError("CIFAR10DataModule: only the native image_size 32 is supported")
         self.img_size, self.flip = image_size, True
@@ -318,8 +339,8 @@ class MNISTDataModule(AbstractDataModule):
 
     def __init__(self, batch_size: int, num_workers: int = 0, image_size: int = 28, data_dir: str = "datasets/mnist",
                  device: str | None = None, seed: int = 42, augment_prob: float = 0.0,
-                 augment_ops=AbstractDataModule.AUGMENT_OPS):
-        super().__init__(data_dir, batch_size, num_workers, device, seed, augment_prob, augment_ops)
+                 augment_ops=AbstractDataModule.AUGMENT_OPS, augment_warp_ops=()):
+        super().__init__(data_dir, batch_size, num_workers, device, seed, augment_prob, augment_ops, augment_warp_ops)
         if image_size != 28:
             raise ValueError("MNISTDataModule: only the native image_size 28 is supported")
 

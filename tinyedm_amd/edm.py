@@ -133,8 +133,9 @@ class EDM(LightningModule):
         augment_labels = augment[0] if augment else None
         if augment_labels is not None and getattr(self.embedding, "augment_dim", 0) == 0:
             # augmenting without telling the network is the leak non-leaking augmentation exists to prevent
+            width = augment_labels.shape[-1] if getattr(augment_labels, "ndim", 0) == 2 else "<label width>"
             raise ValueError("EDM: the batch carries augment labels but embedding.augment_dim is 0: build the Embedding "
-                             "with augment_dim=6, or set the datamodule's augment_prob to 0")
+                             f"with augment_dim={width}, or set the datamodule's augment_prob to 0")
         class_label = class_label if self.conditional else None
         noisy_image, sigma = self.diffuser(clean_image)
         if augment_labels is None:

@@ -2430,6 +2430,46 @@ def u8_gather_augment_normalize(data, index, mean=0.5, std=0.5, flip=False, seed
     return out, aug
 
 
+AUGMENT_WARP_OPS = ("zoom", "rotate", "stretch", "shift")   # bit i of the warp mask: the continuous ops, after the exact ones
+AUGMENT_DIM_WARP = 13       # AUGMENT_DIM + (n_s, cos(theta) - 1, sin(theta), n_a cos(phi), n_a sin(phi), n_x, n_y)
+AUGMENT_WARP_MAX_SIZE = 64  # the resampling kernel keeps a plane and its 2x grid in LDS
+
+
+def augment_warp_mask(names) -> int:
+    """continuous-op names -> the 4-bit warp mask of edm_u8_gather_augment_warp_normalize"""
+    mask = 0
+    for n in names:
+        if n not in AUGMENT_WARP_OPS:
+            raise ValueError(f"unknown continuous augmentation op {n!r}: expected a subset of {AUGMENT_WARP_OPS}")
+        mask |= 1 << AUGMENT_WARP_OPS.index(n)
+    return mask
+
+
+def u8_gather_augment_warp_normalize(data, index, mean=0.5, std=0.5, flip=False, seed=0, epoch=0, *, p=0.0,
+                                     ops=AUGMENT_OPS, warp_ops=AUGMENT_WARP_OPS, return_theta=False):
+    """u8_gather_augment_normalize followed by the continuous ops of the EDM pipe (zoom, rotate, stretch, shift: 2x
+    upsampling, a bilinear warp, 2x downsampling; DESIGN.md, "Continuous augmentation") -> (x fp32 (B,C,H,W), aug fp32
+    (B,13)), with return_theta also each sample's 2x3 matrix on the 2x grid, fp32 (B,6).  Every op of `ops` and `warp_ops`
+    is applied per sample with probability p; a sample with no continuous op is u8_gather_augment_normalize's bit for bit."""
+    _chk(data, torch.uint8, "data")
+    _chk(index, torch.int64, "index")
+    if data.dim() != 4 or index.dim() != 1:
+        raise ValueError("u8_gather_augment_warp_normalize: data must be (N,C,H,W), index (B,)")
+    if not 0.0 <= float(p) <= 1.0:
+        raise ValueError(f"u8_gather_augment_warp_normalize: p must be in [0, 1], got {p}")
+    mask = augment_op_mask(ops) if not isinstance(ops, int) else int(ops)
+    wmask = augment_warp_mask(warp_ops) if not isinstance(warp_ops, int) else int(warp_ops)
+    N, C, H, W = data.shape
+    B = index.shape[0]
+    out = torch.empty(B, C, H, W, device=data.device, dtype=f32)
+    aug = torch.empty(B, AUGMENT_DIM_WARP, device=data.device, dtype=f32)
+    theta = torch.empty(B, 6, device=data.device, dtype=f32) if return_theta else None
+    _lib.call("edm_u8_gather_augment_warp_normalize", _p(data), _p(index), _p(out), B, C, H, W, N, float(mean), float(std),
+              int(bool(flip)), int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF, label_drop_threshold(p), mask,
+              wmask, _p(aug), _p(theta) if return_theta else None, _stream())
+    return (out, aug, theta) if return_theta else (out, aug)
+
+
 def denormalize_u8(x, scale=127.5, offset=128.0):
     """fp32 tensor -> uint8, same shape: (x*scale+offset).clip(0,255) truncated."""
     _chk(x, f32, "x")
