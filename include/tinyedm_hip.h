@@ -367,6 +367,36 @@ int edm_conv_out_fwd(const void* x, const float* w_hat, const float* gain_out, c
 int edm_conv_out_bwd(const void* x, const float* w_hat, const float* gain_out, const float* Fraw, const float* dD,
                      const float* sigma, int sigma_stride, float sigma_data, void* gx, float* gw_hat, float* ggain,
                      int B, int HW, int C, int Co, edm_stream_t stream);
+
+/* ---------------------------------------------------------------- the output end in factored form (csrc/tail_lowrank.hip)
+ * conv_out's input gradient g_h = dF . Wout has rank Co <= 8 per pixel; the last decoder block's second 3x3 conv takes its
+ * dgrad and its weight gradient from dF (fp32 NCHW [B, Co, H, W]) instead of the C-channel g_h.  t = 3 ky + kx,
+ * d(t) = (ky - 1, kx - 1); zero padding; any H, W; C % 8 == 0.  (edm_conv_out_bwd with gw_hat == NULL writes gx only.) */
+/* dF = dD * c_out(b) * gain_out; aux (nullable) = dD * c_out(b) * Fraw, whose sum is d loss / d gain_out */
+int edm_lowrank_df(const float* dD, const float* Fraw, const float* gain_out, const float* sigma, int sigma_stride,
+                   float sigma_data, float* dF, float* aux, int B, int Co, int HW, edm_stream_t stream);
+/* ga2 (bf16 NHWC, nullable when r1 is given) = scale * sum_t sum_o dF[p - d(t), o] * Wc[o][t][c], Wc fp32 [Co][9][C].
+ * r1 != NULL: edm_conv3x3_modbwd's epilogue on ga2 in registers (gr, raw modulation sums += into zero-filled gm rows). */
+int edm_lowrank_dgrad3x3(const float* dF, const float* Wc, float scale, void* ga2, const void* r1, const float* lin,
+                         long lin_stride, const float* gain, void* gr, float* gm, long gm_stride, float pdrop,
+                         unsigned long long seed, unsigned sub, unsigned step, int u_marked, int B, int H, int W, int C,
+                         int Co, const void* dyn, edm_stream_t stream);
+/* G (fp32 [Co][taps][C], overwritten) = sum_p dF[p, o] * X[p + d(t), c]; X bf16 NHWC, taps 1 or 9.  Deterministic (workgroup
+ * partials in ws, edm_lowrank_wgrad_workspace(C, Co, taps) floats, added in a fixed order; no atomics).
+ * aux (nullable, like dF): *aux_out += sum of aux. */
+long edm_lowrank_wgrad_workspace(int C, int Co, int taps);
+/* 1 when the LDS tables of edm_lowrank_wgrad(taps) -- and, taps == 9, of the fused edm_lowrank_dgrad3x3 -- fit for maps of
+ * width W with C channels (60 KB: e.g. Co <= 5 at C = 256); the entry points refuse other shapes.  Host logic only. */
+int edm_lowrank_supported(int C, int Co, int W, int taps);
+int edm_lowrank_wgrad(const float* dF, const void* X, int taps, const float* aux, float* G, float* aux_out, float* ws,
+                      long ws_floats, int B, int H, int W, int C, int Co, edm_stream_t stream);
+/* Wc[o][t][i] = sum_c Wout_hat[o, c] * float(wd[taps - 1 - t][i][c]): wd = the plain bf16 dgrad pack [taps][I][O] of the conv */
+int edm_lowrank_expand_wc(const float* wout_hat, const void* wd, float* Wc, int Co, int O, int I, int taps,
+                          edm_stream_t stream);
+/* slab[t][c][i] = scale * sum_o Wout_hat[o, c] * G[o][t][i]: one slab [1][taps][O][Ipad] for edm_wgrad_finish(_multi) */
+int edm_lowrank_expand_slab(const float* wout_hat, const float* G, float* slab, float scale, int Co, int O, int I,
+                            int Ipad, int taps, edm_stream_t stream);
+
 int edm_nchw_to_nhwc_bf16(const float* x, void* y, int B, int C, int HW, edm_stream_t stream);
 int edm_nhwc_bf16_to_nchw(const void* x, float* y, int B, int C, int HW, edm_stream_t stream);
 

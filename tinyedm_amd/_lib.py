@@ -55,6 +55,14 @@ SIGNATURES = {
     "edm_conv_out_bwd": [P, P, P, P, P, P, I, F, P, P, P, I, I, I, I, P],
     "edm_nchw_to_nhwc_bf16": [P, P, I, I, I, P],
     "edm_nhwc_bf16_to_nchw": [P, P, I, I, I, P],
+    # tail_lowrank.hip
+    "edm_lowrank_df": [P, P, P, P, I, F, P, P, I, I, I, P],
+    "edm_lowrank_dgrad3x3": [P, P, F, P, P, P, L, P, P, P, L, F, U64, U, U, I, I, I, I, I, I, P, P],
+    "edm_lowrank_wgrad_workspace": [I, I, I],
+    "edm_lowrank_supported": [I, I, I, I],
+    "edm_lowrank_wgrad": [P, P, I, P, P, P, P, L, I, I, I, I, I, P],
+    "edm_lowrank_expand_wc": [P, P, P, I, I, I, I, P],
+    "edm_lowrank_expand_slab": [P, P, P, F, I, I, I, I, I, P],
     # conv_igemm.hip / conv_wgrad.hip
     "edm_conv_igemm": [P, P, P, P, F, F, I, I, I, I, I, I, P],
     "edm_conv_igemm_v2": [P, P, P, P, F, F, I, I, I, I, I, I, P],
@@ -172,10 +180,10 @@ DIAG_SIGNATURES = {
     "edm_wgrad3_plan_ksplit": [P, I, P],
     "edm_v6_persistent_launches": [],
 }
-_RET = {"edm_last_error": ctypes.c_char_p, "edm_v6_persistent_launches": ctypes.c_long, "edm_wgrad3_workspace": ctypes.c_long, "edm_wgrad3_table_bytes": ctypes.c_long,
+_RET = {"edm_last_error": ctypes.c_char_p, "edm_lowrank_wgrad_workspace": ctypes.c_long, "edm_v6_persistent_launches": ctypes.c_long, "edm_wgrad3_workspace": ctypes.c_long, "edm_wgrad3_table_bytes": ctypes.c_long,
         "edm_skip_gate_wgrad_multi_table_bytes": ctypes.c_long, "edm_skip_gate_fwd_multi_table_bytes": ctypes.c_long, "edm_skip_gate_bwd_multi_table_bytes": ctypes.c_long,
         "edm_conv_wgrad_1x1_group_table_bytes": ctypes.c_long, "edm_wgrad_finish_multi_table_bytes": ctypes.c_long}
-_NO_STATUS = {"edm_skip_gate_bwd_multi_table_bytes", "edm_skip_gate_fwd_multi_table_bytes", "edm_v6_persistent_launches", "edm_conv3x3_fold_supported", "edm_conv_plan", "edm_skip_gate_wgrad_multi_table_bytes", "edm_version", "edm_graph_replay_safe", "edm_last_error", "edm_conv_wgrad_nsplit", "edm_conv_wgrad_1x1_nsplit", "edm_conv_wgrad_1x1_nsplit_grouped", "edm_wgrad3_workspace", "edm_wgrad3_table_bytes", "edm_wgrad3_max_layers",
+_NO_STATUS = {"edm_lowrank_wgrad_workspace", "edm_lowrank_supported", "edm_skip_gate_bwd_multi_table_bytes", "edm_skip_gate_fwd_multi_table_bytes", "edm_v6_persistent_launches", "edm_conv3x3_fold_supported", "edm_conv_plan", "edm_skip_gate_wgrad_multi_table_bytes", "edm_version", "edm_graph_replay_safe", "edm_last_error", "edm_conv_wgrad_nsplit", "edm_conv_wgrad_1x1_nsplit", "edm_conv_wgrad_1x1_nsplit_grouped", "edm_wgrad3_workspace", "edm_wgrad3_table_bytes", "edm_wgrad3_max_layers",
               "edm_conv_wgrad_1x1_group_table_bytes", "edm_wgrad_finish_multi_table_bytes", "edm_attention_qkv_supported",
               "edm_u8_knn_splits"}
 

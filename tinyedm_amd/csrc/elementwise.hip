@@ -1668,7 +1668,7 @@ __global__ void k_conv_out_bwd_w(const bf16* __restrict__ x, const float* __rest
   }
   if (c8 == 0) atomicAdd(ggain, gg);
 }
-// gw_hat [Co,C] and ggain are accumulated (+=): caller zero-fills.
+// gw_hat [Co,C] and ggain are accumulated (+=): caller zero-fills.  gw_hat == NULL: gx only.
 extern "C" int edm_conv_out_bwd(const void* x, const float* w_hat, const float* gain_out, const float* Fraw,
                                 const float* dD, const float* sigma, int sigma_stride, float sigma_data, void* gx,
                                 float* gw_hat, float* ggain, int B, int HW, int C, int Co, hipStream_t st) {
@@ -1679,7 +1679,7 @@ extern "C" int edm_conv_out_bwd(const void* x, const float* w_hat, const float* 
   hipLaunchKernelGGL(k_conv_out_bwd_x, dim3(grid_for(n8, 256)), dim3(256), 0, st, dD, w_hat, gain_out, sigma,
                      sigma_stride, sigma_data, (bf16*)gx, HW, C, Co, n8);
   EDM_CHECK_LAUNCH("conv_out_bwd_x");
-  {
+  if (gw_hat) {     // (NULL: the input gradient alone -- the weight and gain gradients come from edm_lowrank_wgrad)
     const int CL = C / 8;
     EDM_REQUIRE(CL <= 256, "conv_out_bwd: C=%d too large", C);
     int block = (256 / CL) * CL, PS = block / CL;
@@ -1689,8 +1689,8 @@ extern "C" int edm_conv_out_bwd(const void* x, const float* w_hat, const float* 
     hipLaunchKernelGGL(k_conv_out_bwd_w, dim3(cdiv(npix, PIXW)), dim3(block), (size_t)PS * Co * C * sizeof(float), st,
                        (const bf16*)x, dD, Fraw, gain_out, sigma, sigma_stride, sigma_data, gw_hat, ggain, HW, C, Co,
                        npix, PIXW);
+    EDM_CHECK_LAUNCH("conv_out_bwd_w");
   }
-  EDM_CHECK_LAUNCH("conv_out_bwd_w");
   return EDM_OK;
 }
 

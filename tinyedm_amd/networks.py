@@ -151,7 +151,8 @@ W3_GROUP = max(0, min(ops.W3_MAX_LAYERS, int(os.environ.get("EDM_W3_GROUP", "16"
 # Data-parallel runs: the LAST grouped launch of a backward pass finishes at the very end of it, so the all-reduce of its
 # layers' gradients has nothing left to hide under except the optimizer.  W3_TAIL > 0 cuts the groups so that the final one
 # holds at most that many layers (CIFAR-10: 43 layers as 16 + 16 + 7 + 4 instead of 16 + 16 + 11: 9.4 MB = 6.6 % of the
-# gradient bytes left for the exposed tail instead of 26 MB) at the price of one more launch.  The number of 3x3 layers of
+# gradient bytes left for the exposed tail instead of 26 MB; with TAIL_LOWRANK one layer leaves the groups: 42 layers as
+# 16 + 16 + 6 + 4 instead of 16 + 16 + 10) at the price of one more launch.  The number of 3x3 layers of
 # a pass is learned from the previous pass.  Set by ddp.GradReducer when more than one rank takes part (EDM_W3_TAIL overrides;
 # 0 = off: one GPU keeps the three launches).
 W3_TAIL = max(0, int(os.environ.get("EDM_W3_TAIL", "0")))
@@ -173,6 +174,12 @@ SG_BWD_MULTI = os.environ.get("EDM_SG_BWD_MULTI", "1") != "0"   # ... and their 
 SG_DEFER = os.environ.get("EDM_SG_DEFER", "1") != "0"
 _sg_pending = {}            # device index -> [(ScaleLong module, ws, mean, R)]
 _w3_pending = {}            # device index -> [(mod, x, dy, scale)] 3x3 layers waiting for their grouped launch
+# The output end in factored form (csrc/tail_lowrank.hip): conv_out's input gradient g_h = dF . Wout has rank
+# Co <= 8 per pixel, so the last decoder block takes the dgrad (+ modulation backward) and the weight gradient of its second
+# 3x3 conv from dF instead of multiplying the C-channel g_h on the MFMA kernels, and conv_out's own weight gradient is the
+# one-tap form of the same reduction.  Arena gradients only.  EDM_TAIL_LOWRANK=0: the launches of before (A/B runs, bisecting).
+TAIL_LOWRANK = os.environ.get("EDM_TAIL_LOWRANK", "1") != "0"
+_tail_slot = {}             # device index -> (dF, Wout_hat, gx): left by _ConvOutFn.backward for the consumer of ITS gx only
 _fin_pending = {}           # device index -> [(slabs, w, perm, taps, I, scale)] small weight gradients to finish
 
 
@@ -254,6 +261,7 @@ def _backward_end(key):
     """End of a backward pass on device `key`: flush the last partial group, then make the stream that ran the
     backward wait for the auxiliary stream (the optimizer reads what the weight-gradient kernels wrote)."""
     _bwd_end_queued.discard(key)
+    _tail_slot.pop(key, None)
     if key in _w3_seen:
         _w3_total[key] = _w3_seen.pop(key)
     _flush_sg(key)
@@ -277,6 +285,7 @@ def _queue_backward_end(device):
 def reset_backward_state():
     """Forget deferred work of a backward pass that did not complete (an exception inside autograd leaves its
     end-of-backward callback unrun).  Called at the start of every Denoiser forward."""
+    _tail_slot.clear()
     if _bwd_end_queued or _w3_pending or _fin_pending or _w1_pending or _sg_pending:
         _bwd_end_queued.clear()
         for items in _sg_pending.values():
@@ -341,6 +350,18 @@ def _wgrad(mod, x, dy, taps, scale=1.0):
         _queue_backward_end(w.device)
         return None
     return mod.finish_grad(ops.conv_wgrad(x, dy, taps), scale=scale)
+
+
+def _wgrad_lowrank(mod, x, dF, wout_hat, scale):
+    """Weight gradient of the 3x3 conv `mod` whose output gradient is dF . Wout (arena mode): the Co-channel reduction G
+    over x, expanded through Wout into ONE slab that the multi-tensor finish projects and accumulates.  The layer joins no
+    k_wgrad3 group and is not counted among the 3x3 layers of the pass (_w3_seen / _w3_total: W3_TAIL still cuts the last
+    group where it did); its parameter is deferred and its hooks run with the finish launch, like every small gradient."""
+    w = mod.weight
+    box = []
+    _run_on_side(w.device, lambda: box.append(ops.lowrank_expand_slab(wout_hat, ops.lowrank_wgrad(dF, x, 9)[0], scale)),
+                 (x, dF, wout_hat))
+    return mod.finish_grad(box[0])
 
 
 # bf16 tile of a weight-prep workgroup (rows x fan_in): 96 KB = 16 rows of a 256-channel 3x3 layer, two workgroups per CU
@@ -1071,7 +1092,28 @@ class _ResBlockFn(torch.autograd.Function):
         gdirect = gp.grad is not None and getattr(gp, "_edm_direct", False) and gp.grad.is_contiguous()
         ggain_out = gp.grad if gdirect else None
         deferred = False
-        if ops.FUSE_MOD and ops.IGEMM_VERSION == 0 and (gout.shape[1] * gout.shape[2]) % 32 == 0:
+        fused = ops.FUSE_MOD and ops.IGEMM_VERSION == 0 and (gout.shape[1] * gout.shape[2]) % 32 == 0
+        tail = None
+        if blk._tail_last:
+            # the slot is taken only by the consumer of the very tensor _ConvOutFn.backward returned, and emptied whatever
+            # happens here
+            slot = _tail_slot.pop(gout.device.index, None)
+            w2 = blk.conv_3x3_2.weight
+            if (slot is not None and slot[2].data_ptr() == gout.data_ptr() and slot[2].shape == gout.shape
+                    and w2.grad is not None and getattr(w2, "_edm_direct", False) and r1 is not None
+                    and wd2.dim() == 3 and not getattr(wd2, "_edm_frag", False)
+                    and ops.lowrank_supported(r1.shape[-1], slot[0].shape[1], r1.shape[2], 9)):
+                tail = slot[:2]
+        if tail is not None:
+            # g_h = dF . Wout has rank Co: conv2's dgrad as a Co -> C transposed conv with the modulation backward on its
+            # result in registers (csrc/tail_lowrank.hip; any H * W)
+            deferred = ctx.gm_view is not None and gdirect and (fused or MOD_DEFER_UNFUSED)
+            gr1, glin, ggain = ops.lowrank_dgrad3x3_modbwd(tail[0], ops.lowrank_expand_wc(tail[1], wd2), b, r1, lin, gain, pdrop,
+                                                             seed, sub, step, glin_out=glin_out, ggain_out=ggain_out, dyn=dyn,
+                                                             gm_out=ctx.gm_view if deferred else None, u_marked=ctx.u_marked)
+            if deferred:
+                gp._edm_deferred = True
+        elif fused:
             # conv2's dgrad with the modulation backward in its epilogue: ga2 never touches HBM.  With a shared gm buffer
             # (batched mode, arena gradients) the finish (glin = gm * gain, d loss / d gain) is NOT launched per block:
             # _EmbedAllFn.backward runs ONE edm_mod_finish_multi for all blocks; until then the gain's gradient is not
@@ -1097,7 +1139,10 @@ class _ResBlockFn(torch.autograd.Function):
             if not deferred:
                 for hook in getattr(gp, "_edm_hooks", ()):
                     hook(gp)
-        gw2 = _wgrad(blk.conv_3x3_2, a2, gout, 9, b)
+        if tail is not None:
+            gw2 = _wgrad_lowrank(blk.conv_3x3_2, a2, tail[0], tail[1], b)
+        else:
+            gw2 = _wgrad(blk.conv_3x3_2, a2, gout, 9, b)
         gwemb = gemb = gtoken = None
         if ctx.batched:
             gtoken = ops.zeros_f32((1,), gout.device) if ctx.has_token else None
@@ -1193,6 +1238,7 @@ class _BlockBase(nn.Module):
         self.embed = Linear(embedding_dim, out_channels)
         self.embed.weight._edm_late = True        # its gradient is written by _EmbedAllFn.backward, behind every block (ema.FlatArena)
         self.gain = nn.Parameter(torch.ones(()))
+        self._tail_last = False     # set by the Denoiser on the block whose output conv_out reads (TAIL_LOWRANK)
         _rng_sub_counter[0] += 1
         self.rng_sub = _rng_sub_counter[0]
 
@@ -1628,8 +1674,21 @@ class _ConvOutFn(torch.autograd.Function):
         # independent of the stream earlier (eager) steps ran on
         gp = ctx.den.gain_out
         gdirect = gp.grad is not None and getattr(gp, "_edm_direct", False) and gp.grad.is_contiguous()
-        gx, gwh, gg = ops.conv_out_bwd(x, wh, gain_out, Fraw, gD.contiguous().float(), sigma, ctx.den.sigma_data,
-                                       gg_out=gp.grad if gdirect else None)
+        w = ctx.den.conv_out.weight
+        dD = gD.contiguous().float()
+        if (TAIL_LOWRANK and w.grad is not None and getattr(w, "_edm_direct", False)
+                and ops.lowrank_supported(x.shape[-1], wh.shape[0], x.shape[2], 1)):
+            # dF once; weight and gain gradients from the one-tap low-rank reduction (deterministic: no atomics); the last
+            # decoder block finds (dF, Wout_hat) in the slot if -- and only if -- the gradient it receives is this gx
+            dF, aux = ops.lowrank_df(dD, Fraw, gain_out, sigma, ctx.den.sigma_data)
+            gx = ops.conv_out_bwd_x(wh, gain_out, dD, sigma, ctx.den.sigma_data, x.shape[-1])
+            G, gg = ops.lowrank_wgrad(dF, x, 1, aux=aux, aux_out=gp.grad if gdirect else None)
+            gwh = G.view(G.shape[0], G.shape[2])
+            _tail_slot[gx.device.index] = (dF, wh, gx)
+            _queue_backward_end(gx.device)      # (empties the slot if no block takes it)
+        else:
+            gx, gwh, gg = ops.conv_out_bwd(x, wh, gain_out, Fraw, dD, sigma, ctx.den.sigma_data,
+                                           gg_out=gp.grad if gdirect else None)
         if gdirect:
             gg = None
             for hook in getattr(gp, "_edm_hooks", ()):
@@ -1683,6 +1742,8 @@ class Denoiser(nn.Module):
         self.decoder_blocks = build_decoder_blocks(
             decoder_block_types, decoder_out_channels, skip_channels, embedding_dim=embedding_dim,
             dropout_rate=dropout_rate, add_factor=decoder_add_factor, num_heads=num_heads)
+        if len(self.decoder_blocks):
+            self.decoder_blocks[-1]._tail_last = True
 
         self.in_channels = in_channels
         self.out_channels = out_channels

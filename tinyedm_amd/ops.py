@@ -826,6 +826,143 @@ def conv_out_bwd(x, w_hat, gain_out, Fraw, dD, sigma, sigma_data, gg_out=None):
     return gx, gw, gg
 
 
+def conv_out_bwd_x(w_hat, gain_out, dD, sigma, sigma_data, C):
+    """the input gradient of conv_out alone (bf16 NHWC); the weight / gain gradients come from lowrank_wgrad"""
+    Co = w_hat.shape[0]
+    _chk(w_hat, f32, "w_hat", (Co, C))
+    _chk(dD, f32, "dD")
+    B, _, H, W = dD.shape
+    ss = _sigma_arg(sigma, B)
+    gx = torch.empty(B, H, W, C, device=dD.device, dtype=bf16)
+    _lib.call("edm_conv_out_bwd", None, _p(w_hat), _p(gain_out), None, _p(dD), _p(sigma), ss, float(sigma_data),
+              _p(gx), None, None, B, H * W, C, Co, _stream())
+    return gx
+
+
+# ------------------------------------------------------------------ the output end in factored form (csrc/tail_lowrank.hip)
+LOWRANK_MAX_CO = 8
+
+
+@functools.lru_cache(maxsize=None)
+def lowrank_supported(C, Co, W, taps):
+    """the factored kernels run this shape (their LDS tables fit): lowrank_wgrad(taps) and, taps == 9, lowrank_dgrad3x3_modbwd.
+    A host query, not a launch (_lib.N_CALLS)."""
+    return bool(_lib.lib().edm_lowrank_supported(int(C), int(Co), int(W), int(taps)))
+
+
+def lowrank_df(dD, Fraw, gain_out, sigma, sigma_data, want_aux=True):
+    """dF = dD * c_out * gain_out (fp32 NCHW, the rank-Co factor of conv_out's input gradient) and, want_aux,
+    aux = dD * c_out * Fraw, whose sum is d loss / d gain_out"""
+    _chk(dD, f32, "dD")
+    B, Co, H, W = dD.shape
+    ss = _sigma_arg(sigma, B)
+    _chk(gain_out, f32, "gain_out")
+    dF = torch.empty_like(dD)
+    aux = None
+    if want_aux:
+        _chk(Fraw, f32, "Fraw", dD.shape)
+        aux = torch.empty_like(dD)
+    _lib.call("edm_lowrank_df", _p(dD), _p(Fraw), _p(gain_out), _p(sigma), ss, float(sigma_data), _p(dF), _p(aux), B, Co,
+              H * W, _stream())
+    return dF, aux
+
+
+def _lowrank_args(dF, Wc, C):
+    _chk(dF, f32, "dF")
+    if dF.dim() != 4 or not 1 <= dF.shape[1] <= LOWRANK_MAX_CO:
+        raise ValueError(f"dF: expected (B, Co <= {LOWRANK_MAX_CO}, H, W)")
+    B, Co, H, W = dF.shape
+    _chk(Wc, f32, "Wc", (Co, 9, C))
+    return B, Co, H, W
+
+
+def lowrank_dgrad3x3(dF, Wc, scale=1.0):
+    """ga2 (bf16 NHWC [B, H, W, C]) = scale * sum_t sum_o dF[p - d(t), o] * Wc[o, t, :]: the dgrad of a 3x3 conv whose
+    output gradient is dF . Wout, from the Co-channel factor dF (fp32 NCHW) and Wc = lowrank_expand_wc(Wout, dgrad pack)"""
+    C = Wc.shape[-1]
+    B, Co, H, W = _lowrank_args(dF, Wc, C)
+    ga = torch.empty(B, H, W, C, device=dF.device, dtype=bf16)
+    _lib.call("edm_lowrank_dgrad3x3", _p(dF), _p(Wc), float(scale), _p(ga), None, None, 0, None, None, None, 0, 0.0, 0, 0, 0,
+              0, B, H, W, C, Co, None, _stream())
+    return ga
+
+
+def lowrank_dgrad3x3_modbwd(dF, Wc, alpha, r1, lin, gain, pdrop, seed, sub, step, glin_out=None, ggain_out=None, dyn=None,
+                            gm_out=None, u_marked=False):
+    """lowrank_dgrad3x3 with the modulation backward on its result in registers: conv3x3_modbwd (same arguments, same
+    returns) for an output gradient of rank Co; no constraint on H * W"""
+    B, H, W, C = _nhwc(r1, "r1")
+    if tuple(dF.shape[0:1] + dF.shape[2:]) != (B, H, W):
+        raise ValueError(f"lowrank_dgrad3x3_modbwd: dF {tuple(dF.shape)} does not match r1 {tuple(r1.shape)}")
+    _, Co, _, _ = _lowrank_args(dF, Wc, C)
+    ls = _lin_view(lin, B, C, "lin")
+    _chk(gain, f32, "gain")
+    gr = torch.empty_like(r1)
+    if gm_out is not None:
+        gms = _lin_view(gm_out, B, C, "gm_out")
+        gm = gm_out
+    else:
+        gms = C
+        gm = zeros_f32((B, C), r1.device)
+        glin = torch.empty(B, C, device=r1.device, dtype=f32) if glin_out is None else glin_out
+        gs = _lin_view(glin, B, C, "glin")
+        ggain = zeros_f32((), r1.device) if ggain_out is None else _chk(ggain_out, f32, "ggain_out", ())
+    _lib.call("edm_lowrank_dgrad3x3", _p(dF), _p(Wc), float(alpha), None, _p(r1), _p(lin), ls, _p(gain), _p(gr), _p(gm),
+              gms, float(pdrop), int(seed), int(sub), int(step), int(bool(u_marked)), B, H, W, C, Co, _dyn(dyn), _stream())
+    if gm_out is not None:
+        return gr, None, None
+    _lib.call("edm_mod_finish", _p(gm), _p(lin), ls, _p(gain), _p(glin), gs, _p(ggain), B, C, _stream())
+    return gr, glin, ggain
+
+
+def lowrank_wgrad(dF, X, taps, aux=None, aux_out=None):
+    """G (fp32 [Co, taps, C]) = sum_p dF[p, o] * X[p + d(t), c] (X bf16 NHWC, taps 1 or 9), deterministic.  aux (fp32 like
+    dF): its sum is ACCUMULATED into the 0-dim fp32 tensor aux_out (else into a fresh zero scalar).  Returns (G, aux sum)."""
+    B, H, W, C = _nhwc(X, "X")
+    _chk(dF, f32, "dF")
+    if dF.dim() != 4 or tuple(dF.shape[0:1] + dF.shape[2:]) != (B, H, W) or not 1 <= dF.shape[1] <= LOWRANK_MAX_CO:
+        raise ValueError(f"lowrank_wgrad: dF {tuple(dF.shape)} does not match X {tuple(X.shape)}")
+    if taps not in (1, 9):
+        raise ValueError("lowrank_wgrad: taps must be 1 or 9")
+    Co = dF.shape[1]
+    asum = None
+    if aux is not None:
+        _chk(aux, f32, "aux", dF.shape)
+        asum = zeros_f32((), X.device) if aux_out is None else _chk(aux_out, f32, "aux_out", ())
+    G = torch.empty(Co, taps, C, device=X.device, dtype=f32)
+    nws = int(_lib.call("edm_lowrank_wgrad_workspace", C, Co, taps))
+    ws = torch.empty(nws, device=X.device, dtype=f32)
+    _lib.call("edm_lowrank_wgrad", _p(dF), _p(X), int(taps), _p(aux), _p(G), _p(asum), _p(ws), nws, B, H, W, C, Co, _stream())
+    return G, asum
+
+
+def lowrank_expand_wc(wout_hat, wd):
+    """Wc (fp32 [Co, taps, I]) = Wout_hat . float(W) from the plain bf16 dgrad pack wd [taps, I, O] of the conv (the values
+    its MFMA dgrad multiplies; taps flipped back)"""
+    _chk(wd, bf16, "wd")
+    if wd.dim() != 3 or getattr(wd, "_edm_frag", False):
+        raise ValueError("lowrank_expand_wc: expected a plain (taps, I, O) dgrad pack")
+    taps, I, O = wd.shape
+    Co = wout_hat.shape[0]
+    _chk(wout_hat, f32, "wout_hat", (Co, O))
+    Wc = torch.empty(Co, taps, I, device=wd.device, dtype=f32)
+    _lib.call("edm_lowrank_expand_wc", _p(wout_hat), _p(wd), _p(Wc), Co, O, I, taps, _stream())
+    return Wc
+
+
+def lowrank_expand_slab(wout_hat, G, scale=1.0, Ipad=None):
+    """one weight-gradient slab (1, taps, O, Ipad) fp32 in packed order, slab[t, c, i] = scale * sum_o Wout_hat[o, c] * G[o, t, i]:
+    what wgrad_finish / wgrad_finish_multi / finish_grad reduce and project like any other"""
+    _chk(G, f32, "G")
+    Co, taps, I = G.shape
+    O = wout_hat.shape[1]
+    _chk(wout_hat, f32, "wout_hat", (Co, O))
+    Ipad = I if Ipad is None else Ipad
+    slab = torch.empty(1, taps, O, Ipad, device=G.device, dtype=f32)
+    _lib.call("edm_lowrank_expand_slab", _p(wout_hat), _p(G), _p(slab), float(scale), Co, O, I, Ipad, taps, _stream())
+    return slab
+
+
 def nchw_to_nhwc_bf16(x):
     _chk(x, f32, "x")
     B, C, H, W = x.shape
