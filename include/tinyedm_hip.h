@@ -396,6 +396,26 @@ int edm_lowrank_expand_wc(const float* wout_hat, const void* wd, float* Wc, int 
 /* slab[t][c][i] = scale * sum_o Wout_hat[o, c] * G[o][t][i]: one slab [1][taps][O][Ipad] for edm_wgrad_finish(_multi) */
 int edm_lowrank_expand_slab(const float* wout_hat, const float* G, float* slab, float scale, int Co, int O, int I,
                             int Ipad, int taps, edm_stream_t stream);
+/* The forward side of the same algebra: the block ends in h = sb * conv3x3(a2, W2) + sa * conv1x1(cat, W1) and conv_out
+ * reads nothing else, so F = Wout . h = sb * conv3x3(a2, Wc) + sa * cat . Wp with Wp = Wout . W1 (fp32 [Co][Cc];
+ * edm_lowrank_expand_wc of the 1x1 conv's dgrad pack, or Wout_hat itself when the block has no 1x1 conv): h never exists.
+ * Writes what edm_conv_out_fwd writes: Fraw (fp32 NCHW, nullable) and D = Fraw * gain_out * c_out + noisy * c_skip.
+ * a2 bf16 NHWC [B, H, W, C], cat bf16 NHWC [B, H, W, Cc]; any H, W; deterministic. */
+int edm_lowrank_tail_supported(int C, int Cc, int Co, int W);     /* the LDS tables fit (host logic only) */
+int edm_lowrank_tail_fwd(const void* a2, const void* cat, const float* Wc, const float* Wp, float sb, float sa,
+                         const float* gain_out, const float* noisy, const float* sigma, int sigma_stride, float sigma_data,
+                         float* D, float* Fraw, int B, int H, int W, int C, int Cc, int Co, edm_stream_t stream);
+/* conv_out's weight gradient without h: gw_hat[o, c] = sb * sum_{t, ci} float(wf2[t][c][ci]) * G[o][t][ci]
+ * + sa * sum_cj float(wf1[c][cj]) * G1[o][cj]  (wf1 == NULL: + sa * G1[o][c]); G = edm_lowrank_wgrad(dF, a2, 9),
+ * G1 = edm_lowrank_wgrad(dF, cat, 1); wf2 / wf1 = the plain bf16 forward packs [taps][O][I]. */
+int edm_lowrank_tail_dwout_supported(int C, int Cc, int Co, int has_1x1);
+int edm_lowrank_tail_dwout(const float* G, const void* wf2, const float* G1, const void* wf1, float sb, float sa,
+                           float* gw_hat, int Co, int C, int Cc, edm_stream_t stream);
+/* d loss / d cat without g_h: bf16(t + sa * dF^T Wp), columns < Ci to gu [B, HW, Ci], the others to gcs [B, HW, Cc - Ci]
+ * (gcs == NULL: Ci == Cc); t bf16 NHWC [B, HW, Cc] = the dense part of the gradient. */
+int edm_lowrank_gcat_supported(int Cc, int Ci, int Co);
+int edm_lowrank_gcat_add(const float* dF, const float* Wp, float sa, const void* t, void* gu, void* gcs, int B, int HW,
+                         int Cc, int Ci, int Co, edm_stream_t stream);
 
 int edm_nchw_to_nhwc_bf16(const float* x, void* y, int B, int C, int HW, edm_stream_t stream);
 int edm_nhwc_bf16_to_nchw(const void* x, float* y, int B, int C, int HW, edm_stream_t stream);

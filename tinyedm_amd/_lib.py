@@ -63,6 +63,12 @@ SIGNATURES = {
     "edm_lowrank_wgrad": [P, P, I, P, P, P, P, L, I, I, I, I, I, P],
     "edm_lowrank_expand_wc": [P, P, P, I, I, I, I, P],
     "edm_lowrank_expand_slab": [P, P, P, F, I, I, I, I, I, P],
+    "edm_lowrank_tail_supported": [I, I, I, I],
+    "edm_lowrank_tail_fwd": [P, P, P, P, F, F, P, P, P, I, F, P, P, I, I, I, I, I, I, P],
+    "edm_lowrank_tail_dwout_supported": [I, I, I, I],
+    "edm_lowrank_tail_dwout": [P, P, P, P, F, F, P, I, I, I, P],
+    "edm_lowrank_gcat_supported": [I, I, I],
+    "edm_lowrank_gcat_add": [P, P, F, P, P, P, I, I, I, I, I, P],
     # conv_igemm.hip / conv_wgrad.hip
     "edm_conv_igemm": [P, P, P, P, F, F, I, I, I, I, I, I, P],
     "edm_conv_igemm_v2": [P, P, P, P, F, F, I, I, I, I, I, I, P],
@@ -183,7 +189,7 @@ DIAG_SIGNATURES = {
 _RET = {"edm_last_error": ctypes.c_char_p, "edm_lowrank_wgrad_workspace": ctypes.c_long, "edm_v6_persistent_launches": ctypes.c_long, "edm_wgrad3_workspace": ctypes.c_long, "edm_wgrad3_table_bytes": ctypes.c_long,
         "edm_skip_gate_wgrad_multi_table_bytes": ctypes.c_long, "edm_skip_gate_fwd_multi_table_bytes": ctypes.c_long, "edm_skip_gate_bwd_multi_table_bytes": ctypes.c_long,
         "edm_conv_wgrad_1x1_group_table_bytes": ctypes.c_long, "edm_wgrad_finish_multi_table_bytes": ctypes.c_long}
-_NO_STATUS = {"edm_lowrank_wgrad_workspace", "edm_lowrank_supported", "edm_skip_gate_bwd_multi_table_bytes", "edm_skip_gate_fwd_multi_table_bytes", "edm_v6_persistent_launches", "edm_conv3x3_fold_supported", "edm_conv_plan", "edm_skip_gate_wgrad_multi_table_bytes", "edm_version", "edm_graph_replay_safe", "edm_last_error", "edm_conv_wgrad_nsplit", "edm_conv_wgrad_1x1_nsplit", "edm_conv_wgrad_1x1_nsplit_grouped", "edm_wgrad3_workspace", "edm_wgrad3_table_bytes", "edm_wgrad3_max_layers",
+_NO_STATUS = {"edm_lowrank_wgrad_workspace", "edm_lowrank_supported", "edm_lowrank_tail_supported", "edm_lowrank_tail_dwout_supported", "edm_lowrank_gcat_supported", "edm_skip_gate_bwd_multi_table_bytes", "edm_skip_gate_fwd_multi_table_bytes", "edm_v6_persistent_launches", "edm_conv3x3_fold_supported", "edm_conv_plan", "edm_skip_gate_wgrad_multi_table_bytes", "edm_version", "edm_graph_replay_safe", "edm_last_error", "edm_conv_wgrad_nsplit", "edm_conv_wgrad_1x1_nsplit", "edm_conv_wgrad_1x1_nsplit_grouped", "edm_wgrad3_workspace", "edm_wgrad3_table_bytes", "edm_wgrad3_max_layers",
               "edm_conv_wgrad_1x1_group_table_bytes", "edm_wgrad_finish_multi_table_bytes", "edm_attention_qkv_supported",
               "edm_u8_knn_splits"}
 

@@ -513,3 +513,301 @@ extern "C" int edm_lowrank_expand_slab(const float* wout_hat, const float* G, fl
   EDM_CHECK_LAUNCH("lowrank_expand_slab");
   return EDM_OK;
 }
+
+// ================================================================== the forward side of the same algebra
+// The last decoder block ends in h = b * conv3x3(a2, W2) + a * conv1x1(cat, W1) and conv_out reduces h to Co channels at
+// once (F = Wout . h, nothing in between), so
+//   F[p, o] = b * sum_t sum_ci a2[p + d(t), ci] * Wc[o, t, ci]  +  a * sum_cj cat[p, cj] * Wp[o, cj]        Wp = Wout . W1
+// (Wp = Wout itself when the block has no 1x1 conv: cat is then the block input, Cc == C): 2 * (9 C + Cc) * Co FLOP per
+// pixel from tables of Co * (9 C + Cc) floats, and h never exists.
+//
+// grid = (ceil(H / R), B): a workgroup owns R whole rows of one sample.  LDS: Wc [CO * 9][C], Wp [CO][Cc] and the tile of
+// partial sums pt [3 ky][R * W][3 kx * CO] + [R * W][CO].  Input-stationary: 8 lanes share a pixel (lane `lig` takes the
+// 8-channel chunks lig, lig + 8, ...), a lane works on PX pixels at once so that a weight vector read from LDS serves PX
+// of them; the 8 partial dot products meet by a butterfly (fixed order) and land in pt at the slot of the OUTPUT row they
+// belong to (input row y feeds output row y - (ky - 1): for each ky only the rows that have an output row in the tile are
+// read, so the halo rows cost one ky pass, not three).  The second phase adds, per output value, its taps in the order
+// t = 0 .. 8 (skipping those outside the image: zero padding), then the 1x1 term: bit-equal from run to run.
+constexpr int TAIL_LPP = 8;     // lanes per pixel
+static size_t tail_fwd_lds(int Co, int C, int Cc, int W, int R) {
+  return ((size_t)Co * 9 * C + (size_t)Co * Cc + (size_t)R * W * 10 * Co) * sizeof(float);
+}
+// 1 when edm_lowrank_tail_fwd runs maps of width W: a2 with C channels, cat with Cc, Co outputs
+extern "C" int edm_lowrank_tail_supported(int C, int Cc, int Co, int W) {
+  if (C <= 0 || C % 8 || C > 1024 || Cc <= 0 || Cc % 8 || Cc > 2048 || Co < 1 || Co > 8 || W <= 0) return 0;
+  return tail_fwd_lds(Co, C, Cc, W, 1) <= LOWRANK_LDS_MAX;
+}
+
+// NV = NK * CO dot products over Cx channels of PX pixels (xp[k]: the lane's view of pixel k, NULL = no pixel) against
+// the LDS rows w[(o * wso + k) * Cx ...]; every lane of the pixel's group returns the full sums in s
+template <int CO, int NK, int PX>
+__device__ __forceinline__ void tail_dots(const bf16* const (&xp)[PX], int Cx, const float* __restrict__ w, int wso, int lig,
+                                          float (&s)[PX][NK * CO]) {
+  f32x2 acc[PX][NK * CO];
+#pragma unroll
+  for (int k = 0; k < PX; ++k)
+#pragma unroll
+    for (int v = 0; v < NK * CO; ++v) acc[k][v] = f32x2{0.f, 0.f};
+  const int CL = Cx >> 3;
+  for (int c8 = lig; c8 < CL; c8 += TAIL_LPP) {
+    f32x2 xf[PX][4];
+#pragma unroll
+    for (int k = 0; k < PX; ++k) {
+      u32x4 raw = u32x4{0u, 0u, 0u, 0u};
+      if (xp[k]) raw = *reinterpret_cast<const u32x4*>(xp[k] + c8 * 8);
+      const bf16x8 xv = __builtin_bit_cast(bf16x8, raw);
+#pragma unroll
+      for (int h = 0; h < 4; ++h) xf[k][h] = f32x2{(float)xv[2 * h], (float)xv[2 * h + 1]};
+    }
+#pragma unroll
+    for (int o = 0; o < CO; ++o)
+#pragma unroll
+      for (int kk = 0; kk < NK; ++kk) {
+        const float* wp = w + (long)(o * wso + kk) * Cx + c8 * 8;
+        const f32x4 w0 = *reinterpret_cast<const f32x4*>(wp), w1 = *reinterpret_cast<const f32x4*>(wp + 4);
+        const f32x2 wv[4] = {f32x2{w0[0], w0[1]}, f32x2{w0[2], w0[3]}, f32x2{w1[0], w1[1]}, f32x2{w1[2], w1[3]}};
+#pragma unroll
+        for (int k = 0; k < PX; ++k)
+#pragma unroll
+          for (int h = 0; h < 4; ++h) acc[k][kk * CO + o] += xf[k][h] * wv[h];
+      }
+  }
+#pragma unroll
+  for (int k = 0; k < PX; ++k)
+#pragma unroll
+    for (int v = 0; v < NK * CO; ++v) s[k][v] = group_sum<TAIL_LPP>(acc[k][v][0] + acc[k][v][1]);
+}
+
+template <int CO, int PX>
+__global__ __launch_bounds__(512) void k_lowrank_tail_fwd(const bf16* __restrict__ a2, const bf16* __restrict__ cat,
+                                                          const float* __restrict__ Wc, const float* __restrict__ Wp,
+                                                          float sb, float sa, const float* __restrict__ gain_out,
+                                                          const float* __restrict__ noisy, const float* __restrict__ sigma,
+                                                          int sstride, float sd, float* __restrict__ D,
+                                                          float* __restrict__ Fraw, int H, int W, int C, int Cc, int R) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  float* wl = sm;                               // [CO * 9][C]
+  float* wpl = wl + CO * 9 * C;                 // [CO][Cc]
+  float* pt = wpl + CO * Cc;                    // [3][R * W][3 * CO], then [R * W][CO]
+  const int RW = R * W;
+  float* qt = pt + 3 * RW * 3 * CO;
+  const int b = blockIdx.y, y0 = blockIdx.x * R;
+  const int rows = min(R, H - y0);
+  for (int i = threadIdx.x; i < CO * 9 * C / 4; i += blockDim.x)
+    reinterpret_cast<f32x4*>(wl)[i] = reinterpret_cast<const f32x4*>(Wc)[i];
+  for (int i = threadIdx.x; i < CO * Cc / 4; i += blockDim.x)
+    reinterpret_cast<f32x4*>(wpl)[i] = reinterpret_cast<const f32x4*>(Wp)[i];
+  __syncthreads();
+  const int lig = threadIdx.x % TAIL_LPP, grp = threadIdx.x / TAIL_LPP, NG = blockDim.x / TAIL_LPP;
+  // ---- the nine taps: per ky, the input rows y0 + ky - 1 ... that lie in the image (contiguous pixels of the sample)
+#pragma unroll 1
+  for (int ky = 0; ky < 3; ++ky) {
+    const int r_lo = max(y0 + ky - 1, 0), r_hi = min(y0 + rows - 1 + ky - 1, H - 1);
+    const int np = (r_hi - r_lo + 1) * W;                    // (<= 0: a one-row image has no row above / below)
+    const int slot0 = (r_lo - (y0 + ky - 1)) * W;            // slot of the first pixel: its OUTPUT row's place in the tile
+    const bf16* base = a2 + (((long)b * H + r_lo) * W) * C;
+    float* po = pt + (long)ky * RW * 3 * CO;
+    for (int n0 = grp * PX; n0 < np; n0 += NG * PX) {
+      const bf16* xp[PX];
+#pragma unroll
+      for (int k = 0; k < PX; ++k) xp[k] = n0 + k < np ? base + (long)(n0 + k) * C : nullptr;
+      float s[PX][3 * CO];
+      tail_dots<CO, 3, PX>(xp, C, wl + ky * 3 * C, 9, lig, s);
+#pragma unroll
+      for (int k = 0; k < PX; ++k)
+        if (n0 + k < np) {
+#pragma unroll
+          for (int v = 0; v < 3 * CO; ++v)
+            if ((v % TAIL_LPP) == lig) po[(long)(slot0 + n0 + k) * 3 * CO + v] = s[k][v];
+        }
+    }
+  }
+  // ---- the 1x1 term over cat: the tile's own rows
+  {
+    const int np = rows * W;
+    const bf16* base = cat + (((long)b * H + y0) * W) * Cc;
+    for (int n0 = grp * PX; n0 < np; n0 += NG * PX) {
+      const bf16* xp[PX];
+#pragma unroll
+      for (int k = 0; k < PX; ++k) xp[k] = n0 + k < np ? base + (long)(n0 + k) * Cc : nullptr;
+      float s[PX][CO];
+      tail_dots<CO, 1, PX>(xp, Cc, wpl, 1, lig, s);
+#pragma unroll
+      for (int k = 0; k < PX; ++k)
+        if (n0 + k < np) {
+#pragma unroll
+          for (int v = 0; v < CO; ++v)
+            if ((v % TAIL_LPP) == lig) qt[(long)(n0 + k) * CO + v] = s[k][v];
+        }
+    }
+  }
+  __syncthreads();
+  // ---- every output value: its taps in the order t = 0 .. 8, then the 1x1 term; D as k_conv_out_fwd forms it
+  const float go = *gain_out;
+  const float sg = sigma[b * sstride];
+  const float den = sg * sg + sd * sd;
+  const float cskip = sd * sd / den, cout = sg * sd * rsqrtf(den);
+  for (int i = threadIdx.x; i < CO * rows * W; i += blockDim.x) {
+    const int o = i / (rows * W), n = i - o * rows * W;
+    const int ry = n / W, x = n - ry * W;
+    float s = 0.f;
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) {
+      const int iy = y0 + ry + ky - 1;
+      if (iy < 0 || iy >= H) continue;
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) {
+        const int ix = x + kx - 1;
+        if (ix < 0 || ix >= W) continue;
+        s += pt[((long)ky * RW + ry * W + ix) * 3 * CO + kx * CO + o];
+      }
+    }
+    const float f = sb * s + sa * qt[(long)n * CO + o];
+    const long idx = (((long)b * CO + o) * H + y0 + ry) * W + x;
+    if (Fraw) Fraw[idx] = f;
+    D[idx] = f * go * cout + noisy[idx] * cskip;
+  }
+}
+
+template <int CO>
+static int launch_tail_fwd(const void* a2, const void* cat, const float* Wc, const float* Wp, float sb, float sa,
+                           const float* gain_out, const float* noisy, const float* sigma, int sstride, float sd, float* D,
+                           float* Fraw, int B, int H, int W, int C, int Cc, hipStream_t st) {
+  // two pixels per lane up to Co = 4 (2 * 9 * Co packed accumulators), one above
+  constexpr int PX = CO <= 4 ? 2 : 1;
+  // rows per workgroup: ~128 pixels (the tile of partial sums: 10 Co floats per pixel), shrunk until the tables fit
+  int R = 128 / W;
+  R = R < 1 ? 1 : (R > H ? H : R);
+  auto lds = [&](int r) { return tail_fwd_lds(CO, C, Cc, W, r); };
+  while (R > 1 && lds(R) > LOWRANK_LDS_MAX) --R;
+  EDM_REQUIRE(lds(R) <= LOWRANK_LDS_MAX, "lowrank_tail_fwd: Co=%d, C=%d, Cc=%d, W=%d need %zu bytes of LDS (60 KB at most)", CO,
+              C, Cc, W, lds(R));
+  // a workgroup has 8 lanes per pixel: no more threads than the tile's largest pass can use
+  const long want = ((long)(R + 1) * W + PX - 1) / PX * TAIL_LPP;
+  int block = want >= 512 ? 512 : (int)((want + 63) / 64 * 64);
+  const dim3 grid((H + R - 1) / R, B);
+  hipLaunchKernelGGL((k_lowrank_tail_fwd<CO, PX>), grid, dim3(block), lds(R), st, (const bf16*)a2, (const bf16*)cat, Wc, Wp, sb,
+                     sa, gain_out, noisy, sigma, sstride, sd, D, Fraw, H, W, C, Cc, R);
+  EDM_CHECK_LAUNCH("lowrank_tail_fwd");
+  return EDM_OK;
+}
+
+// Fraw (fp32 NCHW [B, Co, H, W], nullable) = sb * conv3x3(a2, Wc) + sa * cat . Wp and D = Fraw * gain_out * c_out(sigma) +
+// noisy * c_skip(sigma): what edm_conv_out_fwd writes for the block's output.  a2 bf16 NHWC [B, H, W, C], cat bf16 NHWC
+// [B, H, W, Cc], Wc fp32 [Co][9][C] (edm_lowrank_expand_wc), Wp fp32 [Co][Cc].
+extern "C" int edm_lowrank_tail_fwd(const void* a2, const void* cat, const float* Wc, const float* Wp, float sb, float sa,
+                                    const float* gain_out, const float* noisy, const float* sigma, int sigma_stride,
+                                    float sigma_data, float* D, float* Fraw, int B, int H, int W, int C, int Cc, int Co,
+                                    hipStream_t st) {
+  EDM_REQUIRE(a2 && cat && Wc && Wp && gain_out && noisy && sigma && D, "lowrank_tail_fwd: null pointer");
+  EDM_REQUIRE(B > 0 && B <= 65535 && H > 0 && W > 0 && (sigma_stride == 0 || sigma_stride == 1), "lowrank_tail_fwd: bad args");
+  EDM_REQUIRE(edm_lowrank_tail_supported(C, Cc, Co, W), "lowrank_tail_fwd: unsupported shape C=%d Cc=%d Co=%d W=%d", C, Cc, Co, W);
+  EDM_REQUIRE((((uintptr_t)Wc | (uintptr_t)Wp | (uintptr_t)a2 | (uintptr_t)cat) & 15) == 0,
+              "lowrank_tail_fwd: operands must be 16-byte aligned");
+#define CALL(CO_) launch_tail_fwd<CO_>(a2, cat, Wc, Wp, sb, sa, gain_out, noisy, sigma, sigma_stride, sigma_data, D, Fraw, B, \
+                                       H, W, C, Cc, st)
+  EDM_CO_SWITCH(Co, CALL)
+#undef CALL
+}
+
+// ------------------------------------------------------------------ conv_out's weight gradient without h
+// gwh[o, c] = sb * sum_t sum_ci float(wf2[t][c][ci]) * G[o][t][ci] + sa * sum_cj float(wf1[c][cj]) * G1[o][cj]
+// (wf1 == NULL: + sa * G1[o][c]): dWout = dF^T h with h = sb * conv(a2, W2) + sa * W1 cat pushed onto the two reductions
+// the backward has anyway.  wf2 / wf1: the plain bf16 forward packs [taps][O][I].  One wave per channel c, lanes over
+// 8-channel chunks of the rows, the 64 partial sums meet by a butterfly: bit-equal from run to run.
+__global__ __launch_bounds__(256) void k_lowrank_tail_dwout(const float* __restrict__ G, const bf16* __restrict__ wf2,
+                                                            const float* __restrict__ G1, const bf16* __restrict__ wf1,
+                                                            float sb, float sa, float* __restrict__ gwh, int Co, int C,
+                                                            int Cc) {
+  const int lane = threadIdx.x & 63;
+  const int c = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (c >= C) return;
+  float a9[8] = {0, 0, 0, 0, 0, 0, 0, 0}, a1[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int t = 0; t < 9; ++t)
+    for (int ci = lane * 8; ci < C; ci += 64 * 8) {
+      float v[8];
+      load8(wf2 + ((long)t * C + c) * C + ci, v);
+#pragma unroll
+      for (int o = 0; o < 8; ++o)
+        if (o < Co) {
+          const float* gp = G + ((long)o * 9 + t) * C + ci;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) a9[o] += v[j] * gp[j];
+        }
+    }
+  if (wf1)
+    for (int cj = lane * 8; cj < Cc; cj += 64 * 8) {
+      float v[8];
+      load8(wf1 + (long)c * Cc + cj, v);
+#pragma unroll
+      for (int o = 0; o < 8; ++o)
+        if (o < Co) {
+          const float* gp = G1 + (long)o * Cc + cj;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) a1[o] += v[j] * gp[j];
+        }
+    }
+#pragma unroll
+  for (int o = 0; o < 8; ++o)
+    if (o < Co) {
+      const float s9 = wave_sum(a9[o]);
+      const float s1 = wf1 ? wave_sum(a1[o]) : G1[(long)o * Cc + c];
+      if (lane == 0) gwh[(long)o * C + c] = sb * s9 + sa * s1;
+    }
+}
+extern "C" int edm_lowrank_tail_dwout_supported(int C, int Cc, int Co, int has1) {
+  return C > 0 && C % 8 == 0 && Cc > 0 && Cc % 8 == 0 && Co >= 1 && Co <= 8 && (has1 || Cc == C);
+}
+extern "C" int edm_lowrank_tail_dwout(const float* G, const void* wf2, const float* G1, const void* wf1, float sb, float sa,
+                                      float* gwh, int Co, int C, int Cc, hipStream_t st) {
+  EDM_REQUIRE(G && wf2 && G1 && gwh, "lowrank_tail_dwout: null pointer");
+  EDM_REQUIRE(edm_lowrank_tail_dwout_supported(C, Cc, Co, wf1 != nullptr), "lowrank_tail_dwout: bad args (C=%d Cc=%d Co=%d)", C, Cc,
+              Co);
+  EDM_REQUIRE((((uintptr_t)wf2 | (uintptr_t)wf1) & 15) == 0, "lowrank_tail_dwout: packs must be 16-byte aligned");
+  hipLaunchKernelGGL(k_lowrank_tail_dwout, dim3((C + 3) / 4), dim3(256), 0, st, G, (const bf16*)wf2, G1, (const bf16*)wf1, sb,
+                     sa, gwh, Co, C, Cc);
+  EDM_CHECK_LAUNCH("lowrank_tail_dwout");
+  return EDM_OK;
+}
+
+// ------------------------------------------------------------------ d loss / d cat without g_h
+// out[p, cj] = bf16(float(t[p, cj]) + sa * sum_o dF[p, o] * Wp[o, cj]): the 1x1 dgrad of g_h = dF . Wout with the dense part
+// t (bf16 NHWC [B, H, W, Cc], rounded as the dense kernels round it) as its residual.  The columns below Ci go to gu
+// [.., Ci], the others to gcs [.., Cc - Ci] (gcs == NULL: Ci == Cc): the two halves conv_igemm(split =) writes.
+__global__ void k_lowrank_gcat_add(const float* __restrict__ dF, const float* __restrict__ Wp, float sa,
+                                   const bf16* __restrict__ t, bf16* __restrict__ gu, bf16* __restrict__ gcs, int HW, int Cc,
+                                   int Ci, int Co, long n8) {
+  const unsigned CL = (unsigned)Cc >> 3, uHW = (unsigned)HW, CiL = (unsigned)Ci >> 3;
+  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < (unsigned)n8; i += gridDim.x * blockDim.x) {
+    const unsigned p = i / CL, c8 = i - p * CL;
+    const unsigned b = p / uHW, hw = p - b * uHW;
+    float v[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tv[8];
+    load8(t + (long)i * 8, tv);
+    for (int o = 0; o < Co; ++o) {
+      const float df = dF[((long)b * Co + o) * HW + hw];
+      const float* wp = Wp + (long)o * Cc + c8 * 8;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] += df * wp[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = tv[j] + sa * v[j];
+    if (c8 < CiL) store8(gu + ((long)p * Ci + c8 * 8), v);
+    else store8(gcs + ((long)p * (Cc - Ci) + (c8 - CiL) * 8), v);
+  }
+}
+extern "C" int edm_lowrank_gcat_supported(int Cc, int Ci, int Co) {
+  return Cc > 0 && Cc % 8 == 0 && Ci > 0 && Ci % 8 == 0 && Ci <= Cc && Co >= 1 && Co <= 8;
+}
+extern "C" int edm_lowrank_gcat_add(const float* dF, const float* Wp, float sa, const void* t, void* gu, void* gcs, int B,
+                                    int HW, int Cc, int Ci, int Co, hipStream_t st) {
+  EDM_REQUIRE(dF && Wp && t && gu, "lowrank_gcat_add: null pointer");
+  EDM_REQUIRE(B > 0 && HW > 0 && edm_lowrank_gcat_supported(Cc, Ci, Co) && (gcs || Ci == Cc),
+              "lowrank_gcat_add: bad args (Cc=%d Ci=%d Co=%d)", Cc, Ci, Co);
+  const long n8 = (long)B * HW * (Cc / 8);
+  EDM_REQUIRE(n8 < (1L << 31), "lowrank_gcat_add: too many elements");
+  const long blocks = (n8 + 255) / 256;
+  hipLaunchKernelGGL(k_lowrank_gcat_add, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(256), 0, st, dF, Wp, sa,
+                     (const bf16*)t, (bf16*)gu, (bf16*)gcs, HW, Cc, Ci, Co, n8);
+  EDM_CHECK_LAUNCH("lowrank_gcat_add");
+  return EDM_OK;
+}

@@ -180,6 +180,13 @@ _w3_pending = {}            # device index -> [(mod, x, dy, scale)] 3x3 layers w
 # one-tap form of the same reduction.  Arena gradients only.  EDM_TAIL_LOWRANK=0: the launches of before (A/B runs, bisecting).
 TAIL_LOWRANK = os.environ.get("EDM_TAIL_LOWRANK", "1") != "0"
 _tail_slot = {}             # device index -> (dF, Wout_hat, gx): left by _ConvOutFn.backward for the consumer of ITS gx only
+# The forward side of the same algebra: nothing sits between the last decoder block's output h and conv_out, so
+# F = Wout . h is computed from the block's own operands (a2, cat) with 3-channel tables and h is never written; in the
+# backward neither is g_h: conv_out's weight gradient, the block's 1x1 weight gradient and d loss / d cat come from dF and
+# the Co-channel reductions G, G1.  The Denoiser joins the block's autograd node and _TailOutFn by a zero-size handle.
+# EDM_TAIL_FWD=0: the launches of before.
+TAIL_FWD = os.environ.get("EDM_TAIL_FWD", "1") != "0"
+_tail_fwd_slot = {}         # device index -> operands of _TailOutFn: set by the last block's forward, taken by the Denoiser at once
 _fin_pending = {}           # device index -> [(slabs, w, perm, taps, I, scale)] small weight gradients to finish
 
 
@@ -262,6 +269,7 @@ def _backward_end(key):
     backward wait for the auxiliary stream (the optimizer reads what the weight-gradient kernels wrote)."""
     _bwd_end_queued.discard(key)
     _tail_slot.pop(key, None)
+    _tail_fwd_slot.pop(key, None)
     if key in _w3_seen:
         _w3_total[key] = _w3_seen.pop(key)
     _flush_sg(key)
@@ -286,6 +294,7 @@ def reset_backward_state():
     """Forget deferred work of a backward pass that did not complete (an exception inside autograd leaves its
     end-of-backward callback unrun).  Called at the start of every Denoiser forward."""
     _tail_slot.clear()
+    _tail_fwd_slot.clear()
     if _bwd_end_queued or _w3_pending or _fin_pending or _w1_pending or _sg_pending:
         _bwd_end_queued.clear()
         for items in _sg_pending.values():
@@ -352,16 +361,36 @@ def _wgrad(mod, x, dy, taps, scale=1.0):
     return mod.finish_grad(ops.conv_wgrad(x, dy, taps), scale=scale)
 
 
-def _wgrad_lowrank(mod, x, dF, wout_hat, scale):
+def _wgrad_lowrank(mod, x, dF, wout_hat, scale, G=None):
     """Weight gradient of the 3x3 conv `mod` whose output gradient is dF . Wout (arena mode): the Co-channel reduction G
     over x, expanded through Wout into ONE slab that the multi-tensor finish projects and accumulates.  The layer joins no
     k_wgrad3 group and is not counted among the 3x3 layers of the pass (_w3_seen / _w3_total: W3_TAIL still cuts the last
-    group where it did); its parameter is deferred and its hooks run with the finish launch, like every small gradient."""
+    group where it did); its parameter is deferred and its hooks run with the finish launch, like every small gradient.
+    G given (TAIL_FWD: _TailOutFn.backward reduced it already, for a 3x3 or a 1x1 conv): only the expansion."""
     w = mod.weight
     box = []
-    _run_on_side(w.device, lambda: box.append(ops.lowrank_expand_slab(wout_hat, ops.lowrank_wgrad(dF, x, 9)[0], scale)),
-                 (x, dF, wout_hat))
+    if G is not None:
+        _run_on_side(w.device, lambda: box.append(ops.lowrank_expand_slab(wout_hat, G, scale)), (G, wout_hat))
+    else:
+        _run_on_side(w.device, lambda: box.append(ops.lowrank_expand_slab(wout_hat, ops.lowrank_wgrad(dF, x, 9)[0], scale)),
+                     (x, dF, wout_hat))
     return mod.finish_grad(box[0])
+
+
+def _tail_fwd_shapes_ok(u, wf2, wd2, has1, Co, Ci) -> bool:
+    """every factored kernel of the TAIL_FWD path runs the last block's shapes (host queries, no launch): u = the block's
+    `cat` operand (the block input when it has no 1x1 conv), wf2 / wd2 = the packs of its second 3x3 conv, Ci = the columns
+    of u that are the block's input (the split of d loss / d cat in the backward)"""
+    if not (u.dim() == 4 and u.dtype == bf16 and u.is_contiguous() and wf2.dim() == 3 and wd2.dim() == 3):
+        return False
+    if getattr(wf2, "_edm_frag", False) or getattr(wd2, "_edm_frag", False):
+        return False
+    C, Cc, W = wf2.shape[2], u.shape[-1], u.shape[2]
+    if wf2.shape[1] != C or (not has1 and Cc != C) or not 1 <= Co <= ops.LOWRANK_MAX_CO:
+        return False
+    return (ops.lowrank_tail_supported(C, Cc, Co, W) and ops.lowrank_supported(C, Co, W, 9)
+            and ops.lowrank_supported(Cc, Co, W, 1) and ops.lowrank_tail_dwout_supported(C, Cc, Co, has1)
+            and ops.lowrank_gcat_supported(Cc, Ci, Co))
 
 
 # bf16 tile of a weight-prep workgroup (rows x fan_in): 96 KB = 16 rows of a 256-channel 3x3 layer, two workgroups per CU
@@ -980,13 +1009,16 @@ class _ResBlockFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, u, emb, w1x1, w1, w2, wemb, gain, blk, lin_view, glin_view, token, s_pre=None, alias=False,
-                gm_view=None, skip=None, w_sl1=None, w_sl2=None, pre=None, dest=None, pool=False, gate_pre=None):
+                gm_view=None, skip=None, w_sl1=None, w_sl2=None, pre=None, dest=None, pool=False, gate_pre=None, tail=0):
         # skip (decoder blocks with a U-Net skip and no upsample, FUSE_CAT): the concatenation of networks.py:311 happens
         # HERE.  pre = (cat, sil) whose left halves the producer of u already wrote (u is that half of cat): only the gated
         # skip half is filled in; otherwise the standalone concat kernel builds both.  dest = the (cat, sil) buffers of the
         # NEXT block: this block's last kernel writes its output (and mp_silu of it) into their left halves.
         # pool=True (encoder blocks with a downsample and no 1x1 conv, FUSE_RESAMPLE): u is the tensor BEFORE the 2x2 average
         # pool; the pool happens inside the pixel-norm kernels of both directions.
+        # tail = Co > 0 (TAIL_FWD, the Denoiser's last decoder block): conv_out with Co outputs reads this block's output and
+        # nothing else does.  Where the factored kernels run the shape, the block's last conv is NOT run: its operands go to
+        # _tail_fwd_slot for _TailOutFn and the output is a zero-size handle (else: the dense output, and no slot).
         # alias=True: the block input u is handed back as a second output.  The Denoiser takes the U-Net skip from that
         # output, so the skip's gradient arrives in THIS backward (g_alias) and is added by the kernel that writes the
         # input gradient -- not by an autograd `add` launch per skip (9-16 ATen kernels, 0.8 GB per step, round 1).
@@ -998,7 +1030,8 @@ class _ResBlockFn(torch.autograd.Function):
         wf2, wd2, _ = blk.conv_3x3_2.packs()
         batched = lin_view is not None          # embed Linear evaluated for all blocks at once (_EmbedAllFn)
         weh = None if batched else blk.embed.packs()[2]
-        wd11 = None
+        wf11 = wd11 = None
+        tail_fwd = False
         ctx.has_skip = skip is not None
         if skip is not None:
             sl = blk.cat_factor
@@ -1032,6 +1065,9 @@ class _ResBlockFn(torch.autograd.Function):
             fold = False
             if has1:
                 wf11, wd11, _ = blk.conv_1x1.packs()
+            tail_fwd = bool(tail) and _tail_fwd_shapes_ok(u, wf2, wd2, has1, int(tail),
+                                                          ctx.Ci if skip is not None else u.shape[-1])
+            if has1 and not tail_fwd:
                 # round 6: the projection conv_1x1(cat) (networks.py:313) rides in the second 3x3 conv as a second reduction
                 # behind its nine taps (ops.conv3x3_fold) where that conv runs on the static-schedule kernel; elsewhere it
                 # stays a launch of its own whose result is the 3x3 conv's residual
@@ -1053,7 +1089,10 @@ class _ResBlockFn(torch.autograd.Function):
             a2 = ops.mod_silu_drop_fwd(r1, lin, gain, pdrop, seed, sub, step, dyn=rng.dyn)
         a, b = _mp_coeffs(blk.add_factor)
         Co = wf2.shape[1]
-        if (not enc) and fold:
+        if tail_fwd:
+            _tail_fwd_slot[a2.device.index] = (a2, u, wf2, wd2, wf11, wd11, a, b)
+            out = torch.empty(*a2.shape[:3], 0, device=a2.device, dtype=bf16)
+        elif (not enc) and fold:
             if _dest_ok(dest, a2):
                 out = ops.conv3x3_fold(a2, wf2, u, wf11, b, a, out=_col_block(dest[0], Co), silu_out=_col_block(dest[1], Co))
                 out._edm_cat = dest
@@ -1066,6 +1105,7 @@ class _ResBlockFn(torch.autograd.Function):
         else:
             out = ops.conv_igemm(a2, wf2, taps, residual=xres, alpha=b, beta=a)
         ctx.blk, ctx.enc, ctx.has1 = blk, enc, has1
+        ctx.tail_fwd = tail_fwd
         ctx.drop = (pdrop, seed, sub, step, rng.dyn)
         ctx.u_marked = U_MARKS and ops.FUSE_MOD and ops.IGEMM_VERSION == 0
         ctx.batched, ctx.glin_view, ctx.gm_view = batched, glin_view, gm_view
@@ -1093,8 +1133,15 @@ class _ResBlockFn(torch.autograd.Function):
         ggain_out = gp.grad if gdirect else None
         deferred = False
         fused = ops.FUSE_MOD and ops.IGEMM_VERSION == 0 and (gout.shape[1] * gout.shape[2]) % 32 == 0
-        tail = None
-        if blk._tail_last:
+        tail = tfwd = None
+        if ctx.tail_fwd:
+            # the handle's gradient carries nothing: everything comes from what _TailOutFn.backward left in the slot
+            slot = _tail_slot.pop(gout.device.index, None)
+            if slot is None or len(slot) != 7 or r1 is None:
+                raise RuntimeError("tinyedm_amd: the last block's backward ran without the output end's (TAIL_FWD: its "
+                                   "output is a handle that only _TailOutFn consumes)")
+            tail, tfwd = slot[:2], slot[3:]
+        elif blk._tail_last:
             # the slot is taken only by the consumer of the very tensor _ConvOutFn.backward returned, and emptied whatever
             # happens here
             slot = _tail_slot.pop(gout.device.index, None)
@@ -1108,7 +1155,8 @@ class _ResBlockFn(torch.autograd.Function):
             # g_h = dF . Wout has rank Co: conv2's dgrad as a Co -> C transposed conv with the modulation backward on its
             # result in registers (csrc/tail_lowrank.hip; any H * W)
             deferred = ctx.gm_view is not None and gdirect and (fused or MOD_DEFER_UNFUSED)
-            gr1, glin, ggain = ops.lowrank_dgrad3x3_modbwd(tail[0], ops.lowrank_expand_wc(tail[1], wd2), b, r1, lin, gain, pdrop,
+            Wc = tfwd[3] if tfwd is not None else ops.lowrank_expand_wc(tail[1], wd2)
+            gr1, glin, ggain = ops.lowrank_dgrad3x3_modbwd(tail[0], Wc, b, r1, lin, gain, pdrop,
                                                              seed, sub, step, glin_out=glin_out, ggain_out=ggain_out, dyn=dyn,
                                                              gm_out=ctx.gm_view if deferred else None, u_marked=ctx.u_marked)
             if deferred:
@@ -1139,7 +1187,9 @@ class _ResBlockFn(torch.autograd.Function):
             if not deferred:
                 for hook in getattr(gp, "_edm_hooks", ()):
                     hook(gp)
-        if tail is not None:
+        if tfwd is not None:
+            gw2 = _wgrad_lowrank(blk.conv_3x3_2, a2, tail[0], tail[1], b, G=tfwd[0])
+        elif tail is not None:
             gw2 = _wgrad_lowrank(blk.conv_3x3_2, a2, tail[0], tail[1], b)
         else:
             gw2 = _wgrad(blk.conv_3x3_2, a2, gout, 9, b)
@@ -1167,7 +1217,14 @@ class _ResBlockFn(torch.autograd.Function):
                 gu = gx
             g_alias = None
         else:
-            if has1:
+            if tfwd is not None:
+                # g_h = dF . Wout is never formed: d loss / d cat = t + a * dF^T Wp (both halves from one streaming pass), the
+                # 1x1 conv's weight gradient from the one-tap reduction G1 that conv_out's weight gradient needed anyway
+                t = ops.conv3x3_silubwd(gr1, wd1, u) if fuse else ops.silu_bwd(u, gs)
+                gu, gcs = ops.lowrank_gcat_add(tail[0], tfwd[2], a, t, ctx.Ci if ctx.has_skip else None)
+                if has1:
+                    gw11 = _wgrad_lowrank(blk.conv_1x1, None, None, tail[1], a, G=tfwd[1])
+            elif has1:
                 t = ops.conv3x3_silubwd(gr1, wd1, u) if fuse else ops.silu_bwd(u, gs)
                 if ctx.has_skip:
                     # d loss / d cat leaves the 1x1 dgrad as its two halves: d loss / d input (final) and the raw gradient
@@ -1222,7 +1279,7 @@ class _ResBlockFn(torch.autograd.Function):
         if g_alias is not None:         # decoder blocks are never asked for an alias; kept for completeness
             gu = ops.axpby(gu, 1.0, g_alias, 1.0)
         return (gu, gemb, gw11, gw1, gw2, gwemb, ggain, None, None, None, gtoken, None, None, None, gskip, gwsl1, gwsl2,
-                None, None, None, None)
+                None, None, None, None, None)
 
 
 _rng_sub_counter = [0]
@@ -1243,17 +1300,17 @@ class _BlockBase(nn.Module):
         self.rng_sub = _rng_sub_counter[0]
 
     def _res(self, u: Tensor, embedding: Tensor, lin=None, s_pre=None, alias=False, skip=None, dest=None, pool=False,
-             gate=None):
+             gate=None, tail=0):
         """alias=True: returns (out, alias of u) -- see _ResBlockFn.forward.  skip / dest: FUSE_CAT (decoder blocks);
         pool: u is the block input BEFORE its 2x2 average pool (FUSE_RESAMPLE, encoder blocks)"""
         w11 = self.conv_1x1.weight if isinstance(self.conv_1x1, Conv2d) else None
         has_attn = isinstance(self.attention, CosineAttention)
         sk = ()
-        if skip is not None or dest is not None or pool:
+        if skip is not None or dest is not None or pool or tail:
             cf = self.cat_factor if skip is not None else None
             sk = (skip, cf.layer1.weight if cf is not None else None, cf.layer2.weight if cf is not None else None,
                   getattr(u, "_edm_cat", None) if skip is not None else None, None if has_attn else dest, bool(pool),
-                  gate if skip is not None else None)
+                  gate if skip is not None else None, 0 if has_attn else int(tail))
         if lin is None:
             out = _ResBlockFn.apply(u, embedding, w11, self.conv_3x3_1.weight, self.conv_3x3_2.weight,
                                     self.embed.weight, self.gain, self, None, None, None, s_pre, alias, None, *sk)
@@ -1449,8 +1506,12 @@ class DecoderBlock(_BlockBase):
         return (FUSE_CAT and SKIP_GATE_FUSED and not isinstance(self.resample, UpSample)
                 and isinstance(self.conv_1x1, Conv2d) and self.cat_factor is not None)
 
-    def forward(self, input: Tensor, embedding: Tensor, skip: Tensor | None = None, _lin=None, _dest=None, _gate=None) -> Tensor:
+    def forward(self, input: Tensor, embedding: Tensor, skip: Tensor | None = None, _lin=None, _dest=None, _gate=None,
+                _tail=0) -> Tensor:
+        """_tail = Co > 0: the Denoiser's conv_out (Co outputs) is the only reader of this block's output (TAIL_FWD)"""
         x, conv = _as_nhwc(input)
+        if conv:
+            _tail = 0
         s_pre = None
         if skip is not None and FUSE_CAT and SKIP_GATE_FUSED and not isinstance(self.resample, UpSample) \
                 and isinstance(self.conv_1x1, Conv2d):
@@ -1458,7 +1519,7 @@ class DecoderBlock(_BlockBase):
             assert self.cat_factor is not None
             sk, _ = _as_nhwc(skip)
             out = self._res(x, None if _lin is not None else _emb32(embedding, x.shape[0]), _lin, skip=sk, dest=_dest,
-                            gate=_gate)
+                            gate=_gate, tail=_tail)
             return ops.nhwc_bf16_to_nchw(out).to(input.dtype) if conv else _tag(out)
         if skip is not None:
             assert self.cat_factor is not None
@@ -1478,7 +1539,7 @@ class DecoderBlock(_BlockBase):
             else:
                 x = _ResampleFn.apply(x, True)
                 s_pre = None
-        out = self._res(x, None if _lin is not None else _emb32(embedding, x.shape[0]), _lin, s_pre, dest=_dest)
+        out = self._res(x, None if _lin is not None else _emb32(embedding, x.shape[0]), _lin, s_pre, dest=_dest, tail=_tail)
         return ops.nhwc_bf16_to_nchw(out).to(input.dtype) if conv else _tag(out)
 
     @staticmethod
@@ -1697,6 +1758,58 @@ class _ConvOutFn(torch.autograd.Function):
         return gx, gw, gg, None, None, None
 
 
+class _TailOutFn(torch.autograd.Function):
+    """_ConvOutFn for the last decoder block's output h = b * conv3x3(a2, W2) + a * conv1x1(cat, W1) in factored form
+    (TAIL_FWD): `handle` is the block's zero-size output, `pack` what its forward left in _tail_fwd_slot.  Forward: one
+    kernel over a2 and cat with the Co-channel tables Wc = Wout . W2, Wp = Wout . W1.  Backward: dF, the reductions
+    G1 = dF^T cat and G = dF^T a2 (taps), conv_out's weight gradient contracted from them -- h is not needed -- and the
+    slot (dF, Wout_hat, handle gradient, G, G1, Wp, Wc) from which the block's backward takes everything g_h fed."""
+
+    @staticmethod
+    def forward(ctx, handle, w, gain_out, noisy, sigma, den: "Denoiser", pack):
+        a2, cat, wf2, wd2, wf11, wd11, a, b = pack
+        wh = den.conv_out.packs()[2]
+        Wc = ops.lowrank_expand_wc(wh, wd2)
+        Wp = ops.lowrank_expand_wc(wh, wd11).view(wh.shape[0], -1) if wd11 is not None else wh
+        D, Fraw = ops.lowrank_tail_fwd(a2, cat, Wc, Wp, b, a, gain_out, noisy, sigma, den.sigma_data,
+                                       want_fraw=any(ctx.needs_input_grad))
+        ctx.den, ctx.ab, ctx.hshape = den, (a, b), tuple(handle.shape)
+        ctx.save_for_backward(a2, cat, wh, gain_out, Fraw, sigma, Wc, Wp, wf2, wf11)
+        return D
+
+    @staticmethod
+    def backward(ctx, gD):
+        a2, cat, wh, gain_out, Fraw, sigma, Wc, Wp, wf2, wf11 = ctx.saved_tensors
+        a, b = ctx.ab
+        den = ctx.den
+        gp = den.gain_out
+        gdirect = gp.grad is not None and getattr(gp, "_edm_direct", False) and gp.grad.is_contiguous()
+        w = den.conv_out.weight
+        dD = gD.contiguous().float()
+        dF, aux = ops.lowrank_df(dD, Fraw, gain_out, sigma, den.sigma_data)
+        G1, gg = ops.lowrank_wgrad(dF, cat, 1, aux=aux, aux_out=gp.grad if gdirect else None)
+        if gdirect:
+            gg = None
+            for hook in getattr(gp, "_edm_hooks", ()):
+                hook(gp)
+        box = []
+
+        def reduce_and_contract():
+            G = ops.lowrank_wgrad(dF, a2, 9)[0]
+            box.extend((G, ops.lowrank_tail_dwout(G, wf2, G1, wf11, b, a)))
+        if w.grad is not None and getattr(w, "_edm_direct", False):
+            # (arena mode: off the backward's chain like every weight gradient; both results are only read there)
+            _run_on_side(w.device, reduce_and_contract, (dF, a2, G1))
+        else:
+            reduce_and_contract()
+        G, gwh = box
+        gx = torch.empty(ctx.hshape, device=dD.device, dtype=bf16)
+        _tail_slot[dD.device.index] = (dF, wh, gx, G, G1, Wp, Wc)
+        _queue_backward_end(dD.device)      # (empties the slot if the block's backward never runs)
+        gw = den.conv_out.finish_grad(gwh.view(1, 1, *gwh.shape))
+        return gx, gw, gg, None, None, None, None
+
+
 class Denoiser(nn.Module):
     def __init__(
         self,
@@ -1761,6 +1874,33 @@ class Denoiser(nn.Module):
 
     def _res_blocks(self):
         return list(self.encoder_blocks) + list(self.decoder_blocks)
+
+    def _conv_out_of(self, x: Tensor, noisy: Tensor, sig: Tensor) -> Tensor:
+        """conv_out + output preconditioning of the last decoder block's result x -- or, where that block (called with
+        _tail=self._tail_fwd_co()) left its operands in _tail_fwd_slot and returned a zero-size handle, the factored form"""
+        pack = _tail_fwd_slot.pop(x.device.index, None)
+        if pack is not None:
+            return _TailOutFn.apply(x, self.conv_out.weight, self.gain_out, noisy, sig, self, pack)
+        return _ConvOutFn.apply(x, self.conv_out.weight, self.gain_out, noisy, sig, self)
+
+    def _tail_fwd_co(self) -> int:
+        """conv_out's channel count when the last decoder block + conv_out may run in factored form (TAIL_FWD), else 0: the
+        dense launches.  The shapes are judged later, by the block's forward (_tail_fwd_shapes_ok)."""
+        if not (TAIL_FWD and TAIL_LOWRANK) or not len(self.decoder_blocks):
+            return 0
+        blk = self.decoder_blocks[-1]
+        if not (isinstance(blk, DecoderBlock) and blk._tail_last) or isinstance(blk.attention, CosineAttention):
+            return 0
+        for m in (blk, self.conv_out):      # a hook would see (or replace) the handle instead of the block's output
+            if m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or m._backward_pre_hooks:
+                return 0
+        if torch.is_grad_enabled():         # the backward writes these three gradients through the arena's finish queue
+            ws = [blk.conv_3x3_2.weight, self.conv_out.weight]
+            if isinstance(blk.conv_1x1, Conv2d):
+                ws.append(blk.conv_1x1.weight)
+            if not all(w.grad is not None and getattr(w, "_edm_direct", False) for w in ws):
+                return 0
+        return int(self.conv_out.weight.shape[0])
 
     def _modfin_table(self, blocks):
         """Device table of edm_mod_finish_multi ({gain ptr, d loss / d gain ptr, first column, channels} per block), or
@@ -2013,6 +2153,7 @@ class Denoiser(nn.Module):
         # of it into the left halves of those operands (no concat copy); the buffers exist before the decoder runs
         dests = _decoder_dests_impl(dec, skips, x) if FUSE_CAT and SKIP_GATE_FUSED else {}
         gates = self._decoder_gates(dec, skips, dests) if SG_MULTI else {}
+        tail_co = self._tail_fwd_co()
         for i, (block, has_skip) in enumerate(dec):
             skip = skips.pop() if has_skip else None
             dest = dests.get(i)
@@ -2024,8 +2165,9 @@ class Denoiser(nn.Module):
             cat_pre = getattr(x, "_edm_cat", None)
             if cat_pre is not None:
                 xin._edm_cat = cat_pre
-            x = block(xin, None, _tag(skip) if has_skip else None, _lin=lins[block], _dest=dest, _gate=gates.get(block))
-        D = _ConvOutFn.apply(x, self.conv_out.weight, self.gain_out, noisy, sig, self)
+            last = {"_tail": tail_co} if (tail_co and i + 1 == len(dec)) else {}
+            x = block(xin, None, _tag(skip) if has_skip else None, _lin=lins[block], _dest=dest, _gate=gates.get(block), **last)
+        D = self._conv_out_of(x, noisy, sig)
         if self.training:
             rng.step += 1
         return D.to(noisy_image.dtype)

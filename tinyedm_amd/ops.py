@@ -963,6 +963,78 @@ def lowrank_expand_slab(wout_hat, G, scale=1.0, Ipad=None):
     return slab
 
 
+@functools.lru_cache(maxsize=None)
+def lowrank_tail_supported(C, Cc, Co, W):
+    """lowrank_tail_fwd runs maps of width W (a2 with C channels, cat with Cc, Co outputs): its LDS tables fit.  A host
+    query, not a launch."""
+    return bool(_lib.lib().edm_lowrank_tail_supported(int(C), int(Cc), int(Co), int(W)))
+
+
+def lowrank_tail_fwd(a2, cat, Wc, Wp, sb, sa, gain_out, noisy, sigma, sigma_data, want_fraw=True):
+    """(D, Fraw) of conv_out_fwd for the block output h = sb * conv3x3(a2, W2) + sa * conv1x1(cat, W1) that is never formed:
+    Fraw = sb * conv3x3(a2, Wc) + sa * cat . Wp with Wc = lowrank_expand_wc(Wout_hat, dgrad pack of the 3x3 conv) and
+    Wp (fp32 [Co, Cc]) = Wout_hat . W1, or Wout_hat when the block has no 1x1 conv.  Deterministic."""
+    B, H, W, C = _nhwc(a2, "a2")
+    Cc = cat.shape[-1]
+    _chk(cat, bf16, "cat", (B, H, W, Cc))
+    Co = Wc.shape[0]
+    _chk(Wc, f32, "Wc", (Co, 9, C))
+    _chk(Wp, f32, "Wp", (Co, Cc))
+    _chk(noisy, f32, "noisy", (B, Co, H, W))
+    _chk(gain_out, f32, "gain_out")
+    ss = _sigma_arg(sigma, B)
+    D = torch.empty(B, Co, H, W, device=a2.device, dtype=f32)
+    Fraw = torch.empty(B, Co, H, W, device=a2.device, dtype=f32) if want_fraw else None
+    _lib.call("edm_lowrank_tail_fwd", _p(a2), _p(cat), _p(Wc), _p(Wp), float(sb), float(sa), _p(gain_out), _p(noisy),
+              _p(sigma), ss, float(sigma_data), _p(D), _p(Fraw), B, H, W, C, Cc, Co, _stream())
+    return D, Fraw
+
+
+def lowrank_tail_dwout_supported(C, Cc, Co, has1):
+    return bool(_lib.lib().edm_lowrank_tail_dwout_supported(int(C), int(Cc), int(Co), int(bool(has1))))
+
+
+def lowrank_tail_dwout(G, wf2, G1, wf1, sb, sa):
+    """conv_out's weight gradient (fp32 [Co, C], before the projection through its normalisation) without the block output:
+    sb * sum_{t, ci} W2[c, ci, t] G[o, t, ci] + sa * sum_cj W1[c, cj] G1[o, cj]; wf2 / wf1 = the plain bf16 forward packs
+    (taps, O, I) of the block's second 3x3 conv and of its 1x1 conv (None: the block has none, + sa * G1[o, c])."""
+    _chk(G, f32, "G")
+    Co, _, C = G.shape
+    _chk(G, f32, "G", (Co, 9, C))
+    if wf2.dim() != 3 or getattr(wf2, "_edm_frag", False):
+        raise ValueError("lowrank_tail_dwout: expected a plain (9, O, I) forward pack")
+    _chk(wf2, bf16, "wf2", (9, C, C))
+    Cc = G1.shape[-1]
+    _chk(G1, f32, "G1", (Co, 1, Cc))
+    if wf1 is not None:
+        _chk(wf1, bf16, "wf1", (1, C, Cc))
+    elif Cc != C:
+        raise ValueError("lowrank_tail_dwout: without a 1x1 pack G1 must have the block's channel count")
+    gwh = torch.empty(Co, C, device=G.device, dtype=f32)
+    _lib.call("edm_lowrank_tail_dwout", _p(G), _p(wf2), _p(G1), _p(wf1), float(sb), float(sa), _p(gwh), Co, C, Cc, _stream())
+    return gwh
+
+
+def lowrank_gcat_supported(Cc, Ci, Co):
+    return bool(_lib.lib().edm_lowrank_gcat_supported(int(Cc), int(Ci), int(Co)))
+
+
+def lowrank_gcat_add(dF, Wp, sa, t, Ci=None):
+    """d loss / d cat of the last block without conv_out's input gradient: bf16(t + sa * dF^T Wp), t (bf16 NHWC) the dense
+    part.  Ci: the split of conv_igemm(split=): returns (gu [.., Ci], gcs [.., Cc - Ci]); None: (the whole gradient, None)."""
+    B, H, W, Cc = _nhwc(t, "t")
+    _chk(dF, f32, "dF")
+    Co = dF.shape[1]
+    _chk(dF, f32, "dF", (B, Co, H, W))
+    _chk(Wp, f32, "Wp", (Co, Cc))
+    split = Ci is not None and Ci != Cc
+    Ci = Cc if not split else int(Ci)
+    gu = torch.empty(B, H, W, Ci, device=t.device, dtype=bf16)
+    gcs = torch.empty(B, H, W, Cc - Ci, device=t.device, dtype=bf16) if split else None
+    _lib.call("edm_lowrank_gcat_add", _p(dF), _p(Wp), float(sa), _p(t), _p(gu), _p(gcs), B, H * W, Cc, Ci, Co, _stream())
+    return gu, gcs
+
+
 def nchw_to_nhwc_bf16(x):
     _chk(x, f32, "x")
     B, C, H, W = x.shape
