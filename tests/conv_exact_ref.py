@@ -236,11 +236,13 @@ def one_hot_master(Cout, I):
 W3Layer = namedtuple("W3Layer", "x dy wm g0 perm scale accumulate G ref c0 star")
 
 
-def w3_layer(g, B, H, W, Cin, Cout, I=None, perm=False, scale=1.0, accumulate=False):
+def w3_layer(g, B, H, W, Cin, Cout, I=None, perm=False, scale=1.0, accumulate=False, master=None):
     """One layer of a group, as test_wgrad3_gpu._layer builds it but with integer operands and the one-hot master weight.
     G: the raw fp64 gradient w.r.t. the effective weight (exact integers, master order); ref: fp64 autograd through
     O.effective_weight, times scale, plus g0; c0 = 1 / (d sqrt(n)) of the one-hot row; star: mask of the e* elements.
-    g0 (accumulate) is uniform in [-2, 2]: the bound of the GPU test needs |g0| <= 5 |c0 scale G| wherever G != 0."""
+    g0 (accumulate) is uniform in [-2, 2]: the bound of the GPU test needs |g0| <= 5 |c0 scale G| wherever G != 0.
+    master: a callable (g, G) -> fp32 master weight (Cout, I, 3, 3) that replaces the one-hot rows; the reference is then
+    weights_ref.project in fp64 (O.effective_weight takes its norm in fp32), and c0 / star are None."""
     I = Cin if I is None else I
     x = _ints((B, Cin, H, W), WGRAD_LIM, g)
     if I < Cin:
@@ -260,8 +262,13 @@ def w3_layer(g, B, H, W, Cin, Cout, I=None, perm=False, scale=1.0, accumulate=Fa
     n = I * 9
     c0 = 1.0 / ((float(O.EPS) + 1.0 / n ** 0.5) * n ** 0.5)
     nhwc = lambda t: t.permute(0, 2, 3, 1).contiguous().to(bf16)
-    return W3Layer(nhwc(x), nhwc(dy), wm, g0, None if p is None else p.to(torch.int32), scale, accumulate,
-                   what.grad.clone(), w64.grad * scale + g0.double(), c0, wm.bool())
+    G, ref, star = what.grad.clone(), w64.grad * scale + g0.double(), wm.bool()
+    if master is not None:                          # (after every draw of the default form: the operands stay the same)
+        import weights_ref
+        wm = master(g, G)
+        ref = g0.double() + weights_ref.project(scale * G, wm.double())
+        c0 = star = None
+    return W3Layer(nhwc(x), nhwc(dy), wm, g0, None if p is None else p.to(torch.int32), scale, accumulate, G, ref, c0, star)
 
 
 @functools.lru_cache(maxsize=None)

@@ -332,7 +332,9 @@ __global__ __launch_bounds__(1024) void k_wgrad_finish(const float* __restrict__
     if (S <= 3) {
       // few slabs, long rows (the wide layers of the ImageNet nets: one work item per pass would have a single load
       // in flight): four vectors per thread per trip, all their loads issued together
-      const int items = E4;  // G == 1 here (host: 2G <= S fails for S <= 1; S in 2..3 gives G <= 1 when E4 >= 512)
+      // G is 1 or 2 here: the host loop stops at 2 G <= S, so S = 1 gives G = 1, and S in 2..3 gives G = 2 while
+      // E4 * 2 <= 1024 (rows of up to 2048 floats) and G = 1 for longer rows.  Nothing below relies on either value.
+      const int items = E4;
       for (int idx0 = threadIdx.x; idx0 < items * G; idx0 += 4 * blockDim.x) {
         f32x4 acc4[4];
         int e4s[4], sgs[4];
