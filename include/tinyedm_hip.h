@@ -599,12 +599,28 @@ int edm_nll_prior(const float* x, float t, int B, long CHW, double* part, double
  *   atomics: per-(sample, chunk) fp64 partials go to `part`, a DEVICE workspace of B * EDM_NLL_MAX_CHUNKS doubles, and a
  *   one-thread-per-sample finish launch adds them in index order.  A sample's chunking depends on CHW alone, so se[b] is
  *   bit-identical whatever B, the row or the memory path (dwordx4 when CHW % 4 == 0 and D, clean are 16-byte aligned).
- *   Same health bit when se[b] is non-finite. */
+ *   Same health bit when se[b] is non-finite.
+ * The class sweep (tinyedm_amd/classify.py): one network call holds P (image, level) pairs x C classes, row p * C + c is
+ * pair p under class c (the class index fastest).  Both are the kernels above with a row divisor C; C = 1 is the pair above.
+ * edm_eval_diffuse_classes: clean [P, CHW], ids / level DEVICE [P]; noisy [P * C, CHW] and sigma_out [P * C].  The noise
+ *   of a pair is drawn once per element and stored to its C rows: row p * C + c of noisy and sigma_out holds exactly the
+ *   bits edm_eval_diffuse writes for pair p, so the classes of an (image, level, draw) meet the same noise.  P * C < 2^31.
+ *   Level checking, health bit and memory paths as edm_eval_diffuse (dwordx4 when CHW % 4 == 0 and clean, noisy are
+ *   16-byte aligned: every row then is).
+ * edm_eval_sqerr_classes: se[p * C + c] = sum_j ((double)D_(p*C+c)j - (double)clean_pj)^2 with the bits edm_eval_sqerr
+ *   gives for row D[p * C + c] against clean[p] (chunking, thread-to-quad assignment, block reduction and finish order
+ *   are the same code); D contiguous [P * C, CHW], clean contiguous [P, CHW] and never replicated in memory,
+ *   P * C <= 65535; part: DEVICE workspace of P * C * EDM_NLL_MAX_CHUNKS doubles; se: DEVICE fp64 [P * C] slice, WRITTEN. */
 int edm_eval_diffuse(const float* clean, const unsigned* ids, const int* level, const float* sigmas, int L,
                      const void* rec, int B, long CHW, float* noisy, float* sigma_out, unsigned* health,
                      edm_stream_t stream);
 int edm_eval_sqerr(const float* D, const float* clean, int B, long CHW, double* part, double* se, unsigned* health,
                    edm_stream_t stream);
+int edm_eval_diffuse_classes(const float* clean, const unsigned* ids, const int* level, const float* sigmas, int L,
+                             const void* rec, int P, int C, long CHW, float* noisy, float* sigma_out, unsigned* health,
+                             edm_stream_t stream);
+int edm_eval_sqerr_classes(const float* D, const float* clean, int P, int C, long CHW, double* part, double* se,
+                           unsigned* health, edm_stream_t stream);
 int edm_scale_f32(const float* x, float s, float* y, long n, edm_stream_t stream);
 
 /* ---------------------------------------------------------------- reference-precision evaluation (eval_f32.hip)

@@ -134,6 +134,8 @@ SIGNATURES = {
     "edm_nll_prior": [P, F, I, L, P, P, P, P],
     "edm_eval_diffuse": [P, P, P, P, I, P, I, L, P, P, P, P],
     "edm_eval_sqerr": [P, P, I, L, P, P, P, P],
+    "edm_eval_diffuse_classes": [P, P, P, P, I, P, I, I, L, P, P, P, P],
+    "edm_eval_sqerr_classes": [P, P, I, I, L, P, P, P, P],
     "edm_scale_f32": [P, F, P, L, P],
     # restore.hip
     "edm_degrade": [P, P, I, I, I, I, I, I, P],

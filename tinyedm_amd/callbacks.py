@@ -250,21 +250,15 @@ class ModelCheckpoint:
             self._maybe_save(trainer, pl_module)
 
 
-class LossByNoiseLevel:
-    """Every ``every_n_epochs`` validation epochs: the denoising loss of the first ``num_images`` validation images at
-    fixed noise levels with fixed noise (evaluate.NoiseLevelEvaluator; ``evaluator_kwargs`` are its constructor's), under
-    the weights validation is using (the EMA callback has them swapped in at this hook).  Logs ``val_expected_loss`` (the
-    mean loss over explicit ``sigmas``, which have no expected loss) and ``val_loss_sigma/<level>``.  Unlike ``val_loss``
-    the numbers depend on the weights alone: the images, the levels and the noise are the same at every epoch.
-    Additive: nothing runs unless the callback is configured."""
+class _FirstValidationImages:
+    """the first ``num_images`` validation images, taken once and sharded over the ranks by id (id = rank mod world): the
+    fixed evaluation set of LossByNoiseLevel and ClassifierAccuracy"""
 
-    def __init__(self, num_images: int = 1024, every_n_epochs: int = 1, **evaluator_kwargs):
-        from .evaluate import NoiseLevelEvaluator
+    def __init__(self, num_images: int, every_n_epochs: int):
         for name, v in (("num_images", num_images), ("every_n_epochs", every_n_epochs)):
             if isinstance(v, bool) or not isinstance(v, int) or v < 1:
-                raise ValueError(f"LossByNoiseLevel: {name} must be an integer >= 1, got {v!r}")
+                raise ValueError(f"{type(self).__name__}: {name} must be an integer >= 1, got {v!r}")
         self.num_images, self.every_n_epochs = num_images, every_n_epochs
-        self.evaluator = NoiseLevelEvaluator(**evaluator_kwargs)
         self.images = self.labels = self.ids = self.last = None
 
     def _take(self, trainer, pl_module):
@@ -277,7 +271,7 @@ class LossByNoiseLevel:
             self.labels = ds[1][:n]
             return
         if dm is None or not hasattr(dm, "val_dataloader"):
-            raise RuntimeError("LossByNoiseLevel: the trainer has no datamodule with a val_dataloader")
+            raise RuntimeError(f"{type(self).__name__}: the trainer has no datamodule with a val_dataloader")
         xs, ys, have = [], [], 0
         for batch in dm.val_dataloader():
             xs.append(batch[0].float())
@@ -288,20 +282,66 @@ class LossByNoiseLevel:
         self.images = torch.cat(xs)[:self.num_images].to(pl_module.device).contiguous()
         self.labels = torch.cat(ys)[:self.num_images].to(pl_module.device)
 
-    def on_validation_epoch_end(self, trainer, pl_module):
+    def _due(self, trainer, pl_module) -> bool:
+        """whether this epoch evaluates; takes and shards the images the first time it does"""
         if trainer.current_epoch % self.every_n_epochs != 0:
-            return
+            return False
         if self.images is None:
             self._take(trainer, pl_module)
             world, rank = getattr(trainer, "world_size", 1), getattr(trainer, "global_rank", 0)
-            if world > 1:       # every rank took the same images: each keeps its share, the evaluator merges the sums
+            if world > 1:       # every rank took the same images: each keeps its share, the evaluation merges the sums
                 keep = torch.arange(self.images.shape[0], device=self.images.device) % world == rank
                 self.ids = torch.arange(self.images.shape[0])[keep.cpu()]
                 self.images, self.labels = self.images[keep].contiguous(), self.labels[keep]
+        return True
+
+
+class LossByNoiseLevel(_FirstValidationImages):
+    """Every ``every_n_epochs`` validation epochs: the denoising loss of the first ``num_images`` validation images at
+    fixed noise levels with fixed noise (evaluate.NoiseLevelEvaluator; ``evaluator_kwargs`` are its constructor's), under
+    the weights validation is using (the EMA callback has them swapped in at this hook).  Logs ``val_expected_loss`` (the
+    mean loss over explicit ``sigmas``, which have no expected loss) and ``val_loss_sigma/<level>``.  Unlike ``val_loss``
+    the numbers depend on the weights alone: the images, the levels and the noise are the same at every epoch.
+    Additive: nothing runs unless the callback is configured."""
+
+    def __init__(self, num_images: int = 1024, every_n_epochs: int = 1, **evaluator_kwargs):
+        from .evaluate import NoiseLevelEvaluator
+        super().__init__(num_images, every_n_epochs)
+        self.evaluator = NoiseLevelEvaluator(**evaluator_kwargs)
+
+    def on_validation_epoch_end(self, trainer, pl_module):
+        if not self._due(trainer, pl_module):
+            return
         labels = self.labels if getattr(pl_module, "conditional", False) else None
         res = self.evaluator.evaluate(pl_module, self.images, labels, self.ids)
         self.last = res
         total = res["expected_loss"] if res["expected_loss"] is not None else res["mean_loss"]
         for name, v in [("val_expected_loss", total)] + [(f"val_loss_sigma/{l}", v) for l, v in enumerate(res["loss"])]:
+            pl_module.log(name, v)
+            trainer.callback_metrics[name] = float(v)
+
+
+class ClassifierAccuracy(_FirstValidationImages):
+    """Every ``every_n_epochs`` validation epochs: the diffusion-classifier accuracy of the first ``num_images`` validation
+    images (classify.DiffusionClassifier; ``classifier_kwargs`` are its constructor's), under the weights validation is
+    using: how often the class with the lowest conditional denoising error is the image's own.  Logs ``val_class_acc``
+    and ``val_class_acc_sigma/<level>`` (the accuracy of each level alone), so
+    ``ModelCheckpoint(monitor="val_class_acc", mode="max")`` works.  The images, the levels and the noise are the same at
+    every epoch.  Needs a class-conditional model.  Additive: nothing runs unless the callback is configured."""
+
+    def __init__(self, num_images: int = 1024, every_n_epochs: int = 1, **classifier_kwargs):
+        from .classify import DiffusionClassifier
+        super().__init__(num_images, every_n_epochs)
+        self.classifier = DiffusionClassifier(**classifier_kwargs)
+
+    def on_validation_epoch_end(self, trainer, pl_module):
+        if not getattr(pl_module, "conditional", False):
+            raise RuntimeError("ClassifierAccuracy: the model is unconditional: it has no classes to tell apart")
+        if not self._due(trainer, pl_module):
+            return
+        res = self.classifier.classify(pl_module, self.images, self.labels, self.ids)
+        self.last = res
+        for name, v in [("val_class_acc", res["accuracy"])] + [(f"val_class_acc_sigma/{l}", v)
+                                                               for l, v in enumerate(res["level_accuracy"])]:
             pl_module.log(name, v)
             trainer.callback_metrics[name] = float(v)

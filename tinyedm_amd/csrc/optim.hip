@@ -761,50 +761,55 @@ inline int nll_chunks(long CHW) {
 // probes) and from the 16-bit tags 0xD1FF / 0x5167 (high half 0).  The noise of (id, level, draw) depends neither on B,
 // on the row, on the row's neighbours nor on the memory path.  A level outside [0, L) is never used as an index: the
 // sample's sigma and outputs become NaN and the health bit is set (ops refuses such a level before the launch).
+// C (the row divisor of the class sweep, classify.py): pair b is drawn once per element and stored to the C rows b * C + c
+// of noisy / sigma_out, each with the bits of the C = 1 form; edm_eval_diffuse is C = 1.
 template <bool VEC>
 __global__ __launch_bounds__(256) void k_eval_diffuse(const float* __restrict__ clean, const uint32_t* __restrict__ ids,
                                                       const int* __restrict__ level, const float* __restrict__ sigmas,
-                                                      int L, const uint32_t* __restrict__ rec, int B, long CHW,
+                                                      int L, const uint32_t* __restrict__ rec, int B, int C, long CHW,
                                                       float* __restrict__ noisy, float* __restrict__ sigma_out,
                                                       unsigned* __restrict__ health) {
   const uint32_t seed_lo = rec[0], seed_hi = rec[1], draw = rec[2];
   const long nq = (CHW + 3) / 4, total = (long)B * nq;
   bool bad = false;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const long b = i / nq, q = i - b * nq, e = b * CHW + 4 * q;
+    const long b = i / nq, q = i - b * nq;
     const int lv = level[b];
     const bool lv_ok = lv >= 0 && lv < L;
     const float s = lv_ok ? sigmas[lv] : __builtin_nanf("");
-    if (q == 0) sigma_out[b] = s;
+    if (q == 0)
+      for (int c = 0; c < C; ++c) sigma_out[b * C + c] = s;
     bad |= !lv_ok;
     const Philox4 r = philox4x32_10((uint32_t)q, ids[b], 0x45560000u ^ (uint32_t)lv, draw, seed_lo, seed_hi);
     float nn[4], xv[4], ov[4];
     box_muller(r.x, r.y, nn[0], nn[1]);
     box_muller(r.z, r.w, nn[2], nn[3]);
     const int m = VEC ? 4 : (int)(CHW - 4 * q < 4 ? CHW - 4 * q : 4);
-    nll_load4<VEC>(clean + e, m, xv);
+    nll_load4<VEC>(clean + b * CHW + 4 * q, m, xv);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       ov[k] = fmaf(s, nn[k], xv[k]);
       bad |= k < m && !(fabsf(ov[k]) <= 3.0e38f);
     }
-    nll_store4<VEC>(noisy + e, m, ov);
+    for (int c = 0; c < C; ++c) nll_store4<VEC>(noisy + (b * C + c) * CHW + 4 * q, m, ov);
   }
   if (health && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(health, 2u);
 }
 // part[b][chunk] = this chunk's share of sum_j ((double)D_bj - (double)clean_bj)^2.  The difference of two fp32 values
 // is exact in fp64.  grid (nll_chunks(CHW), B): a sample's chunking, and with it the order of every add, depends on CHW
 // alone, so se[b] has the same bits whatever B, the row or the memory path (the padding of a partial quad adds +0.0).
+// C (the row divisor of the class sweep): row b of D is compared with row b / C of clean, which is never replicated;
+// edm_eval_sqerr is C = 1.
 template <bool VEC>
-__global__ __launch_bounds__(256) void k_eval_sqerr(const float* __restrict__ D, const float* __restrict__ clean,
+__global__ __launch_bounds__(256) void k_eval_sqerr(const float* __restrict__ D, const float* __restrict__ clean, int C,
                                                     long CHW, double* __restrict__ part) {
-  const long nq = (CHW + 3) / 4, b = blockIdx.y;
+  const long nq = (CHW + 3) / 4, b = blockIdx.y, p = b / C;
   double acc = 0.0;
   for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
     const int m = VEC ? 4 : (int)(CHW - 4 * q < 4 ? CHW - 4 * q : 4);
     float dv[4], cv[4];
     nll_load4<VEC>(D + b * CHW + 4 * q, m, dv);
-    nll_load4<VEC>(clean + b * CHW + 4 * q, m, cv);
+    nll_load4<VEC>(clean + p * CHW + 4 * q, m, cv);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const double d = (double)dv[k] - (double)cv[k];
@@ -999,6 +1004,29 @@ extern "C" int edm_heun_churn(const float* x, float c, const void* rec, int step
   EDM_CHECK_LAUNCH("heun_churn");
   return EDM_OK;
 }
+inline void launch_eval_diffuse(const float* clean, const unsigned* ids, const int* level, const float* sigmas, int L,
+                                const void* rec, int P, int C, long CHW, float* noisy, float* sigma_out,
+                                unsigned* health, hipStream_t st) {
+  const dim3 grid(grid_for((long)P * ((CHW + 3) / 4), 256)), block(256);
+  if (CHW % 4 == 0 && aligned16({clean, noisy}))
+    hipLaunchKernelGGL(k_eval_diffuse<true>, grid, block, 0, st, clean, (const uint32_t*)ids, level, sigmas, L,
+                       (const uint32_t*)rec, P, C, CHW, noisy, sigma_out, health);
+  else
+    hipLaunchKernelGGL(k_eval_diffuse<false>, grid, block, 0, st, clean, (const uint32_t*)ids, level, sigmas, L,
+                       (const uint32_t*)rec, P, C, CHW, noisy, sigma_out, health);
+}
+// rows = the rows of D and se; row b is compared with row b / C of clean
+inline void launch_eval_sqerr(const float* D, const float* clean, int rows, int C, long CHW, double* part, double* se,
+                              unsigned* health, hipStream_t st) {
+  const int chunks = nll_chunks(CHW);
+  const dim3 grid(chunks, rows), block(256);
+  if (CHW % 4 == 0 && aligned16({D, clean}))
+    hipLaunchKernelGGL(k_eval_sqerr<true>, grid, block, 0, st, D, clean, C, CHW, part);
+  else
+    hipLaunchKernelGGL(k_eval_sqerr<false>, grid, block, 0, st, D, clean, C, CHW, part);
+  hipLaunchKernelGGL(k_eval_sqerr_finish, dim3((rows + 63) / 64), dim3(64), 0, st, (const double*)part, chunks, rows, se,
+                     health);
+}
 // ids [B] uint32, level [B] int32, sigmas [L] float: DEVICE arrays; rec: the churn's device record with the draw in word 2
 extern "C" int edm_eval_diffuse(const float* clean, const unsigned* ids, const int* level, const float* sigmas, int L,
                                 const void* rec, int B, long CHW, float* noisy, float* sigma_out, unsigned* health,
@@ -1006,13 +1034,7 @@ extern "C" int edm_eval_diffuse(const float* clean, const unsigned* ids, const i
   EDM_REQUIRE(clean && ids && level && sigmas && rec && noisy && sigma_out && B > 0 && CHW > 0 && L >= 1 && L <= 65535,
               "eval_diffuse: bad args (1 <= L <= 65535)");
   EDM_REQUIRE((CHW + 3) / 4 <= 0xFFFFFFFFL, "eval_diffuse: CHW / 4 must fit the 32-bit Philox counter word");
-  const dim3 grid(grid_for((long)B * ((CHW + 3) / 4), 256)), block(256);
-  if (CHW % 4 == 0 && aligned16({clean, noisy}))
-    hipLaunchKernelGGL(k_eval_diffuse<true>, grid, block, 0, st, clean, (const uint32_t*)ids, level, sigmas, L,
-                       (const uint32_t*)rec, B, CHW, noisy, sigma_out, health);
-  else
-    hipLaunchKernelGGL(k_eval_diffuse<false>, grid, block, 0, st, clean, (const uint32_t*)ids, level, sigmas, L,
-                       (const uint32_t*)rec, B, CHW, noisy, sigma_out, health);
+  launch_eval_diffuse(clean, ids, level, sigmas, L, rec, B, 1, CHW, noisy, sigma_out, health, st);
   EDM_CHECK_LAUNCH("eval_diffuse");
   return EDM_OK;
 }
@@ -1020,15 +1042,29 @@ extern "C" int edm_eval_diffuse(const float* clean, const unsigned* ids, const i
 extern "C" int edm_eval_sqerr(const float* D, const float* clean, int B, long CHW, double* part, double* se,
                               unsigned* health, hipStream_t st) {
   EDM_REQUIRE(D && clean && part && se && B > 0 && B <= 65535 && CHW > 0, "eval_sqerr: bad args (B <= 65535)");
-  const int chunks = nll_chunks(CHW);
-  const dim3 grid(chunks, B), block(256);
-  if (CHW % 4 == 0 && aligned16({D, clean}))
-    hipLaunchKernelGGL(k_eval_sqerr<true>, grid, block, 0, st, D, clean, CHW, part);
-  else
-    hipLaunchKernelGGL(k_eval_sqerr<false>, grid, block, 0, st, D, clean, CHW, part);
+  launch_eval_sqerr(D, clean, B, 1, CHW, part, se, health, st);
   EDM_CHECK_LAUNCH("eval_sqerr");
-  hipLaunchKernelGGL(k_eval_sqerr_finish, dim3((B + 63) / 64), dim3(64), 0, st, (const double*)part, chunks, B, se, health);
-  EDM_CHECK_LAUNCH("eval_sqerr (finish)");
+  return EDM_OK;
+}
+// the class sweep (classify.py): P pairs x C classes, row p * C + c; ids / level [P]; noisy [P * C, CHW], sigma_out [P * C]
+extern "C" int edm_eval_diffuse_classes(const float* clean, const unsigned* ids, const int* level, const float* sigmas,
+                                        int L, const void* rec, int P, int C, long CHW, float* noisy, float* sigma_out,
+                                        unsigned* health, hipStream_t st) {
+  EDM_REQUIRE(clean && ids && level && sigmas && rec && noisy && sigma_out && P > 0 && C > 0 && CHW > 0 && L >= 1 &&
+                  L <= 65535 && (long)P * C <= 0x7FFFFFFFL,
+              "eval_diffuse_classes: bad args (1 <= L <= 65535, P * C < 2^31)");
+  EDM_REQUIRE((CHW + 3) / 4 <= 0xFFFFFFFFL, "eval_diffuse_classes: CHW / 4 must fit the 32-bit Philox counter word");
+  launch_eval_diffuse(clean, ids, level, sigmas, L, rec, P, C, CHW, noisy, sigma_out, health, st);
+  EDM_CHECK_LAUNCH("eval_diffuse_classes");
+  return EDM_OK;
+}
+// part: device workspace of P * C * EDM_NLL_MAX_CHUNKS doubles; se: device fp64 [P * C], written; clean [P, CHW]
+extern "C" int edm_eval_sqerr_classes(const float* D, const float* clean, int P, int C, long CHW, double* part,
+                                      double* se, unsigned* health, hipStream_t st) {
+  EDM_REQUIRE(D && clean && part && se && P > 0 && C > 0 && (long)P * C <= 65535 && CHW > 0,
+              "eval_sqerr_classes: bad args (P * C <= 65535)");
+  launch_eval_sqerr(D, clean, P * C, C, CHW, part, se, health, st);
+  EDM_CHECK_LAUNCH("eval_sqerr_classes");
   return EDM_OK;
 }
 // Dg and w both given (guided) or both null; m2 needs m1; m_out nullable.  x_out and m_out alias no operand.

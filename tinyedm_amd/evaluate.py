@@ -115,6 +115,26 @@ def level_stats(sums, sigmas, sigma_data: float) -> dict:
     return out
 
 
+def check_images(images, labels, ids, who: str = "evaluate"):
+    """the operands of an evaluation -> (contiguous fp32 NCHW images on the GPU, labels [N] on their device or None,
+    ids as int64 [N] on the host: given, or 0 .. N - 1)"""
+    if not isinstance(images, torch.Tensor) or not images.is_cuda or images.dtype != torch.float32 or images.dim() != 4:
+        raise ValueError(f"{who}: images must be an fp32 NCHW tensor on the GPU")
+    N, dev = images.shape[0], images.device
+    if N == 0 or images[0].numel() == 0:
+        raise ValueError(f"{who}: no images")
+    images = images.contiguous()
+    ids_h = np.arange(N, dtype=np.int64) if ids is None else np.asarray(
+        ids.detach().cpu() if isinstance(ids, torch.Tensor) else ids).astype(np.int64).reshape(-1)
+    if ids_h.shape[0] != N or ids_h.min() < 0 or ids_h.max() >= 1 << 32 or np.unique(ids_h).shape[0] != N:
+        raise ValueError(f"{who}: ids must be {N} distinct integers in [0, 2**32)")
+    if labels is not None:
+        if not isinstance(labels, torch.Tensor) or labels.numel() != N:
+            raise ValueError(f"{who}: labels must be a tensor of {N} class indices")
+        labels = labels.to(dev).reshape(N)
+    return images, labels, ids_h
+
+
 # ---------------------------------------------------------------------------------------------------- the evaluator
 class NoiseLevelEvaluator:
     """evaluate(model, images, labels=None, ids=None) -> the per-level denoising error of `images` (see the module text).
@@ -164,20 +184,8 @@ class NoiseLevelEvaluator:
     def evaluate(self, model, images, labels=None, ids=None) -> dict:
         from . import ops
         from .callbacks import _eval_dtype
-        if not isinstance(images, torch.Tensor) or not images.is_cuda or images.dtype != torch.float32 or images.dim() != 4:
-            raise ValueError("evaluate: images must be an fp32 NCHW tensor on the GPU")
+        images, labels, ids_h = check_images(images, labels, ids)
         N, dev = images.shape[0], images.device
-        if N == 0 or images[0].numel() == 0:
-            raise ValueError("evaluate: no images")
-        images = images.contiguous()
-        ids_h = np.arange(N, dtype=np.int64) if ids is None else np.asarray(
-            ids.detach().cpu() if isinstance(ids, torch.Tensor) else ids).astype(np.int64).reshape(-1)
-        if ids_h.shape[0] != N or ids_h.min() < 0 or ids_h.max() >= 1 << 32 or np.unique(ids_h).shape[0] != N:
-            raise ValueError(f"evaluate: ids must be {N} distinct integers in [0, 2**32)")
-        if labels is not None:
-            if not isinstance(labels, torch.Tensor) or labels.numel() != N:
-                raise ValueError(f"evaluate: labels must be a tensor of {N} class indices")
-            labels = labels.to(dev).reshape(N)
         sigmas = [float(np.float32(s)) for s in self.levels_for(model)]     # what the kernel and the network see
         L, R, chw = len(sigmas), self.num_draws, images[0].numel()
         sigma_data = float(getattr(model, "sigma_data", self.sigma_data))
@@ -279,37 +287,42 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
-def check_args(args) -> NoiseLevelEvaluator:
-    """every choice that needs nothing loaded, checked before a checkpoint or the GPU is touched; returns the evaluator"""
+def check_data_args(args, who: str = "evaluate") -> None:
+    """the data, label and checkpoint flags, which need nothing loaded"""
     if (args.dataset is None) == (args.image_dir is None):
-        raise ValueError("evaluate: give exactly one data source: --dataset cifar10|mnist --data_dir DIR, or --image_dir DIR")
+        raise ValueError(f"{who}: give exactly one data source: --dataset cifar10|mnist --data_dir DIR, or --image_dir DIR")
     if args.dataset is not None:
         if args.data_dir is None:
-            raise ValueError("evaluate: --dataset needs --data_dir")
+            raise ValueError(f"{who}: --dataset needs --data_dir")
         for flag in ("labels_json", "mean", "std", "image_size", "in_channels"):
             if getattr(args, flag) is not None:
-                raise ValueError(f"evaluate: --{flag} goes with --image_dir (the built-in datasets carry their own)")
+                raise ValueError(f"{who}: --{flag} goes with --image_dir (the built-in datasets carry their own)")
     else:
         if args.data_dir is not None:
-            raise ValueError("evaluate: --data_dir goes with --dataset")
+            raise ValueError(f"{who}: --data_dir goes with --dataset")
         if args.image_size is None or args.image_size < 1:
-            raise ValueError("evaluate: --image_dir needs --image_size")
+            raise ValueError(f"{who}: --image_dir needs --image_size")
         if (args.mean is None) != (args.std is None):
-            raise ValueError("evaluate: --mean and --std go together")
+            raise ValueError(f"{who}: --mean and --std go together")
         if args.in_channels is not None and args.in_channels < 1:
-            raise ValueError(f"evaluate: --in_channels must be >= 1, got {args.in_channels}")
+            raise ValueError(f"{who}: --in_channels must be >= 1, got {args.in_channels}")
         if args.mean is not None and args.in_channels is not None and not (
                 len(args.mean) == len(args.std) == args.in_channels):
-            raise ValueError("evaluate: --mean and --std need one value per channel")
+            raise ValueError(f"{who}: --mean and --std need one value per channel")
     if isinstance(args.num_images, bool) or not isinstance(args.num_images, int) or args.num_images < 1:
-        raise ValueError(f"evaluate: --num_images must be an integer >= 1, got {args.num_images!r}")
+        raise ValueError(f"{who}: --num_images must be an integer >= 1, got {args.num_images!r}")
     if len(set(args.ckpt_path)) != len(args.ckpt_path):
-        raise ValueError("evaluate: --ckpt_path names a checkpoint twice")
+        raise ValueError(f"{who}: --ckpt_path names a checkpoint twice")
+
+
+def check_args(args) -> NoiseLevelEvaluator:
+    """every choice that needs nothing loaded, checked before a checkpoint or the GPU is touched; returns the evaluator"""
+    check_data_args(args)
     return NoiseLevelEvaluator(sigmas=args.sigmas, num_levels=args.num_levels, seed=args.seed, num_draws=args.num_draws,
                                batch_size=args.batch_size, network_dtype=args.network_dtype)
 
 
-def _load_data(args, model, dev):
+def _load_data(args, model, dev, who: str = "evaluate"):
     """(images fp32 NCHW on dev, labels or None): the first --num_images of the source"""
     from . import ops
     if args.dataset is not None:
@@ -330,7 +343,7 @@ def _load_data(args, model, dev):
             labels = json.load(f)
         if not isinstance(labels, list) or len(labels) < images.shape[0] or not all(
                 isinstance(v, int) and not isinstance(v, bool) and v >= 0 for v in labels):
-            raise ValueError(f"evaluate: --labels_json must hold a list of at least {images.shape[0]} class indices")
+            raise ValueError(f"{who}: --labels_json must hold a list of at least {images.shape[0]} class indices")
         labels = torch.tensor(labels[:images.shape[0]], dtype=torch.int64, device=dev)
     return images.to(dev), labels
 

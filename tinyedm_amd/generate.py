@@ -81,6 +81,11 @@ ground truth in pixel units, ...}.  Exclusive with `--mask_box`, `--invert_to` a
     python -m tinyedm.generate --ckpt_path last.ckpt --load_ema --init_dir photos --restore_scale 4 \\
         --save_degraded lowres --restore_report sr.json --output_dir restored --num_samples 64 --image_size 32 \\
         --num_classes 10 --batch_size 64
+`--labels_to FILE.json` (plain, guided, churned and multistep sampling of a class-conditional checkpoint; not with
+`--init_dir`) records the labels the samples were drawn for: rank 0 writes the JSON list of the class indices of the
+written `<index>.png` files, in index order, which is what `--labels_json` of `tinyedm.evaluate` and `tinyedm.classify`
+reads.  `python -m tinyedm.classify --image_dir samples --labels_json FILE.json ...` then measures how often the
+sampler produced the class it was asked for.  Without the flag nothing changes.
 Multi-GPU = replicas only: under `python -m torch.distributed.run --nproc-per-node N` every rank samples
 its own contiguous index range with its own noise seed and writes `<global index>.png`; there is no collective.
 """
@@ -149,6 +154,27 @@ def _check_conditioning(init_dir, start_step, mask_box, invert_to, solver, S_chu
                          "evaluation error is meaningless)")
 
 
+def _check_labels_to(labels_to, init_dir) -> None:
+    """the label record's choices that need nothing loaded"""
+    if labels_to is not None and init_dir is not None:
+        raise ValueError("generate: --labels_to records the labels of plain sampling; it does not combine with --init_dir")
+
+
+def _drawn_labels(batch_size, num_workers, image_size, num_samples, num_classes, in_channels, seed, world) -> list:
+    """the class indices of samples 0 .. num_samples - 1 in index order.  A sample's label is a function of the seed, its
+    rank and its batch alone (RandomNoiseDataModule), so one rank replays every rank's draws on the host: no collective"""
+    from .datamodules import RandomNoiseDataModule
+    per_rank = (num_samples + world - 1) // world
+    labels = []
+    for r in range(world):
+        n_r = max(0, min(per_rank, num_samples - r * per_rank))
+        dm = RandomNoiseDataModule(batch_size, num_workers, image_size, n_r, num_classes, in_channels=in_channels,
+                                   seed=seed + 1000003 * r, device="cpu")
+        for batch in dm.predict_dataloader():
+            labels.extend(int(v) for v in batch[1].flatten())
+    return labels
+
+
 RESTORE_SCALES = (1, 2, 4, 8)
 
 
@@ -215,7 +241,7 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
              guidance_interval=None, S_churn=0.0, S_min=0.0, S_max=float("inf"), S_noise=1.0, solver="heun",
              solver_order=2, init_dir=None, start_step=0, mask_box=None, invert_to=None, likelihood_to=None,
              num_probes=1, dequantize=False, restore_scale=1, restore_gray=False, save_degraded=None,
-             restore_report=None) -> None:
+             restore_report=None, labels_to=None) -> None:
     from .callbacks import PreditionWriter
     from .datamodules import RandomNoiseDataModule
     from .edm import EDM
@@ -228,12 +254,15 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
                         dequantize=dequantize)
     restoring = _check_restoration(init_dir, restore_scale, restore_gray, save_degraded, restore_report, mask_box,
                                    invert_to, likelihood_to, image_size)
+    _check_labels_to(labels_to, init_dir)
 
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
     dev = torch.device("cuda", torch.cuda.current_device())
     if model is None:
         model = EDM.load_from_checkpoint(ckpt_path, load_ema=load_ema)
+    if labels_to is not None and not model.conditional:
+        raise ValueError("generate: --labels_to needs a class-conditional checkpoint: this one draws no labels")
     model = model.to(dev)
     model.denoiser.set_eval_dtype(network_dtype)
     if guide_ckpt_path is not None:
@@ -367,6 +396,11 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
     if n_local > 0:
         trainer.predict(model, datamodule=datamodule, return_predictions=False, ckpt_path=None, distributed=False)   # generate.py:45-47
     print(f"[rank {rank}] wrote images {first}..{first + n_local - 1} to {output_dir}", flush=True)
+    if labels_to is not None and rank == 0:
+        import json
+        with open(labels_to, "w") as f:
+            json.dump(_drawn_labels(batch_size, num_workers, image_size, num_samples, num_classes, C, seed, world), f)
+        print(f"[rank 0] wrote the labels of images 0..{num_samples - 1} to {labels_to}", flush=True)
 
 
 def main(argv=None):
@@ -444,9 +478,13 @@ def main(argv=None):
                         help="restoration: write A+ y, the measurement replicated to the image grid, as <index>.png")
     parser.add_argument("--restore_report", type=str, default=None, metavar="OUT.json",
                         help="restoration: write max |A x - y| and the mean PSNR of the restored images and of A+ y")
+    parser.add_argument("--labels_to", type=str, default=None, metavar="FILE.json",
+                        help="write the class indices the samples were drawn for, in index order (the format "
+                             "--labels_json of tinyedm.classify reads); class-conditional checkpoints, not with --init_dir")
     args = parser.parse_args(argv)
     _check_solver(args.solver, args.S_churn)
     try:
+        _check_labels_to(args.labels_to, args.init_dir)
         _check_restoration(args.init_dir, args.restore_scale, args.restore_gray, args.save_degraded,
                            args.restore_report, args.mask_box, args.invert_to, args.likelihood_to, args.image_size)
         _check_conditioning(args.init_dir, args.start_step, args.mask_box, args.invert_to, args.solver, args.S_churn,
@@ -489,7 +527,7 @@ def main(argv=None):
              init_dir=args.init_dir, start_step=args.start_step, mask_box=args.mask_box, invert_to=args.invert_to,
              likelihood_to=args.likelihood_to, num_probes=args.num_probes, dequantize=args.dequantize,
              restore_scale=args.restore_scale, restore_gray=args.restore_gray, save_degraded=args.save_degraded,
-             restore_report=args.restore_report)
+             restore_report=args.restore_report, labels_to=args.labels_to)
 
 
 if __name__ == "__main__":

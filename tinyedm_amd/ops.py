@@ -2215,12 +2215,8 @@ def _chk_eval(t, dtype, name, shape=None, device=None):
         raise ValueError(f"{name}: expected a tensor on {device}, got {t.device}")
 
 
-def eval_diffuse(clean, ids, level, sigmas, rec, check_levels=True):
-    """noisy_b = clean_b + sigmas[level[b]] * n with n ~ N(0, 1) drawn in the kernel for the IMAGE ids[b]: the noise depends
-    only on (seed, draw, ids[b], level[b], element), not on the batch or the row.  clean: contiguous fp32 [B, ...]; ids:
-    uint32 [B]; level: int32 [B] with values in [0, L); sigmas: fp32 [L], L <= 65535; rec: ops.churn_record(seed, draw).
-    Returns (noisy, sigma [B] fp32).  The level range is checked on the host before the launch (one device read);
-    check_levels=False is for a caller that built `level` itself from values it has already checked."""
+def _eval_diffuse_args(clean, ids, level, sigmas, rec, check_levels):
+    """the operand checks eval_diffuse and eval_diffuse_classes share -> (pairs, levels)"""
     _chk_eval(clean, f32, "clean")
     if clean.dim() < 2 or clean.numel() == 0:
         raise ValueError(f"clean: expected a non-empty [B, ...] tensor, got {tuple(clean.shape)}")
@@ -2239,6 +2235,16 @@ def eval_diffuse(clean, ids, level, sigmas, rec, check_levels=True):
         lo, hi = (int(v) for v in torch.aminmax(level))
         if lo < 0 or hi >= L:
             raise ValueError(f"level: values must be in [0, {L}), got [{lo}, {hi}]")
+    return B, L
+
+
+def eval_diffuse(clean, ids, level, sigmas, rec, check_levels=True):
+    """noisy_b = clean_b + sigmas[level[b]] * n with n ~ N(0, 1) drawn in the kernel for the IMAGE ids[b]: the noise depends
+    only on (seed, draw, ids[b], level[b], element), not on the batch or the row.  clean: contiguous fp32 [B, ...]; ids:
+    uint32 [B]; level: int32 [B] with values in [0, L); sigmas: fp32 [L], L <= 65535; rec: ops.churn_record(seed, draw).
+    Returns (noisy, sigma [B] fp32).  The level range is checked on the host before the launch (one device read);
+    check_levels=False is for a caller that built `level` itself from values it has already checked."""
+    B, L = _eval_diffuse_args(clean, ids, level, sigmas, rec, check_levels)
     noisy = torch.empty_like(clean)
     sigma = torch.empty(B, dtype=f32, device=clean.device)
     _lib.call("edm_eval_diffuse", _p(clean), _p(ids), _p(level), _p(sigmas), L, _p(rec), B, clean.numel() // B,
@@ -2264,6 +2270,51 @@ def eval_sqerr(D, clean, out=None):
     part = torch.empty(B * NLL_MAX_CHUNKS, dtype=torch.float64, device=clean.device)
     _lib.call("edm_eval_sqerr", _p(D), _p(clean), B, clean.numel() // B, _p(part), _p(out), _p(health(clean.device)),
               _stream())
+    return out
+
+
+def _chk_classes(num_classes):
+    if isinstance(num_classes, bool) or not isinstance(num_classes, int) or num_classes < 1:
+        raise ValueError(f"num_classes must be an integer >= 1, got {num_classes!r}")
+    return num_classes
+
+
+def eval_diffuse_classes(clean, ids, level, sigmas, rec, num_classes, check_levels=True):
+    """eval_diffuse for the class sweep: the noise of pair p is drawn once and stored to the C = num_classes rows
+    p * C + c of the result, so every class of an (image, level, draw) meets the same noise and no replicated `clean`
+    exists in memory.  clean: contiguous fp32 [P, ...]; ids, level: [P] as eval_diffuse.  Returns (noisy [P * C, ...],
+    sigma [P * C]); row p * C + c holds the bits eval_diffuse gives for pair p."""
+    C = _chk_classes(num_classes)
+    P, L = _eval_diffuse_args(clean, ids, level, sigmas, rec, check_levels)
+    if P * C >= 1 << 31:
+        raise ValueError(f"eval_diffuse_classes: P * num_classes must be below 2**31, got {P} * {C}")
+    noisy = torch.empty((P * C,) + tuple(clean.shape[1:]), dtype=f32, device=clean.device)
+    sigma = torch.empty(P * C, dtype=f32, device=clean.device)
+    _lib.call("edm_eval_diffuse_classes", _p(clean), _p(ids), _p(level), _p(sigmas), L, _p(rec), P, C,
+              clean.numel() // P, _p(noisy), _p(sigma), _p(health(clean.device)), _stream())
+    return noisy, sigma
+
+
+def eval_sqerr_classes(D, clean, num_classes, out=None):
+    """eval_sqerr for the class sweep: se[p * C + c] = sum_j ((double)D[p * C + c]_j - (double)clean[p]_j)^2 with the bits
+    eval_sqerr gives for that row against clean[p]; `clean` [P, ...] is read in place, never replicated.  D: contiguous
+    fp32 [P * C, ...], P * C <= 65535; out: a contiguous fp64 [P * C] tensor that is written, or None to allocate."""
+    _chk_eval(clean, f32, "clean")
+    if clean.dim() < 2 or clean.numel() == 0:
+        raise ValueError(f"clean: expected a non-empty [P, ...] tensor, got {tuple(clean.shape)}")
+    C = _chk_classes(num_classes)
+    P = clean.shape[0]
+    rows = P * C
+    if rows > 65535:
+        raise ValueError(f"eval_sqerr_classes takes at most 65535 rows per call, got {P} * {C}")
+    _chk_eval(D, f32, "D", (rows,) + tuple(clean.shape[1:]), clean.device)
+    if out is None:
+        out = torch.empty(rows, dtype=torch.float64, device=clean.device)
+    else:
+        _chk_eval(out, torch.float64, "out", (rows,), clean.device)
+    part = torch.empty(rows * NLL_MAX_CHUNKS, dtype=torch.float64, device=clean.device)
+    _lib.call("edm_eval_sqerr_classes", _p(D), _p(clean), P, C, clean.numel() // P, _p(part), _p(out),
+              _p(health(clean.device)), _stream())
     return out
 
 
