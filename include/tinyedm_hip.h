@@ -203,6 +203,19 @@ int edm_attention_fwd(const void* qkv, void* y, int B, int N, int C, int heads, 
 int edm_attention_bwd(const void* qkv, const void* y, const void* gy, void* gqkv, int B, int N, int C, int heads,
                       edm_stream_t stream);
 
+/* The same attention for any number of tokens N >= 1 (csrc/attention_long.hip; networks.py:194-202 at whatever resolution
+ * the level has): key tiles of 64 and a fixed-offset softmax p = exp(s - sqrt(d)) -- pixel-normalised q, k bound every
+ * logit by sqrt(d), so there is no running maximum.  Head dims 64, 32, 128, 144, 192.
+ * edm_attention_long_supported: 1 / 0 (head_dim built, N >= 1). */
+int edm_attention_long_supported(int N, int C, int heads);
+/* networks.py:194-202.  stat [B, heads, N] fp32 = the rows' log-sum-exp sqrt(d) + log sum p, kept for the backward; may be
+ * NULL in evaluation. */
+int edm_attention_long_fwd(const void* qkv, void* y, float* stat, int B, int N, int C, int heads, edm_stream_t stream);
+/* autograd of networks.py:194-202: y, stat = the forward's outputs; work = B*heads*N floats (delta = <dO, y>, written by the
+ * query-major kernel, read by the key-major one).  No atomics: gqkv is bit-reproducible. */
+int edm_attention_long_bwd(const void* qkv, const void* y, const void* gy, const float* stat, void* gqkv, float* work,
+                           int B, int N, int C, int heads, edm_stream_t stream);
+
 /* CosineAttention with the qkv projection inside the attention kernel (csrc/attention_fused.hip, round 5; replaces
  * networks.py:193-202 = qkv_conv -> view -> pixel_norm -> scaled_dot_product_attention as ONE launch; the qkv tensor never
  * exists in HBM).  x [B*N, C] bf16 tokens, Wqkv [3C, C] bf16 = the qkv conv's forward pack (rows in [head][q|k|v][d] order),

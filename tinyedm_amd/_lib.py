@@ -98,6 +98,10 @@ SIGNATURES = {
     # attention.hip
     "edm_attention_fwd": [P, P, I, I, I, I, P],
     "edm_attention_bwd": [P, P, P, P, I, I, I, I, P],
+    # attention_long.hip
+    "edm_attention_long_supported": [I, I, I],
+    "edm_attention_long_fwd": [P, P, P, I, I, I, I, P],
+    "edm_attention_long_bwd": [P, P, P, P, P, P, I, I, I, I, P],
     # attention_fused.hip
     "edm_attention_qkv_supported": [I, I, I],
     "edm_attention_qkv_fwd": [P, P, P, P, I, I, I, I, I, P],
@@ -193,6 +197,7 @@ _RET = {"edm_last_error": ctypes.c_char_p, "edm_lowrank_wgrad_workspace": ctypes
         "edm_conv_wgrad_1x1_group_table_bytes": ctypes.c_long, "edm_wgrad_finish_multi_table_bytes": ctypes.c_long}
 _NO_STATUS = {"edm_lowrank_wgrad_workspace", "edm_lowrank_supported", "edm_lowrank_tail_supported", "edm_lowrank_tail_dwout_supported", "edm_lowrank_gcat_supported", "edm_skip_gate_bwd_multi_table_bytes", "edm_skip_gate_fwd_multi_table_bytes", "edm_v6_persistent_launches", "edm_conv3x3_fold_supported", "edm_conv_plan", "edm_skip_gate_wgrad_multi_table_bytes", "edm_version", "edm_graph_replay_safe", "edm_last_error", "edm_conv_wgrad_nsplit", "edm_conv_wgrad_1x1_nsplit", "edm_conv_wgrad_1x1_nsplit_grouped", "edm_wgrad3_workspace", "edm_wgrad3_table_bytes", "edm_wgrad3_max_layers",
               "edm_conv_wgrad_1x1_group_table_bytes", "edm_wgrad_finish_multi_table_bytes", "edm_attention_qkv_supported",
+              "edm_attention_long_supported",
               "edm_u8_knn_splits"}
 
 _lib = None

@@ -2,7 +2,7 @@
 //   q,k,v rows pixel-normalised over head_dim (:195), softmax(q k^T / sqrt(d)) v (:201).
 // Low-resolution only (N = H*W <= 256 tokens, head_dim 64), so one workgroup owns one
 // (sample, head): Q,K,V live in LDS for the whole kernel and the N x N score matrix never
-// leaves registers.
+// leaves registers.  Above 256 tokens: attention_long.hip (tiled softmax, any number of tokens).
 //
 // qkv   [B*N, 3C] bf16, channel order per token = [head][q|k|v][d]   (the qkv conv's output rows
 //        are permuted into this order by edm_weight_prep)

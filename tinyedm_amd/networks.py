@@ -951,19 +951,26 @@ class _AttnFn(torch.autograd.Function):
     block of the CIFAR-10 nets) the qkv projection runs INSIDE the attention kernel -- forward: fused kernel + out conv (with
     the mp_add epilogue), 2 launches instead of 3; backward: fused kernel (dO = b * gout . W_out, recomputed q / k / v) + the
     qkv conv's dgrad, 2 instead of 3 -- and the qkv tensor never exists in HBM; the 1x1 weight gradients join the grouped
-    launches as before."""
+    launches as before.  Above 256 tokens (an "A" block on a 32x32 or 64x64 level) the tiled-softmax kernels of
+    csrc/attention_long.hip take the place of attention.hip's: qkv conv -> attention_long_fwd, which also returns the rows'
+    log-sum-exp for attention_long_bwd."""
 
     @staticmethod
     def forward(ctx, x, w_qkv, w_out, mod: CosineAttention, dest=None, grad_mode: bool = True):
         wf_qkv, wd_qkv, _ = mod.qkv_conv.packs()
         wf_out, wd_out, _ = mod.out_conv.packs()
         fused = ops.attention_qkv_supported(x, mod.num_heads)
+        long = not fused and x.shape[1] * x.shape[2] > 256
+        want_stat = grad_mode and any(ctx.needs_input_grad[:3])
         stat = qkv = None
         if fused:
-            y, stat = ops.attention_qkv_fwd(x, wf_qkv, mod.num_heads, want_stat=grad_mode and any(ctx.needs_input_grad[:3]))
+            y, stat = ops.attention_qkv_fwd(x, wf_qkv, mod.num_heads, want_stat=want_stat)
         else:
             qkv = ops.conv_igemm(x, wf_qkv, 1)
-            y = ops.attention_fwd(qkv, mod.num_heads)
+            if long:
+                y, stat = ops.attention_long_fwd(qkv, mod.num_heads, want_stat=want_stat)
+            else:
+                y = ops.attention_fwd(qkv, mod.num_heads)
         a, b = _mp_coeffs(0.5)
         C = wf_out.shape[1]
         if _dest_ok(dest, y):     # the block's output goes straight into the next block's cat / mp_silu(cat)
@@ -972,11 +979,11 @@ class _AttnFn(torch.autograd.Function):
             out._edm_cat = dest
         else:
             out = ops.conv_igemm(y, wf_out, 1, residual=x, alpha=b, beta=a)
-        ctx.mod, ctx.fused = mod, fused
+        ctx.mod, ctx.fused, ctx.long = mod, fused, long
         if fused:
             ctx.save_for_backward(x, stat, y, wd_qkv, wd_out, wf_qkv)
         else:
-            ctx.save_for_backward(x, qkv, y, wd_qkv, wd_out)
+            ctx.save_for_backward(x, qkv, y, wd_qkv, wd_out, stat)
         return out
 
     @staticmethod
@@ -986,14 +993,19 @@ class _AttnFn(torch.autograd.Function):
         a, b = _mp_coeffs(0.5)
         if ctx.fused:
             x, stat, y, wd_qkv, wd_out, wf_qkv = ctx.saved_tensors
-            if stat is None:
-                raise RuntimeError("tinyedm_amd: attention backward without the forward's softmax statistics (the forward ran "
-                                   "under torch.no_grad())")
+        else:
+            x, qkv, y, wd_qkv, wd_out, stat = ctx.saved_tensors
+        if (ctx.fused or ctx.long) and stat is None:
+            raise RuntimeError("tinyedm_amd: attention backward without the forward's softmax statistics (the forward ran "
+                               "under torch.no_grad())")
+        if ctx.fused:
             gqkv = ops.attention_qkv_bwd(x, y, gout, stat, wf_qkv, wd_out, mod.num_heads, alpha=b)
         else:
-            x, qkv, y, wd_qkv, wd_out = ctx.saved_tensors
             gy = ops.conv_igemm(gout, wd_out, 1, alpha=b)
-            gqkv = ops.attention_bwd(qkv, y, gy, mod.num_heads)
+            if ctx.long:
+                gqkv = ops.attention_long_bwd(qkv, y, gy, stat, mod.num_heads)
+            else:
+                gqkv = ops.attention_bwd(qkv, y, gy, mod.num_heads)
         gw_out = _wgrad(mod.out_conv, y, gout, 1, b)
         gx = ops.conv_igemm(gqkv, wd_qkv, 1, residual=gout, alpha=1.0, beta=a)
         gw_qkv = _wgrad(mod.qkv_conv, x, gqkv, 1)

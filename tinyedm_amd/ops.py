@@ -1525,6 +1525,39 @@ def attention_bwd(qkv, y, gy, heads):
     return gqkv
 
 
+def attention_long_supported(N, C, heads):
+    """the tiled-softmax kernels (attention_long.hip) cover this shape: any N >= 1, head_dim 64 / 32 / 128 / 144 / 192"""
+    return bool(_lib.call("edm_attention_long_supported", N, C, heads))
+
+
+def attention_long_fwd(qkv, heads, want_stat=True):
+    """attention_fwd for any number of tokens: qkv (B,H,W,3C) bf16, channel order [head][q|k|v][d] ->
+    y (B,H,W,C) bf16, stat (B, heads, H*W) fp32 = the rows' log-sum-exp, or None (networks.py:194-202)"""
+    B, H, W, C3 = _nhwc(qkv, "qkv")
+    C = C3 // 3
+    N = H * W
+    y = torch.empty(B, H, W, C, device=qkv.device, dtype=bf16)
+    stat = torch.empty(B, heads, N, device=qkv.device, dtype=f32) if want_stat else None
+    with _prof("attention_long_fwd", 4.0 * B * N * N * C, 2.0 * B * N * 4 * C):
+        _lib.call("edm_attention_long_fwd", _p(qkv), _p(y), _p(stat), B, N, C, heads, _stream())
+    return y, stat
+
+
+def attention_long_bwd(qkv, y, gy, stat, heads):
+    """-> gqkv (B,H,W,3C) bf16; y, stat = attention_long_fwd's outputs"""
+    B, H, W, C3 = _nhwc(qkv, "qkv")
+    C = C3 // 3
+    N = H * W
+    _chk(y, bf16, "y", (B, H, W, C))
+    _chk(gy, bf16, "gy", (B, H, W, C))
+    _chk(stat, f32, "stat", (B, heads, N))
+    gqkv = torch.empty_like(qkv)
+    work = torch.empty(B, heads, N, device=qkv.device, dtype=f32)     # delta = <dO, y>: query-major kernel -> key-major kernel
+    with _prof("attention_long_bwd", 14.0 * B * N * N * C, 2.0 * B * N * 8 * C):
+        _lib.call("edm_attention_long_bwd", _p(qkv), _p(y), _p(gy), _p(stat), _p(gqkv), _p(work), B, N, C, heads, _stream())
+    return gqkv
+
+
 ATTN_FUSED = os.environ.get("EDM_ATTN_FUSED", "1") != "0"      # qkv projection inside the attention kernels (attention_fused.hip)
 ATTN_HP = int(os.environ.get("EDM_ATTN_HP", "0"))               # heads per workgroup of the FORWARD (0 = the kernel's default;
                                                                 # the backward always runs one head per workgroup)
