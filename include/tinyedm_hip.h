@@ -373,6 +373,20 @@ int edm_skip_half_bwd(const void* gcs, const float* gate, const float* gmean, vo
 /* out[b,h,w,:] = [c_in(b)*noisy[b,:,h,w], 1, 0...] (bf16, CP channels); sigma_stride 0 = one scalar sigma */
 int edm_precond_in(const float* noisy, const float* sigma, int sigma_stride, float sigma_data, void* out, int B,
                    int Cimg, int HW, int CP, edm_stream_t stream);
+/* The input gradient of the denoiser (reference networks.py:584-587, 602-603; conv_in_dgrad.hip): conv_in's 3x3 dgrad into
+ * the Cimg image channels with the preconditioning folded in,
+ *   gx[b,c,h,w] = c_in(b) * sum_{ky,kx,co} gy[b, h+1-ky, w+1-kx, co] * w^[co,c,ky,kx]  (zero outside the map)
+ *               + c_skip(b) * gD[b,c,h,w]                                               (gD nullable: the term is absent)
+ * gy: bf16 NHWC [B,H,W,C0], the gradient of conv_in's output; gx, gD: fp32 NCHW [B,Cimg,H,W], 1 <= Cimg <= 8; the constant
+ * ones channel gets no gradient.  wpack: fp32 [C0][NT], NT = edm_conv_in_dgrad_pack_cols(Cimg) = 9*Cimg rounded up to 4,
+ * wpack[co][(ky*3+kx)*Cimg + c] = w^[co,c,ky,kx] (the bf16-rounded forward operand), padding columns zero, 16-byte aligned.
+ * fp32 accumulation in a fixed order (co ascending per tap, then the taps ky, kx ascending); the c_skip product is rounded on
+ * its own, so gy = 0 returns c_skip * gD bit for bit; a sample's result does not depend on B.  gy may be 2-byte aligned
+ * (16-byte pieces when it is 16-byte aligned and C0 % 8 == 0, same bits otherwise).  sigma_stride 0 = one scalar sigma.
+ * EDM_ERR_UNSUPPORTED when three rows of W pixels do not fit the LDS table. */
+int edm_conv_in_dgrad_pack_cols(int Cimg);
+int edm_conv_in_dgrad(const void* gy, const float* wpack, const float* gD, const float* sigma, int sigma_stride,
+                      float sigma_data, float* gx, int B, int Cimg, int H, int W, int C0, edm_stream_t stream);
 /* D = conv_out(x)*gain_out*c_out + noisy*c_skip (fp32 NCHW); Fraw = conv_out(x) saved for the backward */
 int edm_conv_out_fwd(const void* x, const float* w_hat, const float* gain_out, const float* noisy, const float* sigma,
                      int sigma_stride, float sigma_data, float* D, float* Fraw, int B, int HW, int C, int Co,
@@ -559,6 +573,23 @@ int edm_inpaint_blend(const float* x, const float* image, const unsigned char* m
 int edm_degrade(const float* x, float* y, int B, int C, int H, int W, int scale, int gray, edm_stream_t stream);
 int edm_project_denoised(const float* Dm, const float* Dg, const float* w, const float* y, float* out, int B, int C,
                          int H, int W, int scale, int gray, unsigned* health, edm_stream_t stream);
+/* Diffusion posterior sampling (Chung et al. 2023; restore.hip): the measurement side of a step x' + (zeta / ||r||) g with
+ * r = y - A D and g = J^T A^T r.  All tensors contiguous fp32; no output aliases an operand.
+ * edm_degrade_adjoint: out [B, C, H, W] = A^T r for the averaging A of edm_degrade (r of the measurement shape): every value
+ *   replicated to its block (and, gray, to the C channels) times 1.0f / n, n = scale*scale*(gray ? C : 1).
+ * edm_blur2d: y = K x on each of `planes` H x W planes, K the separable blur with the 2*radius+1 taps `taps` (a HOST
+ *   pointer, copied into the launch; radius 1..4) and ZERO padding -- with symmetric taps K is its own adjoint.  Both passes
+ *   are fma chains over all taps in ascending order (a tap off the map adds 0).
+ * edm_dps_residual: r = y - AD over [B, n] and nrm[b] = sqrt(sum_i r[b,i]^2): thread t of the sample's workgroup adds the
+ *   squares of elements t, t + 256, ... in that order, then a fixed binary tree over the 256 partial sums -- no atomics:
+ *   the same bits on every run, whatever B.
+ * edm_dps_update: out[b,:] = x[b,:] + (scale / nrm[b]) * g[b,:] (one division per sample, one fma per element); out = x bit
+ *   for bit where nrm[b] == 0 or scale == 0.  Same health bit as the Heun updates. */
+int edm_degrade_adjoint(const float* r, float* out, int B, int C, int H, int W, int scale, int gray, edm_stream_t stream);
+int edm_blur2d(const float* x, float* y, const float* taps, int radius, long planes, int H, int W, edm_stream_t stream);
+int edm_dps_residual(const float* y, const float* AD, float* r, float* nrm, int B, long n, edm_stream_t stream);
+int edm_dps_update(const float* x, const float* g, const float* nrm, float scale, float* out, int B, long n,
+                   unsigned* health, edm_stream_t stream);
 /* Likelihood evaluation along the probability-flow ODE dx/dt = (x - D(x; t)) / t: the Heun updates plus the integral of
  * the drift's divergence (CHW - tr dD/dx) / t, the trace estimated without a backward pass (Hutchinson with Rademacher
  * probes, central difference through the network):

@@ -8,10 +8,11 @@ from .edm import EDM, Diffuser
 from .ema import EMA, EMAOptimizer, FusedAdam, sigma_rel_to_gamma
 from .metric import WeightedMeanSquaredError
 from .networks import Conv2d, Denoiser, DenoiserWrapper, Embedding, Linear, manual_seed
-from .solvers import DeterministicSolver, LinearDegradation, MultistepSolver, StochasticSolver
+from .solvers import DeterministicSolver, GaussianBlur, LinearDegradation, MultistepSolver, StochasticSolver
 from .trainer import LightningModule, Trainer
+from .vjp import input_vjp
 from . import config, networks, ops
 
-__all__ = ["EDM", "Diffuser", "DeterministicSolver", "StochasticSolver", "MultistepSolver", "LinearDegradation", "WeightedMeanSquaredError", "Denoiser", "Linear", "Conv2d",
+__all__ = ["EDM", "Diffuser", "DeterministicSolver", "StochasticSolver", "MultistepSolver", "LinearDegradation", "GaussianBlur", "input_vjp", "WeightedMeanSquaredError", "Denoiser", "Linear", "Conv2d",
            "Embedding", "DenoiserWrapper", "EMA", "EMAOptimizer", "FusedAdam", "Trainer", "LightningModule",
            "sigma_rel_to_gamma", "manual_seed", "config", "networks", "ops"]

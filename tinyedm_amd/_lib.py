@@ -144,6 +144,13 @@ SIGNATURES = {
     # restore.hip
     "edm_degrade": [P, P, I, I, I, I, I, I, P],
     "edm_project_denoised": [P, P, P, P, P, I, I, I, I, I, I, P, P],
+    "edm_degrade_adjoint": [P, P, I, I, I, I, I, I, P],
+    "edm_blur2d": [P, P, P, I, L, I, I, P],
+    "edm_dps_residual": [P, P, P, P, I, L, P],
+    "edm_dps_update": [P, P, P, F, P, I, L, P, P],
+    # conv_in_dgrad.hip
+    "edm_conv_in_dgrad_pack_cols": [I],
+    "edm_conv_in_dgrad": [P, P, P, P, I, F, P, I, I, I, I, I, P],
     # weights.hip
     "edm_weight_prep": [P, I, I, I, I, P, P, P, P, I, P],
     "edm_weight_prep_multi": [P, P, I, I, I, P],
@@ -197,7 +204,7 @@ _RET = {"edm_last_error": ctypes.c_char_p, "edm_lowrank_wgrad_workspace": ctypes
         "edm_conv_wgrad_1x1_group_table_bytes": ctypes.c_long, "edm_wgrad_finish_multi_table_bytes": ctypes.c_long}
 _NO_STATUS = {"edm_lowrank_wgrad_workspace", "edm_lowrank_supported", "edm_lowrank_tail_supported", "edm_lowrank_tail_dwout_supported", "edm_lowrank_gcat_supported", "edm_skip_gate_bwd_multi_table_bytes", "edm_skip_gate_fwd_multi_table_bytes", "edm_v6_persistent_launches", "edm_conv3x3_fold_supported", "edm_conv_plan", "edm_skip_gate_wgrad_multi_table_bytes", "edm_version", "edm_graph_replay_safe", "edm_last_error", "edm_conv_wgrad_nsplit", "edm_conv_wgrad_1x1_nsplit", "edm_conv_wgrad_1x1_nsplit_grouped", "edm_wgrad3_workspace", "edm_wgrad3_table_bytes", "edm_wgrad3_max_layers",
               "edm_conv_wgrad_1x1_group_table_bytes", "edm_wgrad_finish_multi_table_bytes", "edm_attention_qkv_supported",
-              "edm_attention_long_supported",
+              "edm_attention_long_supported", "edm_conv_in_dgrad_pack_cols",
               "edm_u8_knn_splits"}
 
 _lib = None

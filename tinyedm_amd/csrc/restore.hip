@@ -171,3 +171,140 @@ extern "C" int edm_project_denoised(const float* Dm, const float* Dg, const floa
   EDM_CHECK_LAUNCH("project_denoised");
   return EDM_OK;
 }
+
+// ------------------------------------------------------------------ diffusion posterior sampling (Chung et al. 2023)
+// The measurement side of a DPS step: the adjoint of the averaging operator, a small zero-padded Gaussian blur (its own
+// adjoint), the residual r = y - A D with its per-sample 2-norm, and the guided update x' + (zeta / ||r||) g.
+namespace {
+
+struct BlurTaps {
+  float k[9];     // 2 * radius + 1 normalised taps
+};
+
+// out[b,c,h,w] = r[b, gray ? 0 : c, h / S, w / S] * inv_n: A^T of the block (and channel) mean
+__global__ void __launch_bounds__(256)
+k_degrade_adjoint(const float* __restrict__ r, float* __restrict__ out, int C, int H, int W, int S, int gray,
+                  float inv_n, long total) {
+  const int Hs = H / S, Ws = W / S, Cp = gray ? 1 : C;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int w = (int)(i % W);
+    long q = i / W;
+    const int h = (int)(q % H);
+    q /= H;
+    const int c = (int)(q % C);
+    const long b = q / C;
+    out[i] = r[((b * Cp + (gray ? 0 : c)) * Hs + h / S) * Ws + w / S] * inv_n;
+  }
+}
+
+// y[p,h,w] = sum_dy k[dy] * (sum_dx k[dx] * x[p, h+dy-R, w+dx-R]), zero outside the map; both sums are fma chains in
+// ascending order over ALL 2R+1 taps (a tap off the map adds 0), so a plane's bits depend on nothing but the plane
+__global__ void __launch_bounds__(256)
+k_blur2d(const float* __restrict__ x, float* __restrict__ y, BlurTaps taps, int R, int H, int W, long total) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int w = (int)(i % W);
+    const long q = i / W;
+    const int h = (int)(q % H);
+    const float* xp = x + (q / H) * (long)H * W;
+    float acc = 0.f;
+    for (int dy = 0; dy <= 2 * R; ++dy) {
+      const int hh = h + dy - R;
+      float row = 0.f;
+      if (hh >= 0 && hh < H) {
+        for (int dx = 0; dx <= 2 * R; ++dx) {
+          const int ww = w + dx - R;
+          const float v = (ww >= 0 && ww < W) ? xp[(long)hh * W + ww] : 0.f;
+          row = fmaf(taps.k[dx], v, row);
+        }
+      }
+      acc = fmaf(taps.k[dy], row, acc);
+    }
+    y[i] = acc;
+  }
+}
+
+// r = y - AD and nrm[b] = sqrt(sum r^2) of sample b: one workgroup per sample; thread t adds the squares of elements
+// t, t + 256, ... in that order, then the 256 partial sums meet in a fixed binary tree -- no atomics, nothing that depends
+// on B or on the grid: the same bits on every run
+__global__ void __launch_bounds__(256)
+k_dps_residual(const float* __restrict__ y, const float* __restrict__ AD, float* __restrict__ r, float* __restrict__ nrm,
+               long n) {
+  __shared__ float part[256];
+  const long base = (long)blockIdx.x * n;
+  float acc = 0.f;
+  for (long i = threadIdx.x; i < n; i += 256) {
+    const float d = y[base + i] - AD[base + i];
+    r[base + i] = d;
+    acc = fmaf(d, d, acc);
+  }
+  part[threadIdx.x] = acc;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) nrm[blockIdx.x] = sqrtf(part[0]);
+}
+
+// out = x + (scale / nrm[b]) * g, out = x where nrm[b] == 0 (bit for bit x); the factor is one division per sample
+__global__ void __launch_bounds__(256)
+k_dps_update(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ nrm, float scale,
+             float* __restrict__ out, long n, long total, unsigned* __restrict__ health) {
+  bool bad = false;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const float nb = nrm[i / n];
+    float v = x[i];
+    if (nb != 0.f && scale != 0.f) v = fmaf(scale / nb, g[i], v);
+    bad |= !(fabsf(v) <= 3.0e38f);
+    out[i] = v;
+  }
+  if (health && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(health, 2u);
+}
+
+}  // namespace
+
+// out = A^T r for the averaging A of edm_degrade: r [B, gray ? 1 : C, H/scale, W/scale] -> out [B, C, H, W], every value
+// replicated to its block (and channels) and multiplied by 1 / n, n = scale*scale*(gray ? C : 1).  out does not alias r.
+extern "C" int edm_degrade_adjoint(const float* r, float* out, int B, int C, int H, int W, int scale, int gray,
+                                   hipStream_t st) {
+  EDM_REQUIRE(r && out && r != out && shape_ok(B, C, H, W, scale, gray),
+              "degrade_adjoint: bad args (scale in {1, 2, 4, 8}, not the identity, H and W multiples of scale, gray needs "
+              "C <= 8)");
+  const long total = (long)B * C * H * W;
+  const float inv_n = 1.0f / (float)(scale * scale * (gray ? C : 1));
+  hipLaunchKernelGGL(k_degrade_adjoint, dim3(grid_for(total, 256)), dim3(256), 0, st, r, out, C, H, W, scale, gray, inv_n,
+                     total);
+  EDM_CHECK_LAUNCH("degrade_adjoint");
+  return EDM_OK;
+}
+// y = K x: the separable blur with the 2*radius+1 taps `taps` (HOST pointer, copied into the launch), zero padding,
+// on each of the `planes` H x W planes of x (contiguous fp32; y does not alias x).  radius 1..4.
+extern "C" int edm_blur2d(const float* x, float* y, const float* taps, int radius, long planes, int H, int W,
+                          hipStream_t st) {
+  EDM_REQUIRE(x && y && x != y && taps && radius >= 1 && radius <= 4 && planes > 0 && H > 0 && W > 0,
+              "blur2d: bad args (radius 1..4, y must not alias x)");
+  BlurTaps t{};
+  for (int k = 0; k <= 2 * radius; ++k) t.k[k] = taps[k];
+  const long total = planes * H * W;
+  hipLaunchKernelGGL(k_blur2d, dim3(grid_for(total, 256)), dim3(256), 0, st, x, y, t, radius, H, W, total);
+  EDM_CHECK_LAUNCH("blur2d");
+  return EDM_OK;
+}
+// r = y - AD (n elements per sample, all contiguous fp32 [B, n]; r may alias neither) and nrm[b] = ||r_b||_2, an
+// order-fixed reduction: bit-identical from run to run and independent of B.
+extern "C" int edm_dps_residual(const float* y, const float* AD, float* r, float* nrm, int B, long n, hipStream_t st) {
+  EDM_REQUIRE(y && AD && r && nrm && B > 0 && n > 0 && r != y && r != AD, "dps_residual: bad args");
+  hipLaunchKernelGGL(k_dps_residual, dim3(B), dim3(256), 0, st, y, AD, r, nrm, n);
+  EDM_CHECK_LAUNCH("dps_residual");
+  return EDM_OK;
+}
+// out = x + (scale / nrm[b]) * g for sample b, out = x bit for bit where nrm[b] == 0 or scale == 0; [B, n] fp32, out aliases
+// no operand.  Same health bit as the Heun updates.
+extern "C" int edm_dps_update(const float* x, const float* g, const float* nrm, float scale, float* out, int B, long n,
+                              unsigned* health, hipStream_t st) {
+  EDM_REQUIRE(x && g && nrm && out && B > 0 && n > 0 && out != g && out != x, "dps_update: bad args (out aliases no operand)");
+  const long total = (long)B * n;
+  hipLaunchKernelGGL(k_dps_update, dim3(grid_for(total, 256)), dim3(256), 0, st, x, g, nrm, scale, out, n, total, health);
+  EDM_CHECK_LAUNCH("dps_update");
+  return EDM_OK;
+}

@@ -78,6 +78,12 @@ and `--restore_report OUT.json` receives, per rank and computed in fp32 before t
 ground truth in pixel units, ...}.  Exclusive with `--mask_box`, `--invert_to` and `--likelihood_to`; combines with guidance, churn,
 `--solver dpmpp`, `--start_step` and `--network_dtype`.
 
+With `--dps_scale Z` the same flags -- or `--blur_std S [--blur_radius R]`, a zero-padded Gaussian blur -- name the operator
+of diffusion posterior sampling (DPS, Chung et al. 2023) instead: `--measurement_noise N` adds N * N(0, 1) noise from `--seed`
+to the measurement, every Heun step is followed by x += (Z / ||y - A D||) J^T A^T (y - A D) (one backward pass through the
+network, so `--network_dtype bf16`, `--solver heun`, eager), `--save_degraded` receives the noisy measurement on the image
+grid and `--restore_report` the RMS of A x - y (to be read against N) and the PSNRs.
+
     python -m tinyedm.generate --ckpt_path last.ckpt --load_ema --init_dir photos --restore_scale 4 \\
         --save_degraded lowres --restore_report sr.json --output_dir restored --num_samples 64 --image_size 32 \\
         --num_classes 10 --batch_size 64
@@ -178,19 +184,49 @@ def _drawn_labels(batch_size, num_workers, image_size, num_samples, num_classes,
 RESTORE_SCALES = (1, 2, 4, 8)
 
 
+def _check_posterior(dps_scale, blur_std, blur_radius, measurement_noise, restore_scale, restore_gray, network_dtype,
+                     solver, guided) -> bool:
+    """the posterior-sampling (DPS) choices that need nothing loaded; returns whether the run samples with DPS"""
+    import math
+    if dps_scale is None:
+        for flag, on in (("--blur_std", blur_std is not None), ("--measurement_noise", float(measurement_noise) != 0.0)):
+            if on:
+                raise ValueError(f"generate: {flag} needs --dps_scale (posterior sampling; DDNM takes noise-free box / grey "
+                                 "measurements only)")
+        return False
+    if not (math.isfinite(float(dps_scale)) and float(dps_scale) >= 0.0):
+        raise ValueError(f"generate: --dps_scale must be finite and >= 0, got {dps_scale}")
+    if not (math.isfinite(float(measurement_noise)) and float(measurement_noise) >= 0.0):
+        raise ValueError(f"generate: --measurement_noise must be finite and >= 0, got {measurement_noise}")
+    box = restore_scale != 1 or bool(restore_gray)
+    if box == (blur_std is not None):
+        raise ValueError("generate: --dps_scale needs ONE measurement operator: --restore_scale / --restore_gray or --blur_std")
+    if blur_std is not None:
+        from . import ops
+        ops.gaussian_taps(blur_std, blur_radius)
+    if network_dtype != "bf16":
+        raise ValueError("generate: --dps_scale needs --network_dtype bf16 (the path with a backward pass)")
+    if solver != "heun":
+        raise ValueError("generate: --dps_scale needs --solver heun")
+    if guided:
+        raise ValueError("generate: --dps_scale with a guide is not implemented")
+    return True
+
+
 def _check_restoration(init_dir, restore_scale, restore_gray, save_degraded, restore_report, mask_box, invert_to,
-                       likelihood_to, image_size) -> bool:
-    """the restoration choices that need nothing loaded; returns whether the run restores"""
+                       likelihood_to, image_size, blur=False) -> bool:
+    """the restoration choices that need nothing loaded; returns whether the run restores (blur: a --blur_std measurement
+    of posterior sampling takes the place of --restore_scale / --restore_gray)"""
     if isinstance(restore_scale, bool) or not isinstance(restore_scale, int) or restore_scale not in RESTORE_SCALES:
         raise ValueError(f"generate: --restore_scale must be one of {RESTORE_SCALES}, got {restore_scale!r}")
-    active = restore_scale != 1 or bool(restore_gray)
+    active = restore_scale != 1 or bool(restore_gray) or bool(blur)
     if not active:
         for flag, on in (("--save_degraded", save_degraded is not None), ("--restore_report", restore_report is not None)):
             if on:
                 raise ValueError(f"generate: {flag} needs --restore_scale > 1 or --restore_gray")
         return False
     if init_dir is None:
-        flag = "--restore_scale" if restore_scale != 1 else "--restore_gray"
+        flag = "--restore_scale" if restore_scale != 1 else ("--restore_gray" if restore_gray else "--blur_std")
         raise ValueError(f"generate: {flag} needs --init_dir (the ground-truth images that are measured)")
     for flag, on in (("--mask_box", mask_box is not None), ("--invert_to", invert_to is not None),
                      ("--likelihood_to", likelihood_to is not None)):
@@ -241,7 +277,8 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
              guidance_interval=None, S_churn=0.0, S_min=0.0, S_max=float("inf"), S_noise=1.0, solver="heun",
              solver_order=2, init_dir=None, start_step=0, mask_box=None, invert_to=None, likelihood_to=None,
              num_probes=1, dequantize=False, restore_scale=1, restore_gray=False, save_degraded=None,
-             restore_report=None, labels_to=None) -> None:
+             restore_report=None, labels_to=None, dps_scale=None, blur_std=None, blur_radius=2,
+             measurement_noise=0.0) -> None:
     from .callbacks import PreditionWriter
     from .datamodules import RandomNoiseDataModule
     from .edm import EDM
@@ -252,9 +289,13 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
     _check_conditioning(init_dir, start_step, mask_box, invert_to, solver, S_churn, image_size,
                         likelihood_to=likelihood_to, network_dtype=network_dtype, num_probes=num_probes,
                         dequantize=dequantize)
+    posterior = _check_posterior(dps_scale, blur_std, blur_radius, measurement_noise, restore_scale, restore_gray,
+                                 network_dtype, solver, guide is not None or guide_ckpt_path is not None)
     restoring = _check_restoration(init_dir, restore_scale, restore_gray, save_degraded, restore_report, mask_box,
-                                   invert_to, likelihood_to, image_size)
+                                   invert_to, likelihood_to, image_size, blur=posterior and blur_std is not None)
     _check_labels_to(labels_to, init_dir)
+    if posterior:
+        graph = False       # a DPS step runs a backward pass: the eager loop
 
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
@@ -357,6 +398,47 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
                        "first_index": first}, f)
         print(f"[rank {rank}] wrote the likelihoods of images {first}..{first + n_local - 1} to {likelihood_to}",
               flush=True)
+        return
+    if restoring and posterior:
+        import json
+        from .solvers import GaussianBlur, LinearDegradation
+        op = GaussianBlur(float(blur_std), int(blur_radius)) if blur_std is not None else \
+            LinearDegradation(restore_scale, bool(restore_gray))
+        writers = [PreditionWriter(output_dir=d, write_interval="batch", mean=mean, std=std, first_index=first)
+                   for d in (output_dir, save_degraded) if d is not None]
+        model.eval()
+        gen = torch.Generator().manual_seed(seed + 1000003 * rank)
+        sq, count, psnr_out, psnr_deg = 0.0, 0, [], []
+        for bi, (x0, y, img) in enumerate(datamodule.predict_dataloader()):
+            y = y if model.conditional else None
+            meas = op.measure(img)              # the ground truth is used for this and for the report only
+            if float(measurement_noise) > 0.0:
+                meas = meas + float(measurement_noise) * torch.randn(meas.shape, generator=gen).to(meas.device)
+            # what --save_degraded shows: the noisy measurement on the image grid (a blur's y is an image already)
+            back = meas if blur_std is not None else op.pinv(meas, C)
+            out = model.solver.solve(model, x0, y, image=back if start_step > 0 else None, operator=op, measurement=meas,
+                                     dps_scale=float(dps_scale)).float()
+            res = op.measure(out) - meas
+            sq, count = sq + float((res.double() ** 2).sum()), count + res.numel()
+            psnr_out.append(_psnr(out, img, mean, std).cpu())
+            psnr_deg.append(_psnr(back, img, mean, std).cpu())
+            for w, pred in zip(writers, (out, back)):
+                w.write_on_batch_end(None, model, pred, None, None, bi, 0)
+        if restore_report is not None:
+            if world > 1:
+                root, ext = os.path.splitext(restore_report)
+                restore_report = f"{root}.rank{rank}{ext}"
+            with open(restore_report, "w") as f:
+                json.dump({"measurement_rms": (sq / count) ** 0.5 if count else None,
+                           "measurement_noise": float(measurement_noise), "dps_scale": float(dps_scale),
+                           "psnr_restored": float(torch.cat(psnr_out).mean()) if psnr_out else None,
+                           "psnr_degraded": float(torch.cat(psnr_deg).mean()) if psnr_deg else None,
+                           "restore_scale": restore_scale, "restore_gray": bool(restore_gray),
+                           "blur_std": None if blur_std is None else float(blur_std),
+                           "blur_radius": None if blur_std is None else int(blur_radius), "num_steps": num_steps,
+                           "start_step": start_step, "seed": seed, "network_dtype": network_dtype,
+                           "first_index": first, "num_images": n_local}, f)
+        print(f"[rank {rank}] wrote the posterior samples {first}..{first + n_local - 1} to {output_dir}", flush=True)
         return
     if restoring:
         import json
@@ -478,6 +560,16 @@ def main(argv=None):
                         help="restoration: write A+ y, the measurement replicated to the image grid, as <index>.png")
     parser.add_argument("--restore_report", type=str, default=None, metavar="OUT.json",
                         help="restoration: write max |A x - y| and the mean PSNR of the restored images and of A+ y")
+    # posterior sampling (DPS)
+    parser.add_argument("--dps_scale", type=float, default=None, metavar="Z",
+                        help="diffusion posterior sampling: after every step x += (Z / ||y - A D||) J^T A^T (y - A D); the "
+                             "operator A is --restore_scale / --restore_gray or --blur_std; needs --network_dtype bf16")
+    parser.add_argument("--blur_std", type=float, default=None, metavar="S",
+                        help="--dps_scale: A is a zero-padded Gaussian blur of standard deviation S pixels")
+    parser.add_argument("--blur_radius", type=int, default=2, metavar="R",
+                        help="--blur_std: 2R+1 taps, R in 1..4 (default 2)")
+    parser.add_argument("--measurement_noise", type=float, default=0.0, metavar="N",
+                        help="--dps_scale: add N * N(0, 1) noise (from --seed) to the measurement (default 0)")
     parser.add_argument("--labels_to", type=str, default=None, metavar="FILE.json",
                         help="write the class indices the samples were drawn for, in index order (the format "
                              "--labels_json of tinyedm.classify reads); class-conditional checkpoints, not with --init_dir")
@@ -485,8 +577,12 @@ def main(argv=None):
     _check_solver(args.solver, args.S_churn)
     try:
         _check_labels_to(args.labels_to, args.init_dir)
+        guided = (args.guide_ckpt_path is not None or args.guide_config_name is not None or args.guide_unconditional)
+        posterior = _check_posterior(args.dps_scale, args.blur_std, args.blur_radius, args.measurement_noise,
+                                     args.restore_scale, args.restore_gray, args.network_dtype, args.solver, guided)
         _check_restoration(args.init_dir, args.restore_scale, args.restore_gray, args.save_degraded,
-                           args.restore_report, args.mask_box, args.invert_to, args.likelihood_to, args.image_size)
+                           args.restore_report, args.mask_box, args.invert_to, args.likelihood_to, args.image_size,
+                           blur=posterior and args.blur_std is not None)
         _check_conditioning(args.init_dir, args.start_step, args.mask_box, args.invert_to, args.solver, args.S_churn,
                             args.image_size, likelihood_to=args.likelihood_to, network_dtype=args.network_dtype,
                             num_probes=args.num_probes, dequantize=args.dequantize)
@@ -527,7 +623,8 @@ def main(argv=None):
              init_dir=args.init_dir, start_step=args.start_step, mask_box=args.mask_box, invert_to=args.invert_to,
              likelihood_to=args.likelihood_to, num_probes=args.num_probes, dequantize=args.dequantize,
              restore_scale=args.restore_scale, restore_gray=args.restore_gray, save_degraded=args.save_degraded,
-             restore_report=args.restore_report, labels_to=args.labels_to)
+             restore_report=args.restore_report, labels_to=args.labels_to, dps_scale=args.dps_scale,
+             blur_std=args.blur_std, blur_radius=args.blur_radius, measurement_noise=args.measurement_noise)
 
 
 if __name__ == "__main__":

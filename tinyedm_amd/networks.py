@@ -56,6 +56,13 @@ _IN_DENOISER = [False]  # a Denoiser forward is running (its plan chose the pack
 FORWARD_EPOCH = 0       # grad-enabled Denoiser forwards so far (FusedAdam.zero_grad: "was a gradient written since step()?")
 
 
+# input_vjp's dgrad-only backward: set around ONE eval-mode forward + backward whose only wanted gradient is the input image's.
+# The places that produce weight-side gradients (weight-gradient launches, the skip-gate weight reductions, gain / modulation
+# finishes, embedding-weight GEMMs) and the bookkeeping of a training backward (FORWARD_EPOCH, `_edm_deferred`, reducer hooks,
+# the end-of-backward queue) consult it; the data-gradient kernels and the conditions that choose them are the same as ever.
+_DGRAD_ONLY = [False]
+
+
 def bump_weight_epoch() -> None:
     """Called by anything that rewrites parameters through raw pointers (the fused optimizer)."""
     global _WEIGHT_EPOCH
@@ -119,6 +126,8 @@ class _WNBase(nn.Module):
 
     def finish_grad(self, slabs: Tensor, scale: float = 1.0) -> Tensor:
         """slabs (S, taps, O, Ipad) fp32 in packed order -> gradient w.r.t. the master weight."""
+        if _DGRAD_ONLY[0]:
+            return None
         w = self.weight
         I = w.shape[1]
         if w.grad is not None and getattr(w, "_edm_direct", False):
@@ -323,6 +332,8 @@ def _wgrad(mod, x, dy, taps, scale=1.0):
     """Weight gradient of a conv layer.  In flat-arena mode the result is only needed by the optimizer, so the
     kernels run on the side stream (EDM_WGRAD_STREAM=0 disables), off the critical dgrad -> elementwise -> dgrad
     chain of the backward pass, and 3x3 layers are collected into groups of W3_GROUP per launch."""
+    if _DGRAD_ONLY[0]:
+        return None
     w = mod.weight
     direct = w.grad is not None and getattr(w, "_edm_direct", False)
     if (taps == 9 and W3_GROUP and w.dim() == 4 and ops.wgrad3_supported(x, dy, w.shape[1])
@@ -367,6 +378,8 @@ def _wgrad_lowrank(mod, x, dF, wout_hat, scale, G=None):
     k_wgrad3 group and is not counted among the 3x3 layers of the pass (_w3_seen / _w3_total: W3_TAIL still cuts the last
     group where it did); its parameter is deferred and its hooks run with the finish launch, like every small gradient.
     G given (TAIL_FWD: _TailOutFn.backward reduced it already, for a 3x3 or a 1x1 conv): only the expansion."""
+    if _DGRAD_ONLY[0]:
+        return None
     w = mod.weight
     box = []
     if G is not None:
@@ -516,6 +529,26 @@ class Conv2d(_WNBase):
         xh = ops.nchw_to_nhwc_bf16(x.float().contiguous())
         y = _ConvFn.apply(xh, self.weight, self)
         return ops.nhwc_bf16_to_nchw(y).to(x.dtype)
+
+    def in_dgrad_pack(self, cimg: int) -> Tensor:
+        """The operand of ops.conv_in_dgrad (conv_in only): fp32 [O][NT], row co = the nine taps x the first `cimg` input
+        channels of the FORWARD pack -- the bf16-rounded normalised weights the forward multiplied by, so the backward is the
+        transpose of exactly that product.  Taken from the pack the last forward left (never packs(): in training mode that
+        would normalise the master weight a second time); built once per weight version in evaluation mode, per call in
+        training mode (the plan rewrites its pack buffers in place every step)."""
+        if self._cache is None or self._cache[0] is None or self.weight.dim() != 4 or self._taps() != 9:
+            raise RuntimeError("tinyedm_amd: conv_in's input gradient needs the forward pack of a 3x3 conv (run a forward first)")
+        w = self.weight
+        key = (w.data_ptr(), w._version, _WEIGHT_EPOCH, self._cache[0].data_ptr(), int(cimg))
+        hit = self.__dict__.get("_in_dgrad")
+        if self.training or hit is None or hit[0] != key:
+            wf = self._cache[0]                                  # (9, O, Ipad) bf16
+            nt = ops.conv_in_dgrad_pack_cols(cimg)
+            with torch.no_grad():
+                pack = torch.zeros(wf.shape[1], nt, device=wf.device, dtype=f32)
+                pack[:, :9 * cimg] = wf[:, :, :cimg].permute(1, 0, 2).reshape(wf.shape[1], 9 * cimg).float()
+            hit = self.__dict__["_in_dgrad"] = (key, pack)
+        return hit[1]
 
     def extra_repr(self) -> str:
         return f"{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}"
@@ -742,6 +775,10 @@ class _ConcatGateFn(torch.autograd.Function):
         skip, mean, gate, z1, w1h, w2h = ctx.saved_tensors
         gcat = gcat.contiguous()
         Ci, Cs = ctx.Ci, skip.shape[-1]
+        if _DGRAD_ONLY[0] and SKIP_GATE_FUSED:       # input_vjp: the per-sample pass alone, no weight-gradient sums
+            gmean, _ws = ops.skip_gate_bwd(gcat, Ci, skip, mean, w1h, w2h, gate, z1, defer_wgrad=True)
+            ginp, gskip = ops.concat_gate_bwd(gcat, gate, gmean, Ci)
+            return ginp, gskip, None, None, None, None
         if SKIP_GATE_FUSED:
             gmean, gw1h, gw2h = ops.skip_gate_bwd(gcat, Ci, skip, mean, w1h, w2h, gate, z1)
         else:
@@ -1145,6 +1182,13 @@ class _ResBlockFn(torch.autograd.Function):
         ggain_out = gp.grad if gdirect else None
         deferred = False
         fused = ops.FUSE_MOD and ops.IGEMM_VERSION == 0 and (gout.shape[1] * gout.shape[2]) % 32 == 0
+        # dgrad-only (input_vjp): the raw modulation gradient goes to a scratch buffer that nobody finishes -- the same
+        # kernels write the same gr1; no gain gradient, no d loss / d lin, no flag or hook of a parameter is touched
+        only = _DGRAD_ONLY[0]
+        gm_only = ops.zeros_f32((lin.shape[0], lin.shape[-1]), gout.device) if only else None
+
+        def gm_of(deferred):
+            return gm_only if only else (ctx.gm_view if deferred else None)
         tail = tfwd = None
         if ctx.tail_fwd:
             # the handle's gradient carries nothing: everything comes from what _TailOutFn.backward left in the slot
@@ -1170,8 +1214,8 @@ class _ResBlockFn(torch.autograd.Function):
             Wc = tfwd[3] if tfwd is not None else ops.lowrank_expand_wc(tail[1], wd2)
             gr1, glin, ggain = ops.lowrank_dgrad3x3_modbwd(tail[0], Wc, b, r1, lin, gain, pdrop,
                                                              seed, sub, step, glin_out=glin_out, ggain_out=ggain_out, dyn=dyn,
-                                                             gm_out=ctx.gm_view if deferred else None, u_marked=ctx.u_marked)
-            if deferred:
+                                                             gm_out=gm_of(deferred), u_marked=ctx.u_marked)
+            if deferred and not only:
                 gp._edm_deferred = True
         elif fused:
             # conv2's dgrad with the modulation backward in its epilogue: ga2 never touches HBM.  With a shared gm buffer
@@ -1180,9 +1224,9 @@ class _ResBlockFn(torch.autograd.Function):
             # final (`_edm_deferred`: the data-parallel reducer must not count it yet)
             deferred = ctx.gm_view is not None and gdirect
             gr1, glin, ggain = ops.conv3x3_modbwd(gout, wd2, b, r1, lin, gain, pdrop, seed, sub, step, glin_out=glin_out,
-                                                     ggain_out=ggain_out, dyn=dyn, gm_out=ctx.gm_view if deferred else None,
+                                                     ggain_out=ggain_out, dyn=dyn, gm_out=gm_of(deferred),
                                                      u_marked=ctx.u_marked)
-            if deferred:
+            if deferred and not only:
                 gp._edm_deferred = True
         else:
             # (maps whose H*W is no multiple of 32 -- MNIST's 28x28 / 14x14 / 7x7 levels: the fused epilogue's 32-pixel MFMA row
@@ -1191,12 +1235,12 @@ class _ResBlockFn(torch.autograd.Function):
             deferred = MOD_DEFER_UNFUSED and ctx.gm_view is not None and gdirect
             ga2 = ops.conv_igemm(gout, wd2, 9, alpha=b)
             gr1, glin, ggain = ops.mod_silu_drop_bwd(r1, lin, gain, ga2, pdrop, seed, sub, step, glin_out=glin_out,
-                                                        ggain_out=ggain_out, dyn=dyn, gm_out=ctx.gm_view if deferred else None)
-            if deferred:
+                                                        ggain_out=ggain_out, dyn=dyn, gm_out=gm_of(deferred))
+            if deferred and not only:
                 gp._edm_deferred = True
         if gdirect:
             ggain = None
-            if not deferred:
+            if not deferred and not only:
                 for hook in getattr(gp, "_edm_hooks", ()):
                     hook(gp)
         if tfwd is not None:
@@ -1207,7 +1251,9 @@ class _ResBlockFn(torch.autograd.Function):
             gw2 = _wgrad(blk.conv_3x3_2, a2, gout, 9, b)
         gwemb = gemb = gtoken = None
         if ctx.batched:
-            gtoken = ops.zeros_f32((1,), gout.device) if ctx.has_token else None
+            gtoken = ops.zeros_f32((1,), gout.device) if (ctx.has_token and not only) else None
+        elif only:
+            pass
         else:
             dweh = ops.linear_wgrad(glin, emb)
             gwemb = blk.embed.finish_grad(dweh.view(1, 1, *dweh.shape))
@@ -1262,7 +1308,19 @@ class _ResBlockFn(torch.autograd.Function):
             defer = SG_DEFER and all(w.grad is not None and getattr(w, "_edm_direct", False) for w in wsl)
             sgb = getattr(ctx, "sgb", None)
             queued = False
-            if gcs is None:             # (no split form for this shape: the skip half is read out of gcat in place)
+            if only:
+                # dgrad-only: the per-sample pass alone (it yields d loss / d mean); the batch sums of the gate MLPs' weight
+                # gradients are never reduced, nothing is queued for the end of the pass
+                if gcs is None:
+                    gmean, _ws = ops.skip_gate_bwd(gu, Ci, skip, mean, w1h, w2h, gate, z1, defer_wgrad=True)
+                    gu, gskip = ops.concat_gate_bwd(gu, gate, gmean, Ci)
+                elif defer and sgb is not None and SG_BWD_MULTI:
+                    gskip = torch.empty_like(gcs)
+                    sgb.pending.append((gcs, skip, w1h, w2h, gate, z1, gskip, sl, mean))
+                else:
+                    gmean, _ws = ops.skip_gate_bwd(gcs, 0, skip, mean, w1h, w2h, gate, z1, defer_wgrad=True)
+                    gskip = ops.skip_half_bwd(gcs, gate, gmean)
+            elif gcs is None:             # (no split form for this shape: the skip half is read out of gcat in place)
                 gmean, *gws = ops.skip_gate_bwd(gu, Ci, skip, mean, w1h, w2h, gate, z1, defer_wgrad=defer)
                 gu, gskip = ops.concat_gate_bwd(gu, gate, gmean, Ci)
             elif defer and sgb is not None and SG_BWD_MULTI:
@@ -1275,7 +1333,9 @@ class _ResBlockFn(torch.autograd.Function):
             else:
                 gmean, *gws = ops.skip_gate_bwd(gcs, 0, skip, mean, w1h, w2h, gate, z1, defer_wgrad=defer)
                 gskip = ops.skip_half_bwd(gcs, gate, gmean)
-            if defer:       # the batch sums of every gate's weight gradients: one launch at the end of the pass (_flush_sg)
+            if only:
+                pass
+            elif defer:     # the batch sums of every gate's weight gradients: one launch at the end of the pass (_flush_sg)
                 if not queued:
                     _sg_pending.setdefault(wsl[0].device.index, []).append((sl, gws[0], mean, w1h.shape[0]))
                 wsl[0]._edm_deferred = wsl[1]._edm_deferred = True
@@ -1676,7 +1736,7 @@ class _EmbedAllFn(torch.autograd.Function):
         glin_all = ops.zeros_f32(lin_all.shape, lin_all.device)
         # shared raw modulation-gradient buffer + the per-block table of ONE finish launch (only when every block gain's
         # gradient lives in the flat arena; otherwise the blocks finish one by one)
-        table = den._modfin_table(blocks) if any(ctx.needs_input_grad) else None
+        table = den._modfin_table(blocks) if (any(ctx.needs_input_grad) and not _DGRAD_ONLY[0]) else None
         gm_all = ops.zeros_f32(lin_all.shape, lin_all.device) if table is not None else None
         ctx.den, ctx.glin_all, ctx.gm_all, ctx.lin_all, ctx.table = den, glin_all, gm_all, lin_all, table
         ctx.save_for_backward(emb, wcat)
@@ -1691,6 +1751,8 @@ class _EmbedAllFn(torch.autograd.Function):
     def backward(ctx, _g1, _g2, _gtoken, _g4=None):
         emb, wcat = ctx.saved_tensors
         glin_all = ctx.glin_all
+        if _DGRAD_ONLY[0]:          # (input_vjp never reaches this node: it lies on no path to the image)
+            return (None, None) + (None,) * len(ctx.den._res_blocks())
         if ctx.gm_all is not None:
             # every block's modulation finish in one launch; the block gains' gradients are final from here on
             ops.mod_finish_multi(ctx.gm_all, ctx.lin_all, glin_all, ctx.table, len(ctx.den._res_blocks()))
@@ -1710,32 +1772,54 @@ class _EmbedAllFn(torch.autograd.Function):
         return (gemb, None, *gws)
 
 
+def _noisy_grad(ctx, index: int, dD: Tensor, sigma: Tensor):
+    """The c_skip * dD term of d loss / d noisy at the output end (networks.py:602-603), when the image requires grad.  Inside a
+    Denoiser forward it is not formed here: dD is left in `link` -- the list this forward's _ConvInFn shares -- and conv_in's
+    backward, which runs later in the same pass, adds the term inside its own kernel (no extra pass, no autograd add)."""
+    if not ctx.needs_input_grad[index]:
+        return None
+    if ctx.link is not None:
+        ctx.link.append(dD)
+        return None
+    sd = ctx.den.sigma_data
+    s = sigma.view(-1, 1, 1, 1)
+    return dD * (sd * sd / (s * s + sd * sd))
+
+
 class _ConvInFn(torch.autograd.Function):
     """c_in * noisy, ones channel, conv_in 3x3 (networks.py:584-587); input padded to 32 channels."""
 
     @staticmethod
-    def forward(ctx, noisy, sigma, w, den: "Denoiser"):
+    def forward(ctx, noisy, sigma, w, den: "Denoiser", link=None):
         wf, _, _ = den.conv_in.packs()
         xin = ops.precond_in(noisy, sigma, den.sigma_data, den.conv_in._ipad)
-        ctx.den = den
-        ctx.save_for_backward(xin)
+        ctx.den, ctx.link = den, link
+        ctx.save_for_backward(xin, sigma)
         return ops.conv_igemm(xin, wf, 9)
 
     @staticmethod
     def backward(ctx, gy):
-        (xin,) = ctx.saved_tensors
-        gw = _wgrad(ctx.den.conv_in, xin, gy.contiguous(), 9)
-        return None, None, gw, None
+        xin, sigma = ctx.saved_tensors
+        gy = gy.contiguous()
+        gw = _wgrad(ctx.den.conv_in, xin, gy, 9) if ctx.needs_input_grad[2] else None
+        gnoisy = None
+        if ctx.needs_input_grad[0]:
+            # the image gradient: conv_in's dgrad into the Cimg real channels (the ones channel is a constant), times c_in,
+            # plus the c_skip * dD term that the output end left in `link` (one kernel, fp32 out; csrc/conv_in_dgrad.hip)
+            den = ctx.den
+            gD = ctx.link.pop() if ctx.link else None
+            gnoisy = ops.conv_in_dgrad(gy, den.conv_in.in_dgrad_pack(den.in_channels), gD, sigma, den.sigma_data)
+        return gnoisy, None, gw, None, None
 
 
 class _ConvOutFn(torch.autograd.Function):
     """conv_out * gain_out * c_out + noisy * c_skip (networks.py:602-603), fp32 NCHW result."""
 
     @staticmethod
-    def forward(ctx, x, w, gain_out, noisy, sigma, den: "Denoiser"):
+    def forward(ctx, x, w, gain_out, noisy, sigma, den: "Denoiser", link=None):
         wh = den.conv_out.packs()[2]
         D, Fraw = ops.conv_out_fwd(x, wh, gain_out, noisy, sigma, den.sigma_data, want_fraw=True)
-        ctx.den = den
+        ctx.den, ctx.link = den, link
         ctx.save_for_backward(x, wh, gain_out, Fraw, sigma)
         return D
 
@@ -1749,6 +1833,16 @@ class _ConvOutFn(torch.autograd.Function):
         gdirect = gp.grad is not None and getattr(gp, "_edm_direct", False) and gp.grad.is_contiguous()
         w = ctx.den.conv_out.weight
         dD = gD.contiguous().float()
+        gnoisy = _noisy_grad(ctx, 3, dD, sigma)
+        if _DGRAD_ONLY[0]:
+            # input_vjp: the input gradient alone, by the kernel the training backward of this parameter state would use
+            # (and the rank-Co factor for the last block where that backward leaves it); no weight or gain gradient
+            gx = ops.conv_out_bwd_x(wh, gain_out, dD, sigma, ctx.den.sigma_data, x.shape[-1])
+            if (TAIL_LOWRANK and w.grad is not None and getattr(w, "_edm_direct", False)
+                    and ops.lowrank_supported(x.shape[-1], wh.shape[0], x.shape[2], 1)):
+                dF, _ = ops.lowrank_df(dD, None, gain_out, sigma, ctx.den.sigma_data, want_aux=False)
+                _tail_slot[gx.device.index] = (dF, wh, gx)
+            return gx, None, None, gnoisy, None, None, None
         if (TAIL_LOWRANK and w.grad is not None and getattr(w, "_edm_direct", False)
                 and ops.lowrank_supported(x.shape[-1], wh.shape[0], x.shape[2], 1)):
             # dF once; weight and gain gradients from the one-tap low-rank reduction (deterministic: no atomics); the last
@@ -1767,7 +1861,7 @@ class _ConvOutFn(torch.autograd.Function):
             for hook in getattr(gp, "_edm_hooks", ()):
                 hook(gp)
         gw = ctx.den.conv_out.finish_grad(gwh.view(1, 1, *gwh.shape))
-        return gx, gw, gg, None, None, None
+        return gx, gw, gg, gnoisy, None, None, None
 
 
 class _TailOutFn(torch.autograd.Function):
@@ -1778,8 +1872,9 @@ class _TailOutFn(torch.autograd.Function):
     slot (dF, Wout_hat, handle gradient, G, G1, Wp, Wc) from which the block's backward takes everything g_h fed."""
 
     @staticmethod
-    def forward(ctx, handle, w, gain_out, noisy, sigma, den: "Denoiser", pack):
+    def forward(ctx, handle, w, gain_out, noisy, sigma, den: "Denoiser", pack, link=None):
         a2, cat, wf2, wd2, wf11, wd11, a, b = pack
+        ctx.link = link
         wh = den.conv_out.packs()[2]
         Wc = ops.lowrank_expand_wc(wh, wd2)
         Wp = ops.lowrank_expand_wc(wh, wd11).view(wh.shape[0], -1) if wd11 is not None else wh
@@ -1798,6 +1893,13 @@ class _TailOutFn(torch.autograd.Function):
         gdirect = gp.grad is not None and getattr(gp, "_edm_direct", False) and gp.grad.is_contiguous()
         w = den.conv_out.weight
         dD = gD.contiguous().float()
+        gnoisy = _noisy_grad(ctx, 3, dD, sigma)
+        if _DGRAD_ONLY[0]:
+            # input_vjp: dF and the tables are all the block's data gradients need; no reduction over pixels is launched
+            dF, _ = ops.lowrank_df(dD, None, gain_out, sigma, den.sigma_data, want_aux=False)
+            gx = torch.empty(ctx.hshape, device=dD.device, dtype=bf16)
+            _tail_slot[dD.device.index] = (dF, wh, gx, None, None, Wp, Wc)
+            return gx, None, None, gnoisy, None, None, None, None
         dF, aux = ops.lowrank_df(dD, Fraw, gain_out, sigma, den.sigma_data)
         G1, gg = ops.lowrank_wgrad(dF, cat, 1, aux=aux, aux_out=gp.grad if gdirect else None)
         if gdirect:
@@ -1819,7 +1921,7 @@ class _TailOutFn(torch.autograd.Function):
         _tail_slot[dD.device.index] = (dF, wh, gx, G, G1, Wp, Wc)
         _queue_backward_end(dD.device)      # (empties the slot if the block's backward never runs)
         gw = den.conv_out.finish_grad(gwh.view(1, 1, *gwh.shape))
-        return gx, gw, gg, None, None, None, None
+        return gx, gw, gg, gnoisy, None, None, None, None
 
 
 class Denoiser(nn.Module):
@@ -1887,13 +1989,13 @@ class Denoiser(nn.Module):
     def _res_blocks(self):
         return list(self.encoder_blocks) + list(self.decoder_blocks)
 
-    def _conv_out_of(self, x: Tensor, noisy: Tensor, sig: Tensor) -> Tensor:
+    def _conv_out_of(self, x: Tensor, noisy: Tensor, sig: Tensor, link=None) -> Tensor:
         """conv_out + output preconditioning of the last decoder block's result x -- or, where that block (called with
         _tail=self._tail_fwd_co()) left its operands in _tail_fwd_slot and returned a zero-size handle, the factored form"""
         pack = _tail_fwd_slot.pop(x.device.index, None)
         if pack is not None:
-            return _TailOutFn.apply(x, self.conv_out.weight, self.gain_out, noisy, sig, self, pack)
-        return _ConvOutFn.apply(x, self.conv_out.weight, self.gain_out, noisy, sig, self)
+            return _TailOutFn.apply(x, self.conv_out.weight, self.gain_out, noisy, sig, self, pack, link)
+        return _ConvOutFn.apply(x, self.conv_out.weight, self.gain_out, noisy, sig, self, link)
 
     def _tail_fwd_co(self) -> int:
         """conv_out's channel count when the last decoder block + conv_out may run in factored form (TAIL_FWD), else 0: the
@@ -1906,7 +2008,7 @@ class Denoiser(nn.Module):
         for m in (blk, self.conv_out):      # a hook would see (or replace) the handle instead of the block's output
             if m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or m._backward_pre_hooks:
                 return 0
-        if torch.is_grad_enabled():         # the backward writes these three gradients through the arena's finish queue
+        if torch.is_grad_enabled() and not _DGRAD_ONLY[0]:   # the backward writes these three gradients through the arena's finish queue
             ws = [blk.conv_3x3_2.weight, self.conv_out.weight]
             if isinstance(blk.conv_1x1, Conv2d):
                 ws.append(blk.conv_1x1.weight)
@@ -2126,7 +2228,7 @@ class Denoiser(nn.Module):
                     _SPLIT_EVAL[0] = False
             return D.to(noisy_image.dtype)
         reset_backward_state()
-        if torch.is_grad_enabled():      # eval-mode forwards with autograd on (fine-tuning, parity runs) write gradients too
+        if torch.is_grad_enabled() and not _DGRAD_ONLY[0]:      # eval-mode forwards with autograd on (fine-tuning, parity runs) write gradients too
             global FORWARD_EPOCH
             FORWARD_EPOCH += 1
         with torch.no_grad():
@@ -2148,7 +2250,9 @@ class Denoiser(nn.Module):
                        None if gm_all is None else gm_all[:, off:off + C])
             off += C
 
-        x = _ConvInFn.apply(noisy, sig, self.conv_in.weight, self)
+        # (the image requires grad: the output end hands its c_skip * dD to conv_in's backward through this list)
+        link = [] if (torch.is_grad_enabled() and noisy.requires_grad) else None
+        x = _ConvInFn.apply(noisy, sig, self.conv_in.weight, self, link)
         skips = []
         dec = list(zip(self.decoder_blocks, self.skip_connections))
         enc = list(self.encoder_blocks)
@@ -2179,7 +2283,7 @@ class Denoiser(nn.Module):
                 xin._edm_cat = cat_pre
             last = {"_tail": tail_co} if (tail_co and i + 1 == len(dec)) else {}
             x = block(xin, None, _tag(skip) if has_skip else None, _lin=lins[block], _dest=dest, _gate=gates.get(block), **last)
-        D = self._conv_out_of(x, noisy, sig)
+        D = self._conv_out_of(x, noisy, sig, link)
         if self.training:
             rng.step += 1
         return D.to(noisy_image.dtype)
@@ -2211,6 +2315,8 @@ class _SgbPass:
                 for (gcs, skip, w1h, w2h, gate, z1, gskip, sl, mean), (gmean, ws) in zip(part, res):
                     if not SG_HALVES:
                         halves.append((gcs, gate, gmean, gskip))
+                    if _DGRAD_ONLY[0]:      # (input_vjp: the gates' weight gradients are not reduced)
+                        continue
                     _sg_pending.setdefault(sl.layer1.weight.device.index, []).append((sl, ws, mean, w1h.shape[0]))
         for k0 in range(0, len(halves), 32):
             ops.skip_half_bwd_multi(halves[k0:k0 + 32])

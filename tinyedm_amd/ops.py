@@ -2110,6 +2110,130 @@ def project_denoised(Dm, y, scale, gray, Dg=None, w_dev=None, out=None):
     return out
 
 
+# ------------------------------------------------------------------ diffusion posterior sampling (csrc/restore.hip)
+BLUR_MAX_RADIUS = 4
+
+
+def degrade_adjoint(r, channels, scale, gray):
+    """A^T r for the averaging A of degrade(): r (contiguous fp32, the measurement shape of a [B, channels, H, W] image) ->
+    [B, channels, H, W], every value replicated to its block (and channels, gray) and divided by the block size"""
+    _chk(r, f32, "r")
+    if r.dim() != 4:
+        raise ValueError(f"degrade_adjoint: expected a [B, C', h, w] measurement, got {tuple(r.shape)}")
+    shape = (r.shape[0], int(channels), r.shape[2] * scale, r.shape[3] * scale)
+    if tuple(r.shape) != measurement_shape(shape, scale, gray):
+        raise ValueError(f"degrade_adjoint: r of shape {tuple(r.shape)} is no measurement of a {channels}-channel image")
+    out = torch.empty(shape, device=r.device, dtype=f32)
+    _lib.call("edm_degrade_adjoint", _p(r), _p(out), *shape, scale, int(gray), _stream())
+    return out
+
+
+def gaussian_taps(std, radius) -> tuple:
+    """the 2*radius+1 normalised taps exp(-k^2 / (2 std^2)) / sum of a GaussianBlur, as fp32 values (host only)"""
+    if isinstance(radius, bool) or not isinstance(radius, int) or not 1 <= radius <= BLUR_MAX_RADIUS:
+        raise ValueError(f"blur: radius must be an integer in [1, {BLUR_MAX_RADIUS}], got {radius!r}")
+    std = float(std)
+    if not (math.isfinite(std) and std > 0.0):
+        raise ValueError(f"blur: std must be positive and finite, got {std}")
+    raw = [math.exp(-(k * k) / (2.0 * std * std)) for k in range(-radius, radius + 1)]
+    tot = sum(raw)
+    return tuple(float(torch.tensor(v / tot, dtype=f32)) for v in raw)
+
+
+def blur2d(x, taps):
+    """y = K x: the separable zero-padded blur with the odd-length tap tuple `taps` on every H x W plane of x (contiguous
+    fp32 [..., H, W]); order-fixed fma chains (include/tinyedm_hip.h)"""
+    _chk(x, f32, "x")
+    if x.dim() < 2 or x.numel() == 0:
+        raise ValueError(f"blur2d: expected a non-empty [..., H, W] tensor, got {tuple(x.shape)}")
+    n = len(taps)
+    if n % 2 == 0 or not 3 <= n <= 2 * BLUR_MAX_RADIUS + 1:
+        raise ValueError(f"blur2d: 3, 5, 7 or 9 taps, got {n}")
+    H, W = x.shape[-2:]
+    y = torch.empty_like(x)
+    arr = (ctypes.c_float * n)(*[float(t) for t in taps])
+    _lib.call("edm_blur2d", _p(x), _p(y), ctypes.cast(arr, ctypes.c_void_p), n // 2, x.numel() // (H * W), H, W, _stream())
+    return y
+
+
+def dps_residual(y, AD):
+    """(r, nrm): r = y - AD (contiguous fp32 [B, ...] of one shape) and nrm[b] = ||r_b||_2, an order-fixed reduction (the same
+    bits on every run and for every B)"""
+    _chk(y, f32, "y")
+    _chk(AD, f32, "AD", y.shape)
+    if y.dim() < 2 or y.numel() == 0:
+        raise ValueError(f"dps_residual: expected a non-empty [B, ...] tensor, got {tuple(y.shape)}")
+    if AD.device != y.device:
+        raise ValueError(f"AD: expected a tensor on {y.device}, got {AD.device}")
+    B = y.shape[0]
+    r = torch.empty_like(y)
+    nrm = torch.empty(B, device=y.device, dtype=f32)
+    _lib.call("edm_dps_residual", _p(y), _p(AD), _p(r), _p(nrm), B, y.numel() // B, _stream())
+    return r, nrm
+
+
+def dps_update(x, g, nrm, scale):
+    """x + (scale / nrm[b]) * g per sample (x where nrm[b] == 0 or scale == 0, bit for bit): contiguous fp32 [B, ...], nrm [B]"""
+    _chk(x, f32, "x")
+    _chk(g, f32, "g", x.shape)
+    if x.dim() < 2 or x.numel() == 0:
+        raise ValueError(f"dps_update: expected a non-empty [B, ...] tensor, got {tuple(x.shape)}")
+    B = x.shape[0]
+    _chk(nrm, f32, "nrm", (B,))
+    for t, nme in ((g, "g"), (nrm, "nrm")):
+        if t.device != x.device:
+            raise ValueError(f"{nme}: expected a tensor on {x.device}, got {t.device}")
+    scale = float(scale)
+    if not (math.isfinite(scale) and scale >= 0.0):
+        raise ValueError(f"dps_update: scale must be finite and >= 0, got {scale}")
+    out = torch.empty_like(x)
+    _lib.call("edm_dps_update", _p(x), _p(g), _p(nrm), scale, _p(out), B, x.numel() // B, _p(health(x.device)), _stream())
+    return out
+
+
+# ------------------------------------------------------------------ the input gradient of the denoiser (csrc/conv_in_dgrad.hip)
+CONV_IN_DGRAD_MAX_CIMG = 8
+
+
+def conv_in_dgrad_pack_cols(cimg: int) -> int:
+    """columns of conv_in_dgrad's weight pack for `cimg` image channels (a host query, not a launch)"""
+    return int(_lib.lib().edm_conv_in_dgrad_pack_cols(int(cimg)))
+
+
+def conv_in_dgrad(gy, wpack, gD, sigma, sigma_data):
+    """gx (fp32 NCHW [B, Cimg, H, W]) = c_in * dgrad3x3(gy; w^) [+ c_skip * gD]: the gradient of the denoiser's INPUT image from
+    gy (bf16 NHWC [B, H, W, C0]: d loss / d conv_in's output; a 2-byte aligned view is accepted) and, optionally, the
+    cotangent gD of D (fp32 NCHW like gx; the noisy * c_skip term of networks.py:602-603).  wpack: fp32 [C0, NT] from
+    Conv2d.in_dgrad_pack(Cimg); Cimg = gD's channel count, else NT // 9.  fp32 accumulation, order-fixed, independent of B."""
+    if not isinstance(gy, torch.Tensor) or not gy.is_cuda or gy.dtype != bf16 or gy.dim() != 4 or not gy.is_contiguous():
+        raise ValueError("conv_in_dgrad: gy must be a contiguous bf16 (B, H, W, C0) GPU tensor")
+    B, H, W, C0 = gy.shape
+    _chk(wpack, f32, "wpack")
+    if wpack.dim() != 2 or wpack.shape[0] != C0:
+        raise ValueError(f"conv_in_dgrad: wpack must be (C0 = {C0}, NT), got {tuple(wpack.shape)}")
+    NT = wpack.shape[1]
+    if gD is not None:
+        _chk(gD, f32, "gD")
+        if gD.dim() != 4 or (gD.shape[0], gD.shape[2], gD.shape[3]) != (B, H, W):
+            raise ValueError(f"conv_in_dgrad: gD {tuple(gD.shape)} does not match gy {tuple(gy.shape)}")
+        cimg = gD.shape[1]
+    else:
+        cimg = NT // 9
+    if not 1 <= cimg <= CONV_IN_DGRAD_MAX_CIMG or conv_in_dgrad_pack_cols(cimg) != NT:
+        raise ValueError(f"conv_in_dgrad: {cimg} image channels do not match a pack of {NT} columns")
+    if B < 1 or H < 1 or W < 1 or C0 < 1 or B > 65535:
+        raise ValueError(f"conv_in_dgrad: bad shape {tuple(gy.shape)}")
+    ss = _sigma_arg(sigma, B)
+    for t, nme in ((wpack, "wpack"), (gD, "gD"), (sigma, "sigma")):
+        if t is not None and t.device != gy.device:
+            raise ValueError(f"{nme}: expected a tensor on {gy.device}, got {t.device}")
+    gx = torch.empty(B, cimg, H, W, device=gy.device, dtype=f32)
+    with _prof("conv_in_dgrad", 2.0 * B * H * W * C0 * 9 * cimg, 2.0 * gy.numel() + 4.0 * gx.numel() * (2 if gD is not None else 1)):
+        _lib.call("edm_conv_in_dgrad", _p(gy), _p(wpack), _p(gD), _p(sigma), ss, float(sigma_data), _p(gx), B, cimg, H, W, C0,
+                  _stream())
+    return gx
+
+
 NLL_MAX_PROBES = 32             # a probe is one bit of a Philox word
 NLL_MAX_STEPS = 1 << 16         # step < 2**16 keeps the probe tags apart from the churn's and the blend's
 NLL_MAX_CHUNKS = 64             # EDM_NLL_MAX_CHUNKS: per-sample partial sums of the order-fixed reduction

@@ -149,6 +149,63 @@ class LinearDegradation:
         _check_gpu("LinearDegradation", "y", y)
         return ops.project_denoised(torch.zeros(shape, device=y.device), y.float().contiguous(), self.scale, self.gray)
 
+    def adjoint(self, r, channels: int) -> torch.Tensor:
+        """A^T r, fp32 [B, channels, H*scale, W*scale]: r replicated to its blocks (and channels, with ``gray``) and divided
+        by the block size n -- exactly the transpose of the averaging A (<A u, v> = <u, A^T v>); A+ = n A^T."""
+        if not isinstance(r, torch.Tensor) or not r.dtype.is_floating_point or r.dim() != 4:
+            raise ValueError("LinearDegradation.adjoint: r must be a floating-point [B, C', h, w] tensor")
+        if isinstance(channels, bool) or not isinstance(channels, int) or channels < 1:
+            raise ValueError(f"LinearDegradation.adjoint: channels must be a positive integer, got {channels!r}")
+        shape = (r.shape[0], channels, r.shape[2] * self.scale, r.shape[3] * self.scale)
+        if tuple(r.shape) != self.measurement_shape(shape):
+            raise ValueError(f"LinearDegradation.adjoint: r of shape {tuple(r.shape)} is no measurement of a "
+                             f"{channels}-channel image")
+        _check_gpu("LinearDegradation", "r", r)
+        return ops.degrade_adjoint(r.float().contiguous(), channels, self.scale, self.gray)
+
+
+@dataclass(frozen=True)
+class GaussianBlur:
+    """A measurement operator of diffusion posterior sampling (``solve(..., operator=, measurement=, dps_scale=)``): a
+    separable Gaussian blur of every channel with ``2 * radius + 1`` taps exp(-k^2 / (2 std^2)), normalised to sum 1
+    (``radius`` 1..4), and ZERO padding, so y has the image's shape and -- the taps being symmetric -- the operator is its
+    own adjoint.  One small kernel (ops.blur2d).  It has no cheap pseudo-inverse: DDNM (``degradation=``) does not take it."""
+    std: float = 1.0
+    radius: int = 2
+
+    def __post_init__(self):
+        ops.gaussian_taps(self.std, self.radius)
+
+    @property
+    def taps(self) -> tuple:
+        """the normalised taps as fp32 values"""
+        return ops.gaussian_taps(self.std, self.radius)
+
+    def measurement_shape(self, x_shape) -> tuple:
+        if len(x_shape) != 4 or any(int(v) < 1 for v in x_shape):
+            raise ValueError(f"GaussianBlur: expected a non-empty [B, C, H, W] shape, got {tuple(x_shape)}")
+        return tuple(int(v) for v in x_shape)
+
+    def measure(self, image) -> torch.Tensor:
+        """y = A image, fp32 [B, C, H, W]; ``image``: a floating-point GPU tensor [B, C, H, W]"""
+        _check_float("GaussianBlur.measure", "image", image)
+        self.measurement_shape(image.shape)
+        _check_gpu("GaussianBlur", "image", image)
+        return ops.blur2d(image.float().contiguous(), self.taps)
+
+    def adjoint(self, r, channels: int | None = None) -> torch.Tensor:
+        """A^T r = A r (zero padding, symmetric taps)"""
+        if channels is not None and (not isinstance(r, torch.Tensor) or r.dim() != 4 or r.shape[1] != channels):
+            raise ValueError(f"GaussianBlur.adjoint: r must be a [B, {channels}, H, W] tensor")
+        return self.measure(r)
+
+
+class _Dps(NamedTuple):
+    """the posterior-sampling conditioning of one solve"""
+    op: object              # LinearDegradation or GaussianBlur
+    y: torch.Tensor         # fp32, the measurement shape of the state
+    scale: float            # zeta >= 0
+
 
 class _Restoration(NamedTuple):
     """the measurement conditioning of one solve (a captured entry owns a static copy of y)"""
@@ -213,6 +270,12 @@ class DeterministicSolver:
     with ``measurement`` raises ValueError, and so does any invalid combination, on the host before any launch.  Noisy
     measurements (DDNM+), time travel / resampling and blur kernels are not implemented; ``invert`` and
     ``log_likelihood`` do not take the arguments.
+    Diffusion posterior sampling (keyword-only ``operator``, ``measurement``, ``dps_scale`` of ``solve``; Chung et al. 2023
+    in EDM / Heun form; Heun solvers, eager, bf16 evaluation path): step i evaluates D = model(x_i, t_i) with its input
+    gradient, forms r = y - A D and g = J^T A^T r (``tinyedm.input_vjp``'s dgrad-only backward), takes the ordinary Euler +
+    Heun step to x' and returns x' + (dps_scale / ||r_b||) g per sample (x' where the residual is zero).  ``operator`` is a
+    ``LinearDegradation`` or a ``GaussianBlur``; y may be noisy; ``dps_scale=0`` is the plain solve bit for bit.  With
+    ``degradation=``, a guide, ``mask=``, ``graph=True`` or ``MultistepSolver`` it raises ValueError.
     ``invert`` runs the probability-flow ODE upwards, image -> latent; ``log_likelihood`` does the same and integrates
     the change of variables along the way (keyword-only ``delta``: the relative half-width of its central difference)."""
 
@@ -404,7 +467,66 @@ class DeterministicSolver:
                 ops.heun_correct_guided(x, dx, x1, D1, Dg1, w_dev, t0, t1)
         return x1
 
-    def _loop(self, model, x0, class_labels, t_dev, guided, w_dev, state=None, cond=None, rest=None):
+    # ------------------------------------------------------------------ diffusion posterior sampling
+    def _posterior(self, model, x0, guided, mask, graph, degradation, operator, measurement, dps_scale):
+        """Validate operator / measurement / dps_scale of a solve on the host (nothing is read from a device) and return
+        (operator, measurement, scale); None without an operator."""
+        if operator is None:
+            if dps_scale is not None:
+                raise ValueError("solve: dps_scale needs operator= (the measurement operator of posterior sampling)")
+            return None
+        if degradation is not None:
+            raise ValueError("solve: degradation= (DDNM projection) and operator= (posterior sampling) are two ways to use a "
+                             "measurement; give one")
+        if not isinstance(operator, (LinearDegradation, GaussianBlur)):
+            raise ValueError(f"solve: operator must be a LinearDegradation or a GaussianBlur, got {type(operator).__name__}")
+        if measurement is None:
+            raise ValueError("solve: operator and measurement go together (the operator and its y)")
+        if self.guide is not None or any(guided):
+            raise ValueError("solve: operator= (posterior sampling) with a guide is not implemented")
+        if mask is not None:
+            raise ValueError("solve: operator= (posterior sampling) with mask= (inpainting by replacement) is not implemented")
+        if type(self)._step is not DeterministicSolver._step:
+            raise ValueError(f"solve: operator= (posterior sampling) needs a Heun solver, not {type(self).__name__}")
+        if graph:
+            raise ValueError("solve: operator= (posterior sampling) with graph=True is not implemented (the step runs a "
+                             "backward pass)")
+        scale = 1.0 if dps_scale is None else dps_scale
+        if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not math.isfinite(scale) or scale < 0:
+            raise ValueError(f"solve: dps_scale must be a finite number >= 0, got {dps_scale!r}")
+        _check_float("solve", "measurement", measurement)
+        if x0.dim() != 4:
+            raise ValueError(f"solve: a measurement needs x0 of shape [B, C, H, W], got {tuple(x0.shape)}")
+        shape = operator.measurement_shape(x0.shape)
+        if tuple(measurement.shape) != shape:
+            raise ValueError(f"solve: measurement must have shape {shape} for x0 {tuple(x0.shape)} under {operator}, got "
+                             f"{tuple(measurement.shape)}")
+        if measurement.device != x0.device:
+            raise ValueError(f"solve: measurement is on {measurement.device}, x0 on {x0.device}")
+        from . import vjp
+        parts = vjp._library_parts(model)
+        if parts is not None and parts[1].eval_dtype != "bf16":
+            raise ValueError(f"solve: operator= (posterior sampling) needs the bf16 path (the one with a backward pass); the "
+                             f"denoiser evaluates in {parts[1].eval_dtype!r}: set_eval_dtype(\"bf16\") / --network_dtype bf16")
+        return operator, measurement, float(scale)
+
+    def _dps_step(self, model, class_labels, x1, i, ts, t_dev, state, dps):
+        """step i of a posterior-sampling solve (Chung et al. 2023 in EDM / Heun form): the ordinary step from the Euler
+        evaluation D -- taken with its input gradient -- then x' + (zeta / ||r||) J^T A^T r, r = y - A D"""
+        from .vjp import open_input_vjp
+        x, t0, s0 = self._step_start(x1, i, ts, t_dev, state)
+        t1 = ts[i + 1]
+        D, pullback = open_input_vjp(model, x, s0, class_labels)
+        D = D.contiguous()
+        r, nrm = ops.dps_residual(dps.y, dps.op.measure(D))
+        g = pullback(dps.op.adjoint(r, D.shape[1])).contiguous()
+        dx, x1 = ops.heun_euler(x, D, t0, t1)
+        if i < self.num_steps - 1:
+            D1 = model(x1, t_dev[i + 1], class_labels).float().contiguous()
+            x1 = ops.heun_correct(x, dx, x1, D1, t0, t1)
+        return ops.dps_update(x1, g, nrm, dps.scale)
+
+    def _loop(self, model, x0, class_labels, t_dev, guided, w_dev, state=None, cond=None, rest=None, dps=None):
         ts = self.t_steps.tolist()
         k = 0 if cond is None else cond.start
         masked = cond is not None and cond.mask is not None
@@ -415,6 +537,9 @@ class DeterministicSolver:
         for i in range(k, self.num_steps):
             if masked:
                 x = self._blend(x, cond, ts[i], i)
+            if dps is not None:
+                x = self._dps_step(model, class_labels, x, i, ts, t_dev, state, dps)
+                continue
             x = self._step(evaluate, x, i, ts, t_dev, guided, w_dev, state)
         if masked:
             x = self._blend(x, cond, 0.0, self.num_steps)
@@ -422,11 +547,12 @@ class DeterministicSolver:
 
     @torch.no_grad()
     def solve(self, model, x0, class_labels=None, graph: bool = False, *, start_step: int = 0, image=None, mask=None,
-              degradation=None, measurement=None):
+              degradation=None, measurement=None, operator=None, dps_scale=None):
         cond = self._conditioning(x0, start_step, image, mask)
-        rest = self._restoration(x0, mask, degradation, measurement)
-        _check_gpu("DeterministicSolver", "x0", x0)
         guided = self.guided_evaluations()
+        dps = self._posterior(model, x0, guided, mask, graph, degradation, operator, measurement, dps_scale)
+        rest = None if dps is not None else self._restoration(x0, mask, degradation, measurement)
+        _check_gpu("DeterministicSolver", "x0", x0)
         if any(guided):
             self._check_guide(model, x0.device, class_labels)
         in_dtype = x0.dtype
@@ -439,12 +565,14 @@ class DeterministicSolver:
                                  ops.churn_record(self.seed, self.solve_index, x0.device) if masked else None)
         if rest is not None:
             rest = _Restoration(rest[0].scale, rest[0].gray, rest[1].float().contiguous())
+        if dps is not None:
+            dps = _Dps(dps[0], dps[1].float().contiguous(), dps[2])
         start = 0 if cond is None else cond.start
         if not graph:
             t_dev = self.t_steps.to(x0.device)
             w_dev = torch.full((1,), float(self.guidance), device=x0.device) if any(guided) else None
             state = self._solve_state(x0, start)
-            out = self._loop(model, x0, class_labels, t_dev, guided, w_dev, state, cond, rest).to(in_dtype)
+            out = self._loop(model, x0, class_labels, t_dev, guided, w_dev, state, cond, rest, dps).to(in_dtype)
             self._solve_done(masked)
             return out
         mode = _Mode(self._graph_key_extra(start), lambda: self._solve_state(x0, start),
