@@ -98,6 +98,9 @@ its own contiguous index range with its own noise seed and writes `<global index
 from __future__ import annotations
 
 import argparse
+import functools
+import inspect
+import json
 import os
 
 import torch
@@ -249,26 +252,138 @@ def _psnr(x, ref, mean, std) -> torch.Tensor:
 def load_images(init_dir, mean, std, image_size, channels) -> torch.Tensor:
     """the PNGs of a directory as PreditionWriter names them (<index>.png), in numeric order of the index, normalised
     as PreditionWriter denormalises (pixel = x * std * 2 + mean): fp32 [n, C, H, W] on the host"""
-    import numpy as np
-    from PIL import Image
-    names = [f for f in os.listdir(init_dir) if f.lower().endswith(".png")]
-    bad = [f for f in names if not os.path.splitext(f)[0].isdigit()]
-    if bad:
-        raise ValueError(f"generate: --init_dir holds PNGs that are not named <index>.png: {sorted(bad)[:3]}")
-    if not names:
-        raise ValueError(f"generate: no PNG in {init_dir}")
+    from .neighbors import read_png_dir
     m = torch.tensor([float(v) for v in mean], dtype=torch.float32).view(-1, 1, 1)
     sd = torch.tensor([float(v) for v in std], dtype=torch.float32).view(-1, 1, 1)
-    out = []
-    for f in sorted(names, key=lambda f: int(os.path.splitext(f)[0])):
-        a = np.asarray(Image.open(os.path.join(init_dir, f)))
-        a = a[:, :, None] if a.ndim == 2 else a
-        if a.dtype != np.uint8 or a.shape != (image_size, image_size, channels):
-            raise ValueError(f"generate: {f} is {a.dtype} {a.shape}, expected uint8 {(image_size, image_size, channels)}")
-        # the inverse of PreditionWriter's clamp(x * std * 2 + mean, 0, 1) * 255, truncated: level u is the bin
-        # [u, u + 1) / 255, read at its centre, so an image written and read back is written as the same levels
-        out.append(((torch.from_numpy(a.copy()).permute(2, 0, 1).float() + 0.5) / 255.0 - m) / (2.0 * sd))
-    return torch.stack(out)
+    # the inverse of PreditionWriter's clamp(x * std * 2 + mean, 0, 1) * 255, truncated: level u is the bin
+    # [u, u + 1) / 255, read at its centre, so an image written and read back is written as the same levels
+    return torch.stack([((torch.from_numpy(a.copy()).permute(2, 0, 1).float() + 0.5) / 255.0 - m) / (2.0 * sd)
+                        for a in read_png_dir(init_dir, "generate", "--init_dir", image_size, channels)])
+
+
+def _validate(*, solver, S_churn, init_dir, start_step, num_steps, mask_box, invert_to, likelihood_to, network_dtype,
+              num_probes, dequantize, image_size, dps_scale, blur_std, blur_radius, measurement_noise, restore_scale,
+              restore_gray, save_degraded, restore_report, labels_to, guided) -> tuple:
+    """every choice that needs nothing loaded, checked once and in one order for generate() and the command line; returns
+    (posterior, restoring): whether the run samples with DPS, and whether it restores (DDNM or DPS)"""
+    _check_solver(solver, S_churn)
+    _check_conditioning(init_dir, start_step, mask_box, invert_to, solver, S_churn, image_size,
+                        likelihood_to=likelihood_to, network_dtype=network_dtype, num_probes=num_probes,
+                        dequantize=dequantize)
+    posterior = _check_posterior(dps_scale, blur_std, blur_radius, measurement_noise, restore_scale, restore_gray,
+                                 network_dtype, solver, guided)
+    restoring = _check_restoration(init_dir, restore_scale, restore_gray, save_degraded, restore_report, mask_box,
+                                   invert_to, likelihood_to, image_size, blur=posterior and blur_std is not None)
+    _check_labels_to(labels_to, init_dir)
+    if start_step >= num_steps:
+        raise ValueError(f"generate: --start_step must be below --num_steps = {num_steps}, got {start_step}")
+    return posterior, restoring
+
+
+def _rank_path(path, rank, world) -> str:
+    """the per-rank name of an output file: root.rankN.ext when there is more than one rank"""
+    root, ext = os.path.splitext(path)
+    return f"{root}.rank{rank}{ext}" if world > 1 else path
+
+
+def _write_json(path, obj) -> None:
+    with open(path, "w") as f:
+        json.dump(obj, f)
+
+
+def _run_invert(model, datamodule, invert_to, graph, end_step, num_steps, where) -> None:
+    """--invert_to.  The labels of each batch are the ones a solve of the same --seed draws: the latents close the loop"""
+    model.eval()
+    lat, lab = [], []
+    for x0, y, img in datamodule.predict_dataloader():
+        y = y if model.conditional else None
+        lat.append(model.solver.invert(model, img, y, graph=graph, end_step=end_step).cpu())
+        lab.append(None if y is None else y.cpu())
+    torch.save({"latents": torch.cat(lat) if lat else torch.empty(0), "end_step": end_step, "num_steps": num_steps,
+                "class_labels": None if not lab or lab[0] is None else torch.cat(lab)}, invert_to)
+    print(f"[rank {where[0]}] wrote the latents of images {where[1]} to {invert_to}", flush=True)
+
+
+def _run_likelihood(model, datamodule, likelihood_to, graph, end_step, num_probes, dequantize, rank_seed, std, dims, where,
+                    report) -> None:
+    """--likelihood_to: log p and bits/dim of the images, followed in the JSON by ``report``"""
+    from .solvers import bits_per_dim
+    model.eval()
+    sd2 = [2.0 * float(v) for v in std]         # load_images normalises with x = (pixel - mean) / (2 std)
+    gen = torch.Generator().manual_seed(rank_seed)
+    logp = []
+    for x0, y, img in datamodule.predict_dataloader():
+        y = y if model.conditional else None
+        if dequantize:      # level u read at its centre (load_images) -> uniform over its bin [u, u + 1) / 255
+            u = torch.rand(img.shape, generator=gen, dtype=torch.float32) - 0.5
+            img = img + (u / 255.0 / torch.tensor(sd2, dtype=torch.float32).view(-1, 1, 1)).to(img.device)
+        logp.append(model.solver.log_likelihood(model, img, y, graph=graph, end_step=end_step,
+                                                num_probes=num_probes).cpu())
+    logp = torch.cat(logp) if logp else torch.empty(0, dtype=torch.float64)
+    bpd = bits_per_dim(logp, dims, sd2)
+    _write_json(likelihood_to, {"logp": logp.tolist(), "bpd": bpd.tolist(),
+                                "logp_mean": float(logp.mean()) if logp.numel() else None,
+                                "bpd_mean": float(bpd.mean()) if bpd.numel() else None, **report})
+    print(f"[rank {where[0]}] wrote the likelihoods of images {where[1]} to {likelihood_to}", flush=True)
+
+
+def _max_residual():
+    """DDNM's residual statistic as (add, fields): max |A x - y| and the magnitude it is to be read against"""
+    s = {"consistency": 0.0, "max_abs": 0.0}
+
+    def add(res, out, meas):
+        s["consistency"] = max(s["consistency"], float(res.abs().max()))
+        s["max_abs"] = max(s["max_abs"], float(out.abs().max()), float(meas.abs().max()))
+    return add, lambda: s
+
+
+def _rms_residual(measurement_noise, dps_scale):
+    """DPS's residual statistic as (add, fields): the RMS of A x - y, and the noise level it is to be read against"""
+    s = [0.0, 0]
+
+    def add(res, out, meas):
+        s[:] = s[0] + float((res.double() ** 2).sum()), s[1] + res.numel()
+    return add, lambda: {"measurement_rms": (s[0] / s[1]) ** 0.5 if s[1] else None, "measurement_noise": measurement_noise,
+                         "dps_scale": dps_scale}
+
+
+def _run_restore(model, datamodule, op, solve_kw, noise, rank_seed, back, stat, start_step, writers, mean, std, where,
+                 what, output_dir, restore_report, report) -> None:
+    """restoration by DDNM or DPS: measure each ground-truth image with ``op`` (plus noise * N(0, 1) from rank_seed), solve
+    with ``solve_kw`` from ``back(meas)``, the measurement on the image grid, and write both through ``writers``.
+    ``stat`` = (add, fields) accumulates the residual A x - y; the JSON is fields(), the PSNRs, then ``report``"""
+    add, fields = stat
+    model.eval()
+    gen = torch.Generator().manual_seed(rank_seed)
+    psnr_out, psnr_deg = [], []
+    for bi, (x0, y, img) in enumerate(datamodule.predict_dataloader()):
+        y = y if model.conditional else None
+        meas = op.measure(img)              # the ground truth is used for this and for the report only
+        if noise > 0.0:
+            meas = meas + noise * torch.randn(meas.shape, generator=gen).to(meas.device)
+        deg = back(meas)
+        out = model.solver.solve(model, x0, y, image=deg if start_step > 0 else None, measurement=meas, **solve_kw).float()
+        add(op.measure(out) - meas, out, meas)
+        psnr_out.append(_psnr(out, img, mean, std).cpu())
+        psnr_deg.append(_psnr(deg, img, mean, std).cpu())
+        for w, pred in zip(writers, (out, deg)):
+            w.write_on_batch_end(None, model, pred, None, None, bi, 0)
+    if restore_report is not None:
+        _write_json(restore_report, {**fields(), "psnr_restored": float(torch.cat(psnr_out).mean()) if psnr_out else None,
+                                     "psnr_degraded": float(torch.cat(psnr_deg).mean()) if psnr_deg else None, **report})
+    print(f"[rank {where[0]}] wrote the {what} {where[1]} to {output_dir}", flush=True)
+
+
+def _run_sample(model, datamodule, writer, n_local, where, output_dir, labels_to, labels, num_samples) -> None:
+    """plain sampling through Trainer.predict; ``labels()`` (unless None) gives what --labels_to records"""
+    from .trainer import Trainer
+    trainer = Trainer(accelerator="gpu", strategy="auto", callbacks=[writer])
+    if n_local > 0:
+        trainer.predict(model, datamodule=datamodule, return_predictions=False, ckpt_path=None, distributed=False)   # generate.py:45-47
+    print(f"[rank {where[0]}] wrote images {where[1]} to {output_dir}", flush=True)
+    if labels is not None:
+        _write_json(labels_to, labels())
+        print(f"[rank 0] wrote the labels of images 0..{num_samples - 1} to {labels_to}", flush=True)
 
 
 def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_classes, batch_size, num_workers=16,
@@ -279,24 +394,19 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
              num_probes=1, dequantize=False, restore_scale=1, restore_gray=False, save_degraded=None,
              restore_report=None, labels_to=None, dps_scale=None, blur_std=None, blur_radius=2,
              measurement_noise=0.0) -> None:
+    from . import _runtime_env
     from .callbacks import PreditionWriter
     from .datamodules import RandomNoiseDataModule
     from .edm import EDM
-    from .solvers import DeterministicSolver, MultistepSolver, StochasticSolver
-    from .trainer import Trainer
+    from .solvers import DeterministicSolver, GaussianBlur, LinearDegradation, MultistepSolver, StochasticSolver
 
-    _check_solver(solver, S_churn)
-    _check_conditioning(init_dir, start_step, mask_box, invert_to, solver, S_churn, image_size,
-                        likelihood_to=likelihood_to, network_dtype=network_dtype, num_probes=num_probes,
-                        dequantize=dequantize)
-    posterior = _check_posterior(dps_scale, blur_std, blur_radius, measurement_noise, restore_scale, restore_gray,
-                                 network_dtype, solver, guide is not None or guide_ckpt_path is not None)
-    restoring = _check_restoration(init_dir, restore_scale, restore_gray, save_degraded, restore_report, mask_box,
-                                   invert_to, likelihood_to, image_size, blur=posterior and blur_std is not None)
-    _check_labels_to(labels_to, init_dir)
-    if posterior:
-        graph = False       # a DPS step runs a backward pass: the eager loop
-
+    posterior, restoring = _validate(
+        solver=solver, S_churn=S_churn, init_dir=init_dir, start_step=start_step, num_steps=num_steps, mask_box=mask_box,
+        invert_to=invert_to, likelihood_to=likelihood_to, network_dtype=network_dtype, num_probes=num_probes,
+        dequantize=dequantize, image_size=image_size, dps_scale=dps_scale, blur_std=blur_std, blur_radius=blur_radius,
+        measurement_noise=measurement_noise, restore_scale=restore_scale, restore_gray=restore_gray,
+        save_degraded=save_degraded, restore_report=restore_report, labels_to=labels_to,
+        guided=guide is not None or guide_ckpt_path is not None)
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -319,20 +429,16 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
         guide.denoiser.set_eval_dtype(network_dtype)
         if float(guidance) == 1.0:
             print(f"[rank {rank}] guidance 1.0: the guide network is unused", flush=True)
+    rank_seed = seed + 1000003 * rank
+    common = dict(num_steps=num_steps, guide=guide, guidance=guidance, guidance_interval=guidance_interval, seed=rank_seed)
     if solver == "dpmpp":
-        model.solver = MultistepSolver(num_steps=num_steps, order=solver_order, guide=guide, guidance=guidance,
-                                       guidance_interval=guidance_interval, seed=seed + 1000003 * rank)
+        model.solver = MultistepSolver(order=solver_order, **common)
     elif float(S_churn) != 0.0:     # (a negative or non-finite S_churn reaches the solver's validation)
-        model.solver = StochasticSolver(num_steps=num_steps, guide=guide, guidance=guidance,
-                                        guidance_interval=guidance_interval, S_churn=S_churn, S_min=S_min,
-                                        S_max=S_max, S_noise=S_noise, seed=seed + 1000003 * rank)
+        model.solver = StochasticSolver(S_churn=S_churn, S_min=S_min, S_max=S_max, S_noise=S_noise, **common)
     else:
-        model.solver = DeterministicSolver(num_steps=num_steps, guide=guide, guidance=guidance,
-                                           guidance_interval=guidance_interval, seed=seed + 1000003 * rank)
-    if start_step >= num_steps:
-        raise ValueError(f"generate: --start_step must be below --num_steps = {num_steps}, got {start_step}")
-    from . import _runtime_env
-    graph = bool(graph and _runtime_env.GRAPH_REPLAY_SAFE)      # otherwise the eager loop: same values
+        model.solver = DeterministicSolver(**common)
+    # the eager loop (same values) where a replay is not safe, and for DPS, whose step runs a backward pass
+    graph = bool(graph and not posterior and _runtime_env.GRAPH_REPLAY_SAFE)
     if graph or init_dir is not None:
         solve = model.solver.solve
         extra = {} if init_dir is None else {"start_step": start_step}
@@ -354,135 +460,38 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
             mask = torch.ones(image_size, image_size, dtype=torch.uint8)      # non-zero = known pixel, kept
             mask[y0_:y1_, x0_:x1_] = 0
     datamodule = RandomNoiseDataModule(batch_size, num_workers, image_size, n_local, num_classes, in_channels=C,
-                                       seed=seed + 1000003 * rank, images=images, mask=mask)
+                                       seed=rank_seed, images=images, mask=mask)
+    where = (rank, f"{first}..{first + n_local - 1}")       # for the line each task prints at its end
+    writer = functools.partial(PreditionWriter, write_interval="batch", mean=mean, std=std, first_index=first)
     if invert_to is not None:
-        # the labels of each batch are the ones a solve of the same --seed draws: the saved latents close the loop
-        model.eval()
-        lat, lab = [], []
-        for x0, y, img in datamodule.predict_dataloader():
-            y = y if model.conditional else None
-            lat.append(model.solver.invert(model, img, y, graph=graph, end_step=start_step).cpu())
-            lab.append(None if y is None else y.cpu())
-        if world > 1:
-            root, ext = os.path.splitext(invert_to)
-            invert_to = f"{root}.rank{rank}{ext}"
-        torch.save({"latents": torch.cat(lat) if lat else torch.empty(0), "end_step": start_step, "num_steps": num_steps,
-                    "class_labels": None if not lab or lab[0] is None else torch.cat(lab)}, invert_to)
-        print(f"[rank {rank}] wrote the latents of images {first}..{first + n_local - 1} to {invert_to}", flush=True)
-        return
-    if likelihood_to is not None:
-        import json
-        from .solvers import bits_per_dim
-        model.eval()
-        sd2 = [2.0 * float(v) for v in std]         # load_images normalises with x = (pixel - mean) / (2 std)
-        gen = torch.Generator().manual_seed(seed + 1000003 * rank)
-        logp = []
-        for x0, y, img in datamodule.predict_dataloader():
-            y = y if model.conditional else None
-            if dequantize:      # level u read at its centre (load_images) -> uniform over its bin [u, u + 1) / 255
-                u = torch.rand(img.shape, generator=gen, dtype=torch.float32) - 0.5
-                img = img + (u / 255.0 / torch.tensor(sd2, dtype=torch.float32).view(-1, 1, 1)).to(img.device)
-            logp.append(model.solver.log_likelihood(model, img, y, graph=graph, end_step=start_step,
-                                                    num_probes=num_probes).cpu())
-        logp = torch.cat(logp) if logp else torch.empty(0, dtype=torch.float64)
-        bpd = bits_per_dim(logp, C * image_size * image_size, sd2)
-        if world > 1:
-            root, ext = os.path.splitext(likelihood_to)
-            likelihood_to = f"{root}.rank{rank}{ext}"
-        with open(likelihood_to, "w") as f:
-            json.dump({"logp": logp.tolist(), "bpd": bpd.tolist(),
-                       "logp_mean": float(logp.mean()) if logp.numel() else None,
-                       "bpd_mean": float(bpd.mean()) if bpd.numel() else None, "num_steps": num_steps,
-                       "end_step": start_step, "num_probes": num_probes, "delta": float(model.solver.delta),
-                       "seed": seed, "network_dtype": network_dtype, "dequantize": bool(dequantize),
-                       "first_index": first}, f)
-        print(f"[rank {rank}] wrote the likelihoods of images {first}..{first + n_local - 1} to {likelihood_to}",
-              flush=True)
-        return
-    if restoring and posterior:
-        import json
-        from .solvers import GaussianBlur, LinearDegradation
-        op = GaussianBlur(float(blur_std), int(blur_radius)) if blur_std is not None else \
-            LinearDegradation(restore_scale, bool(restore_gray))
-        writers = [PreditionWriter(output_dir=d, write_interval="batch", mean=mean, std=std, first_index=first)
-                   for d in (output_dir, save_degraded) if d is not None]
-        model.eval()
-        gen = torch.Generator().manual_seed(seed + 1000003 * rank)
-        sq, count, psnr_out, psnr_deg = 0.0, 0, [], []
-        for bi, (x0, y, img) in enumerate(datamodule.predict_dataloader()):
-            y = y if model.conditional else None
-            meas = op.measure(img)              # the ground truth is used for this and for the report only
-            if float(measurement_noise) > 0.0:
-                meas = meas + float(measurement_noise) * torch.randn(meas.shape, generator=gen).to(meas.device)
-            # what --save_degraded shows: the noisy measurement on the image grid (a blur's y is an image already)
-            back = meas if blur_std is not None else op.pinv(meas, C)
-            out = model.solver.solve(model, x0, y, image=back if start_step > 0 else None, operator=op, measurement=meas,
-                                     dps_scale=float(dps_scale)).float()
-            res = op.measure(out) - meas
-            sq, count = sq + float((res.double() ** 2).sum()), count + res.numel()
-            psnr_out.append(_psnr(out, img, mean, std).cpu())
-            psnr_deg.append(_psnr(back, img, mean, std).cpu())
-            for w, pred in zip(writers, (out, back)):
-                w.write_on_batch_end(None, model, pred, None, None, bi, 0)
-        if restore_report is not None:
-            if world > 1:
-                root, ext = os.path.splitext(restore_report)
-                restore_report = f"{root}.rank{rank}{ext}"
-            with open(restore_report, "w") as f:
-                json.dump({"measurement_rms": (sq / count) ** 0.5 if count else None,
-                           "measurement_noise": float(measurement_noise), "dps_scale": float(dps_scale),
-                           "psnr_restored": float(torch.cat(psnr_out).mean()) if psnr_out else None,
-                           "psnr_degraded": float(torch.cat(psnr_deg).mean()) if psnr_deg else None,
-                           "restore_scale": restore_scale, "restore_gray": bool(restore_gray),
-                           "blur_std": None if blur_std is None else float(blur_std),
-                           "blur_radius": None if blur_std is None else int(blur_radius), "num_steps": num_steps,
-                           "start_step": start_step, "seed": seed, "network_dtype": network_dtype,
-                           "first_index": first, "num_images": n_local}, f)
-        print(f"[rank {rank}] wrote the posterior samples {first}..{first + n_local - 1} to {output_dir}", flush=True)
-        return
-    if restoring:
-        import json
-        from .solvers import LinearDegradation
-        deg = LinearDegradation(restore_scale, bool(restore_gray))
-        writers = [PreditionWriter(output_dir=d, write_interval="batch", mean=mean, std=std, first_index=first)
-                   for d in (output_dir, save_degraded) if d is not None]
-        model.eval()
-        resid, peak, psnr_out, psnr_deg = 0.0, 0.0, [], []
-        for bi, (x0, y, img) in enumerate(datamodule.predict_dataloader()):
-            y = y if model.conditional else None
-            meas = deg.measure(img)             # the ground truth is used for this and for the report only
-            back = deg.pinv(meas, C)
-            out = model.solver.solve(model, x0, y, image=back if start_step > 0 else None, degradation=deg,
-                                     measurement=meas).float()
-            resid = max(resid, float((deg.measure(out) - meas).abs().max()))
-            peak = max(peak, float(out.abs().max()), float(meas.abs().max()))
-            psnr_out.append(_psnr(out, img, mean, std).cpu())
-            psnr_deg.append(_psnr(back, img, mean, std).cpu())
-            for w, pred in zip(writers, (out, back)):
-                w.write_on_batch_end(None, model, pred, None, None, bi, 0)
-        if restore_report is not None:
-            if world > 1:
-                root, ext = os.path.splitext(restore_report)
-                restore_report = f"{root}.rank{rank}{ext}"
-            with open(restore_report, "w") as f:
-                json.dump({"consistency": resid, "max_abs": peak,
-                           "psnr_restored": float(torch.cat(psnr_out).mean()) if psnr_out else None,
-                           "psnr_degraded": float(torch.cat(psnr_deg).mean()) if psnr_deg else None,
-                           "restore_scale": restore_scale, "restore_gray": bool(restore_gray), "num_steps": num_steps,
-                           "start_step": start_step, "seed": seed, "network_dtype": network_dtype,
-                           "first_index": first, "num_images": n_local}, f)
-        print(f"[rank {rank}] wrote the restored images {first}..{first + n_local - 1} to {output_dir}", flush=True)
-        return
-    writer = PreditionWriter(output_dir=output_dir, write_interval="batch", mean=mean, std=std, first_index=first)
-    trainer = Trainer(accelerator="gpu", strategy="auto", callbacks=[writer])
-    if n_local > 0:
-        trainer.predict(model, datamodule=datamodule, return_predictions=False, ckpt_path=None, distributed=False)   # generate.py:45-47
-    print(f"[rank {rank}] wrote images {first}..{first + n_local - 1} to {output_dir}", flush=True)
-    if labels_to is not None and rank == 0:
-        import json
-        with open(labels_to, "w") as f:
-            json.dump(_drawn_labels(batch_size, num_workers, image_size, num_samples, num_classes, C, seed, world), f)
-        print(f"[rank 0] wrote the labels of images 0..{num_samples - 1} to {labels_to}", flush=True)
+        _run_invert(model, datamodule, _rank_path(invert_to, rank, world), graph, start_step, num_steps, where)
+    elif likelihood_to is not None:
+        _run_likelihood(model, datamodule, _rank_path(likelihood_to, rank, world), graph, start_step, num_probes,
+                        dequantize, rank_seed, std, C * image_size * image_size, where,
+                        {"num_steps": num_steps, "end_step": start_step, "num_probes": num_probes,
+                         "delta": float(model.solver.delta), "seed": seed, "network_dtype": network_dtype,
+                         "dequantize": bool(dequantize), "first_index": first})
+    elif restoring:
+        blur = blur_std is not None
+        op = GaussianBlur(float(blur_std), int(blur_radius)) if blur else LinearDegradation(restore_scale, bool(restore_gray))
+        if posterior:
+            what, solve_kw = "posterior samples", {"operator": op, "dps_scale": float(dps_scale)}
+            stat = _rms_residual(float(measurement_noise), float(dps_scale))
+            blur_fields = {"blur_std": float(blur_std) if blur else None, "blur_radius": int(blur_radius) if blur else None}
+        else:
+            what, solve_kw, stat, blur_fields = "restored images", {"degradation": op}, _max_residual(), {}
+        # back, what --save_degraded shows: the measurement on the image grid (a blur's y is an image already)
+        _run_restore(model, datamodule, op, solve_kw, float(measurement_noise), rank_seed,
+                     (lambda meas: meas) if blur else (lambda meas: op.pinv(meas, C)), stat, start_step,
+                     [writer(d) for d in (output_dir, save_degraded) if d is not None], mean, std, where, what, output_dir,
+                     None if restore_report is None else _rank_path(restore_report, rank, world),
+                     {"restore_scale": restore_scale, "restore_gray": bool(restore_gray), **blur_fields, "num_steps": num_steps,
+                      "start_step": start_step, "seed": seed, "network_dtype": network_dtype, "first_index": first,
+                      "num_images": n_local})
+    else:
+        labels = None if labels_to is None or rank != 0 else functools.partial(
+            _drawn_labels, batch_size, num_workers, image_size, num_samples, num_classes, C, seed, world)
+        _run_sample(model, datamodule, writer(output_dir), n_local, where, output_dir, labels_to, labels, num_samples)
 
 
 def main(argv=None):
@@ -574,20 +583,11 @@ def main(argv=None):
                         help="write the class indices the samples were drawn for, in index order (the format "
                              "--labels_json of tinyedm.classify reads); class-conditional checkpoints, not with --init_dir")
     args = parser.parse_args(argv)
-    _check_solver(args.solver, args.S_churn)
+    _check_solver(args.solver, args.S_churn)        # a ValueError, not a usage error: raised before _validate meets it
     try:
-        _check_labels_to(args.labels_to, args.init_dir)
-        guided = (args.guide_ckpt_path is not None or args.guide_config_name is not None or args.guide_unconditional)
-        posterior = _check_posterior(args.dps_scale, args.blur_std, args.blur_radius, args.measurement_noise,
-                                     args.restore_scale, args.restore_gray, args.network_dtype, args.solver, guided)
-        _check_restoration(args.init_dir, args.restore_scale, args.restore_gray, args.save_degraded,
-                           args.restore_report, args.mask_box, args.invert_to, args.likelihood_to, args.image_size,
-                           blur=posterior and args.blur_std is not None)
-        _check_conditioning(args.init_dir, args.start_step, args.mask_box, args.invert_to, args.solver, args.S_churn,
-                            args.image_size, likelihood_to=args.likelihood_to, network_dtype=args.network_dtype,
-                            num_probes=args.num_probes, dequantize=args.dequantize)
-        if args.start_step >= args.num_steps:
-            raise ValueError(f"generate: --start_step must be below --num_steps = {args.num_steps}, got {args.start_step}")
+        # every option of _validate is a flag of the same name, but for the guide, which has three
+        _validate(guided=args.guide_ckpt_path is not None or args.guide_config_name is not None or args.guide_unconditional,
+                  **{k: getattr(args, k) for k in inspect.signature(_validate).parameters if k != "guided"})
     except ValueError as e:
         parser.error(str(e))
     if args.guide_ckpt_path is not None and args.guide_config_name is not None:

@@ -72,17 +72,17 @@ def duplicates(dist, idx, max_d2: int) -> list:
 
 
 # ---------------------------------------------------------------------------------------------------- images
-def load_images_u8(image_dir, image_size=None, channels=None) -> np.ndarray:
-    """the <index>.png files of a directory (as generate writes them) as raw uint8 [n, C, H, W] in numeric index order.
-    image_size: an int for square images or (H, W); image_size / channels None: taken from the first image.  Every image
-    must agree."""
+def read_png_dir(image_dir, who, where, image_size=None, channels=None) -> list:
+    """the <index>.png files of a directory (as generate writes them) as uint8 [H, W, C] arrays in numeric index order.
+    who / where: the caller's name and its name for the directory, for the messages.  image_size: an int for square
+    images or (H, W); image_size / channels None: taken from the first image.  Every image must agree."""
     from PIL import Image
     names = [f for f in os.listdir(image_dir) if f.lower().endswith(".png")]
     bad = [f for f in names if not os.path.splitext(f)[0].isdigit()]
     if bad:
-        raise ValueError(f"neighbors: {image_dir} holds PNGs that are not named <index>.png: {sorted(bad)[:3]}")
+        raise ValueError(f"{who}: {where} holds PNGs that are not named <index>.png: {sorted(bad)[:3]}")
     if not names:
-        raise ValueError(f"neighbors: no PNG in {image_dir}")
+        raise ValueError(f"{who}: no PNG in {image_dir}")
     out, want = [], None
     for f in sorted(names, key=lambda f: int(os.path.splitext(f)[0])):
         a = np.asarray(Image.open(os.path.join(image_dir, f)))
@@ -91,9 +91,15 @@ def load_images_u8(image_dir, image_size=None, channels=None) -> np.ndarray:
             hw = (image_size, image_size) if isinstance(image_size, int) else tuple(image_size or a.shape[:2])
             want = (int(hw[0]), int(hw[1]), channels or a.shape[2])
         if a.dtype != np.uint8 or a.shape != want:
-            raise ValueError(f"neighbors: {f} is {a.dtype} {a.shape}, expected uint8 {want}")
-        out.append(np.ascontiguousarray(a.transpose(2, 0, 1)))
-    return np.stack(out)
+            raise ValueError(f"{who}: {f} is {a.dtype} {a.shape}, expected uint8 {want}")
+        out.append(a)
+    return out
+
+
+def load_images_u8(image_dir, image_size=None, channels=None) -> np.ndarray:
+    """read_png_dir as raw uint8 [n, C, H, W]"""
+    return np.stack([np.ascontiguousarray(a.transpose(2, 0, 1))
+                     for a in read_png_dir(image_dir, "neighbors", image_dir, image_size, channels)])
 
 
 # ---------------------------------------------------------------------------------------------------- the search

@@ -218,6 +218,19 @@ class _Restoration(NamedTuple):
         return ops.project_denoised(D, self.y, self.scale, self.gray, Dg, None if Dg is None else w_dev)
 
 
+def _check_measurement(x0, op, measurement) -> None:
+    """the measurement y of a solve against x0 and its operator, on the host (nothing is read from a device)"""
+    _check_float("solve", "measurement", measurement)
+    if x0.dim() != 4:
+        raise ValueError(f"solve: a measurement needs x0 of shape [B, C, H, W], got {tuple(x0.shape)}")
+    shape = op.measurement_shape(x0.shape)
+    if tuple(measurement.shape) != shape:
+        raise ValueError(f"solve: measurement must have shape {shape} for x0 {tuple(x0.shape)} under {op}, got "
+                         f"{tuple(measurement.shape)}")
+    if measurement.device != x0.device:
+        raise ValueError(f"solve: measurement is on {measurement.device}, x0 on {x0.device}")
+
+
 def _mask_u8(mask, shape):
     """a bool / uint8 / float mask of shape [B,1,H,W], [1,1,H,W] or [H,W] as uint8 [B or 1, H*W] (non-zero = known)"""
     B, _, H, W = shape
@@ -385,15 +398,7 @@ class DeterministicSolver:
         if mask is not None:
             raise ValueError("solve: mask (inpainting by replacement) and measurement (restoration) are two "
                              "conditionings; their combination is not implemented")
-        _check_float("solve", "measurement", measurement)
-        if x0.dim() != 4:
-            raise ValueError(f"solve: a measurement needs x0 of shape [B, C, H, W], got {tuple(x0.shape)}")
-        shape = degradation.measurement_shape(x0.shape)
-        if tuple(measurement.shape) != shape:
-            raise ValueError(f"solve: measurement must have shape {shape} for x0 {tuple(x0.shape)} under "
-                             f"{degradation}, got {tuple(measurement.shape)}")
-        if measurement.device != x0.device:
-            raise ValueError(f"solve: measurement is on {measurement.device}, x0 on {x0.device}")
+        _check_measurement(x0, degradation, measurement)
         return degradation, measurement
 
     # ------------------------------------------------------------------ subclass hooks (StochasticSolver)
@@ -494,15 +499,7 @@ class DeterministicSolver:
         scale = 1.0 if dps_scale is None else dps_scale
         if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not math.isfinite(scale) or scale < 0:
             raise ValueError(f"solve: dps_scale must be a finite number >= 0, got {dps_scale!r}")
-        _check_float("solve", "measurement", measurement)
-        if x0.dim() != 4:
-            raise ValueError(f"solve: a measurement needs x0 of shape [B, C, H, W], got {tuple(x0.shape)}")
-        shape = operator.measurement_shape(x0.shape)
-        if tuple(measurement.shape) != shape:
-            raise ValueError(f"solve: measurement must have shape {shape} for x0 {tuple(x0.shape)} under {operator}, got "
-                             f"{tuple(measurement.shape)}")
-        if measurement.device != x0.device:
-            raise ValueError(f"solve: measurement is on {measurement.device}, x0 on {x0.device}")
+        _check_measurement(x0, operator, measurement)
         from . import vjp
         parts = vjp._library_parts(model)
         if parts is not None and parts[1].eval_dtype != "bf16":
