@@ -167,6 +167,21 @@ long edm_wgrad3_table_bytes(void);
 int edm_wgrad3_max_layers(void);
 int edm_wgrad3_group(const edm_wgrad3_item* items, int n, void* workspace, long workspace_bytes, void* table_host,
                      void* table_dev, int defer_upload, edm_stream_t stream);
+/* apply form: the finish launch runs edm_adam_ema's update (g = projected gradient * grad_scale) on the weight rows it
+ * holds instead of writing their gradient -- w, m, v and ema rows are rewritten, `grad` is not touched for them.  opt[k]:
+ * the m / v / ema (nullable) tensors of layer k, laid out like its w; dyn: the DEVICE edm_step_params record, required: lr,
+ * ema_beta, grad_scale and the bias corrections are read at run time; health: as edm_adam_ema.  A layer whose rows (I * 9 floats)
+ * exceed the kernel's register prefetch (7168) keeps the plain finish into `grad`.  fused_out (HOST, n ints): 1 = layer k
+ * was updated here, 0 = its gradient is in `grad`.  The launch table takes edm_wgrad3_apply_table_bytes(). */
+typedef struct {
+  float* m;
+  float* v;
+  float* ema;
+} edm_wgrad3_opt;
+long edm_wgrad3_apply_table_bytes(void);
+int edm_wgrad3_group_apply(const edm_wgrad3_item* items, int n, void* workspace, long workspace_bytes, void* table_host,
+                           void* table_dev, int defer_upload, const edm_wgrad3_opt* opt, const void* dyn, float b1,
+                           float b2, float eps, unsigned* health, int* fused_out, edm_stream_t stream);
 
 /* ---------------------------------------------------------------- weights (networks.py:17-19, 32-36, 55-59) */
 /* forced weight normalisation (in place when normalize_inplace) + effective weight w/(eps+|w|/sqrt(n))/sqrt(n),
@@ -494,6 +509,14 @@ int edm_weighted_mse(const float* D, const float* clean, const float* sigma, con
 int edm_adam_ema(float* theta, float* grad, float* m, float* v, float* ema, long n, float lr, float b1, float b2,
                  float eps, int step, float ema_beta, float grad_scale, const void* dyn, int zero_grad,
                  unsigned* health, edm_stream_t stream);
+/* edm_adam_ema over a set of element ranges of the arenas only; elements outside them are neither read nor written.
+ * ranges: DEVICE array of n_ranges (first element, length) pairs of longs; chunks: DEVICE array of n_chunks (range id,
+ * offset inside the range) pairs of ints, one per 1024 elements of a range.  Both stay valid and unchanged until the
+ * launch has executed (captured stream: for the life of the graph).  n_chunks == 0 launches nothing. */
+int edm_adam_ema_ranges(float* theta, float* grad, float* m, float* v, float* ema, long n, const long* ranges,
+                        int n_ranges, const int* chunks, int n_chunks, float lr, float b1, float b2, float eps, int step,
+                        float ema_beta, float grad_scale, const void* dyn, int zero_grad, unsigned* health,
+                        edm_stream_t stream);
 /* post-hoc EMA (Karras et al. 2024, Sec. 3): edm_adam_ema plus K = 1..4 profile arenas of n floats, updated from the new
  * weights in the same pass, p_k = beta_k * p_k + (1 - beta_k) * theta_new.  theta / m / v / ema are bitwise those of
  * edm_adam_ema.  profiles: HOST array of K device pointers (16-byte aligned); betas: DEVICE array of K floats read at

@@ -95,6 +95,8 @@ SIGNATURES = {
     "edm_wgrad3_group": [P, I, P, L, P, P, I, P],
     "edm_wgrad3_table_bytes": [],
     "edm_wgrad3_max_layers": [],
+    "edm_wgrad3_group_apply": [P, I, P, L, P, P, I, P, P, F, F, F, P, P, P],
+    "edm_wgrad3_apply_table_bytes": [],
     # attention.hip
     "edm_attention_fwd": [P, P, I, I, I, I, P],
     "edm_attention_bwd": [P, P, P, P, I, I, I, I, P],
@@ -122,6 +124,7 @@ SIGNATURES = {
     "edm_weighted_mse": [P, P, P, P, F, P, P, I, L, P, P, P],
     "edm_adam_ema": [P, P, P, P, P, L, F, F, F, F, I, F, F, P, I, P, P],
     "edm_adam_ema_phema": [P, P, P, P, P, P, I, P, L, F, F, F, F, I, F, F, P, I, P, P],
+    "edm_adam_ema_ranges": [P, P, P, P, P, L, P, I, P, I, F, F, F, F, I, F, F, P, I, P, P],
     "edm_phema_accumulate": [P, P, P, I, L, P],
     "edm_phema_finish": [P, P, L, P],
     "edm_heun_euler": [P, P, F, F, P, P, L, P, P],
@@ -200,9 +203,11 @@ DIAG_SIGNATURES = {
     "edm_v6_persistent_launches": [],
 }
 _RET = {"edm_last_error": ctypes.c_char_p, "edm_lowrank_wgrad_workspace": ctypes.c_long, "edm_v6_persistent_launches": ctypes.c_long, "edm_wgrad3_workspace": ctypes.c_long, "edm_wgrad3_table_bytes": ctypes.c_long,
+        "edm_wgrad3_apply_table_bytes": ctypes.c_long,
         "edm_skip_gate_wgrad_multi_table_bytes": ctypes.c_long, "edm_skip_gate_fwd_multi_table_bytes": ctypes.c_long, "edm_skip_gate_bwd_multi_table_bytes": ctypes.c_long,
         "edm_conv_wgrad_1x1_group_table_bytes": ctypes.c_long, "edm_wgrad_finish_multi_table_bytes": ctypes.c_long}
 _NO_STATUS = {"edm_lowrank_wgrad_workspace", "edm_lowrank_supported", "edm_lowrank_tail_supported", "edm_lowrank_tail_dwout_supported", "edm_lowrank_gcat_supported", "edm_skip_gate_bwd_multi_table_bytes", "edm_skip_gate_fwd_multi_table_bytes", "edm_v6_persistent_launches", "edm_conv3x3_fold_supported", "edm_conv_plan", "edm_skip_gate_wgrad_multi_table_bytes", "edm_version", "edm_graph_replay_safe", "edm_last_error", "edm_conv_wgrad_nsplit", "edm_conv_wgrad_1x1_nsplit", "edm_conv_wgrad_1x1_nsplit_grouped", "edm_wgrad3_workspace", "edm_wgrad3_table_bytes", "edm_wgrad3_max_layers",
+              "edm_wgrad3_apply_table_bytes",
               "edm_conv_wgrad_1x1_group_table_bytes", "edm_wgrad_finish_multi_table_bytes", "edm_attention_qkv_supported",
               "edm_attention_long_supported", "edm_conv_in_dgrad_pack_cols",
               "edm_u8_knn_splits"}
@@ -251,6 +256,11 @@ class WGrad3Item(ctypes.Structure):
     """edm_wgrad3_item (include/tinyedm_hip.h): one 3x3 layer of a grouped weight-gradient launch."""
     _fields_ = [("X", P), ("dY", P), ("w", P), ("grad", P), ("perm", P), ("B", I), ("H", I), ("W", I), ("Cin", I),
                 ("Cout", I), ("I", I), ("scale", F), ("accumulate", I)]
+
+
+class WGrad3Opt(ctypes.Structure):
+    """edm_wgrad3_opt (include/tinyedm_hip.h): the optimizer rows of one layer of edm_wgrad3_group_apply."""
+    _fields_ = [("m", P), ("v", P), ("ema", P)]
 
 
 def lib() -> ctypes.CDLL:

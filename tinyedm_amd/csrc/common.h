@@ -189,6 +189,26 @@ struct StepParams {  // mirrored by include/tinyedm_hip.h (edm_step_params) and 
   uint32_t step, seed_lo, seed_hi, reserved;
   float lr, ema_beta, grad_scale, bc1, bc2sqrt, pad[3];
 };
+// Adam + EMA update of ONE element, shared by every kernel that applies it (optim.hip k_adam_ema and its ranges form,
+// conv_wgrad3.hip k_wgrad3_finish<true>): g is the raw gradient (grad_scale is applied here), step_size = lr / bc1;
+// t, m, v and e (the EMA, only when has_ema) are updated in place.  Returns true when the gradient or the new weight is
+// not finite (health bit 0).  Two kernels may contract b*x + (1-b)*y into an FMA differently: results agree to the last
+// bit or two, not bitwise (see k_adam_ema_phema).
+struct AdamArgs {
+  float lr, b1, b2, eps, bc1, bc2sqrt, ema_beta, grad_scale;
+};
+__device__ __forceinline__ void adam_args_from(AdamArgs& a, const StepParams* __restrict__ dyn) {
+  a.lr = dyn->lr; a.ema_beta = dyn->ema_beta; a.grad_scale = dyn->grad_scale; a.bc1 = dyn->bc1; a.bc2sqrt = dyn->bc2sqrt;
+}
+__device__ __forceinline__ bool adam_ema_update(float& t, float g, float& m, float& v, float& e, bool has_ema,
+                                                const AdamArgs& a, float step_size) {
+  const float gj = g * a.grad_scale;
+  m = a.b1 * m + (1.f - a.b1) * gj;
+  v = a.b2 * v + (1.f - a.b2) * gj * gj;
+  t -= step_size * m / (sqrtf(v) / a.bc2sqrt + a.eps);
+  if (has_ema) e = a.ema_beta * e + (1.f - a.ema_beta) * t;
+  return !(fabsf(gj) <= 3.0e38f) || !(fabsf(t) <= 3.0e38f);
+}
 struct ModEpilogue {
   const float* lin;   // [B][lin_stride] fp32 embed-linear output
   const float* gain;  // device scalar

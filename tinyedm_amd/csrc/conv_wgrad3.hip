@@ -474,6 +474,18 @@ struct F3Group {
   long q;
   const float* work;
 };
+// The apply form's extra table, right behind F3Group in the launch table: the optimizer rows of every layer (laid out like
+// its w) and what k_adam_ema takes by value or from `dyn`.
+struct F3Apply {
+  float* m[MAXL];
+  float* v[MAXL];
+  float* ema[MAXL];   // nullptr: no EMA
+  const StepParams* dyn;
+  unsigned* health;
+  float b1, b2, eps;
+  int pad;
+};
+constexpr int F3_WPF = 28;   // register prefetch of the finish: rows of n <= F3_WPF * 256 floats (Cin <= 796)
 
 __device__ __forceinline__ float block_sum_f(float v, float* red) {
   v = wave_sum(v);
@@ -486,6 +498,15 @@ __device__ __forceinline__ float block_sum_f(float v, float* red) {
   return s;
 }
 
+// APPLY: a row that fits the register prefetch is not written to the gradient arena; the workgroup holds its master row
+// (wpre) and its projected gradient (gsm) and runs the optimizer's update on it (common.h adam_ema_update, g = v *
+// grad_scale): theta, m, v and ema of the row are rewritten.  The arena's gradient row is neither read nor written (it is
+// all zero and stays so).  Longer rows take the unfused path below in either form.
+// m, v and ema are loaded where they are used, after the block sums: prefetched beside the master row they cost 180-252
+// VGPRs (two workgroups per CU) and the three launches of the CIFAR-10 step took 0.336 ms instead of 0.231 ms.
+// WPF: the register prefetch of the master row in elements per thread; the apply launch takes the smallest of 10 / 19 / 28
+// that covers the group's longest fused row (52 / 70 / 88 VGPRs).
+template <bool APPLY, int WPF = F3_WPF>
 __global__ __launch_bounds__(256) void k_wgrad3_finish(const F3Group* __restrict__ gp) {
   const F3Group& g = *gp;
   extern __shared__ __attribute__((aligned(16))) float gsm[];  // [n] gradient row in master order (i*9 + t)
@@ -508,7 +529,7 @@ __global__ __launch_bounds__(256) void k_wgrad3_finish(const F3Group* __restrict
   const float scale = g.L[li].scale;
   // the row of the master weight (projection below): loaded NOW, while the partial tiles are in flight -- the kernel is a
   // chain of memory round trips per workgroup (partials -> row -> block sums -> store) and this takes one of them out
-  constexpr int WPF = 28;                       // covers n <= 7168 (Cin <= 796) with 256 threads; longer rows load late
+  // F3_WPF covers n <= 7168 (Cin <= 796) with 256 threads; longer rows load late
   const bool pf = n <= WPF * 256;
   float wpre[WPF];
   if (pf) {
@@ -518,6 +539,7 @@ __global__ __launch_bounds__(256) void k_wgrad3_finish(const F3Group* __restrict
       wpre[k] = e < n ? row[e] : 0.f;
     }
   }
+  const F3Apply* const ap = APPLY ? reinterpret_cast<const F3Apply*>(gp + 1) : nullptr;
   // work items: (ci tile, tap, float4 of the 64 ci) -> 16 per (tile, tap)
   const int items = tiles_ci * 9 * 16;
   for (int idx = threadIdx.x; idx < items; idx += blockDim.x) {
@@ -576,6 +598,32 @@ __global__ __launch_bounds__(256) void k_wgrad3_finish(const F3Group* __restrict
   const float d = NORM_EPS + rn / sqn;
   const float c0 = 1.0f / (d * sqn);
   const float c1 = rn > 0.f ? dot / (d * rn * sqn) : 0.f;
+  if (APPLY && pf) {
+    AdamArgs a;
+    adam_args_from(a, ap->dyn);
+    a.b1 = ap->b1; a.b2 = ap->b2; a.eps = ap->eps;
+    const float step_size = a.lr / a.bc1;
+    float* const wr = const_cast<float*>(g.L[li].w) + (long)mo * n;   // (every read of the row is above: wpre)
+    float* const mr = ap->m[li] + (long)mo * n;
+    float* const vr = ap->v[li] + (long)mo * n;
+    float* const er = ap->ema[li] ? ap->ema[li] + (long)mo * n : nullptr;
+    bool bad = false;
+#pragma unroll
+    for (int k = 0; k < WPF; ++k) {
+      const int e = threadIdx.x + k * 256;
+      if (e < n) {
+        const float v = c0 * (gsm[e] - wpre[k] * c1);
+        float tj = wpre[k], mj = mr[e], vj = vr[e], ej = er ? er[e] : 0.f;
+        bad |= adam_ema_update(tj, v, mj, vj, ej, er != nullptr, a, step_size);
+        wr[e] = tj;
+        mr[e] = mj;
+        vr[e] = vj;
+        if (er) er[e] = ej;
+      }
+    }
+    if (ap->health && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(ap->health, 1u);
+    return;
+  }
   float* __restrict__ outp = g.L[li].grad + (long)mo * n;
   const int accumulate = g.L[li].accumulate;
   if (pf) {
@@ -743,6 +791,7 @@ extern "C" int edm_wgrad3_plan_ksplit(const edm_wgrad3_item* items, int n, int* 
 // Weight gradients of up to 48 3x3 layers (edm_wgrad3_max_layers): one stream-K launch + one finish launch.  `items` is HOST memory (read
 // during the call only); workspace is device memory of at least edm_wgrad3_workspace(items, n) bytes.
 extern "C" long edm_wgrad3_table_bytes(void) { return (long)(sizeof(W3Group) + sizeof(F3Group)); }
+extern "C" long edm_wgrad3_apply_table_bytes(void) { return (long)(sizeof(W3Group) + sizeof(F3Group) + sizeof(F3Apply)); }
 extern "C" int edm_wgrad3_max_layers(void) { return MAXL; }
 
 // Measurement hook (bench.py's roofline leg; include/tinyedm_hip_diag.h): the NEXT edm_wgrad3_group call of this thread
@@ -756,8 +805,18 @@ extern "C" int edm_wgrad3_probe(void* ev_start, void* ev_end) {
   return EDM_OK;
 }
 
-extern "C" int edm_wgrad3_group(const edm_wgrad3_item* items, int n, void* workspace, long workspace_bytes,
-                                void* table_host, void* table_dev, int defer_upload, hipStream_t st) {
+// One layer's optimizer rows for edm_wgrad3_group_apply (plain C struct, mirrored by tinyedm_amd/_lib.py).
+extern "C" {
+typedef struct {
+  float* m;
+  float* v;
+  float* ema;
+} edm_wgrad3_opt;
+}
+
+// ap == nullptr: edm_wgrad3_group; else its apply form (ap's per-layer rows filled by the caller)
+static int wgrad3_group_run(const edm_wgrad3_item* items, int n, void* workspace, long workspace_bytes, void* table_host,
+                            void* table_dev, int defer_upload, const F3Apply* ap, hipStream_t st) {
   Plan P;
   const int rc = make_plan(items, n, P);
   if (rc != EDM_OK) return rc;
@@ -770,11 +829,13 @@ extern "C" int edm_wgrad3_group(const edm_wgrad3_item* items, int n, void* works
   P.fg.work = (const float*)workspace;
   // the two layer tables go to device memory with ONE stream-ordered copy (common.h: EDM_UPLOAD_TABLE)
   static_assert(sizeof(W3Group) % 16 == 0, "F3Group must start aligned behind W3Group");
+  static_assert(sizeof(F3Group) % 8 == 0, "F3Apply must start aligned behind F3Group");
   {
-    char stage[sizeof(W3Group) + sizeof(F3Group)];
+    char stage[sizeof(W3Group) + sizeof(F3Group) + sizeof(F3Apply)];
     memcpy(stage, &P.wg, sizeof(W3Group));
     memcpy(stage + sizeof(W3Group), &P.fg, sizeof(F3Group));
-    EDM_UPLOAD_TABLE(table_dev, table_host, stage, sizeof(stage), st, "wgrad3", defer_upload);
+    if (ap) memcpy(stage + sizeof(W3Group) + sizeof(F3Group), ap, sizeof(F3Apply));
+    EDM_UPLOAD_TABLE(table_dev, table_host, stage, sizeof(stage) - (ap ? 0 : sizeof(F3Apply)), st, "wgrad3", defer_upload);
   }
   const W3Group* const wgp = (const W3Group*)table_dev;
   const F3Group* const fgp = (const F3Group*)((const char*)table_dev + sizeof(W3Group));
@@ -816,8 +877,51 @@ extern "C" int edm_wgrad3_group(const edm_wgrad3_item* items, int n, void* works
   if (g_probe_end) (void)hipEventRecord(g_probe_end, st);
   g_probe_start = g_probe_end = nullptr;
   EDM_CHECK_LAUNCH("wgrad3");
-  EDM_MAX_LDS(k_wgrad3_finish, 64 * 1024);
-  hipLaunchKernelGGL(k_wgrad3_finish, dim3(P.rows_total), dim3(256), (size_t)P.max_n * 4, st, fgp);
+  if (ap) {
+    // the longest row the apply form updates (longer ones take the unfused path in every instantiation)
+    int fused_n = 0;
+    for (int k = 0; k < n; ++k)
+      if (items[k].I * 9 <= F3_WPF * 256 && items[k].I * 9 > fused_n) fused_n = items[k].I * 9;
+    auto go = [&](auto kern) {
+      EDM_MAX_LDS(kern, 64 * 1024);
+      hipLaunchKernelGGL(kern, dim3(P.rows_total), dim3(256), (size_t)P.max_n * 4, st, fgp);
+    };
+    if (fused_n <= 10 * 256) go(k_wgrad3_finish<true, 10>);         // Cin <= 284: the 256-channel layers
+    else if (fused_n <= 19 * 256) go(k_wgrad3_finish<true, 19>);    // Cin <= 540: their 512-channel concatenations
+    else go(k_wgrad3_finish<true, F3_WPF>);
+  } else {
+    EDM_MAX_LDS(k_wgrad3_finish<false>, 64 * 1024);
+    hipLaunchKernelGGL(k_wgrad3_finish<false>, dim3(P.rows_total), dim3(256), (size_t)P.max_n * 4, st, fgp);
+  }
   EDM_CHECK_LAUNCH("wgrad3_finish");
+  return EDM_OK;
+}
+
+extern "C" int edm_wgrad3_group(const edm_wgrad3_item* items, int n, void* workspace, long workspace_bytes,
+                                void* table_host, void* table_dev, int defer_upload, hipStream_t st) {
+  return wgrad3_group_run(items, n, workspace, workspace_bytes, table_host, table_dev, defer_upload, nullptr, st);
+}
+
+// edm_wgrad3_group whose finish applies the Adam + EMA update to the rows it holds (k_wgrad3_finish<true>).  opt: HOST array
+// of n records (the m / v / ema tensors of each layer, laid out like its w; ema nullable); dyn: DEVICE StepParams (required);
+// fused_out: HOST array of n ints, 1 = the layer was updated here, 0 = its rows exceed the register prefetch and its
+// gradient went to items[k].grad as in edm_wgrad3_group.  table_host / table_dev: edm_wgrad3_apply_table_bytes().
+extern "C" int edm_wgrad3_group_apply(const edm_wgrad3_item* items, int n, void* workspace, long workspace_bytes,
+                                      void* table_host, void* table_dev, int defer_upload, const edm_wgrad3_opt* opt,
+                                      const void* dyn, float b1, float b2, float eps, unsigned* health, int* fused_out,
+                                      hipStream_t st) {
+  EDM_REQUIRE(items && n > 0 && n <= MAXL && opt && dyn && fused_out, "wgrad3_apply: null argument or %d layers", n);
+  F3Apply ap;
+  memset(&ap, 0, sizeof(ap));
+  for (int k = 0; k < n; ++k) {
+    EDM_REQUIRE(opt[k].m && opt[k].v, "wgrad3_apply: layer %d has no m / v rows", k);
+    ap.m[k] = opt[k].m; ap.v[k] = opt[k].v; ap.ema[k] = opt[k].ema;
+  }
+  ap.dyn = (const StepParams*)dyn;
+  ap.health = health;
+  ap.b1 = b1; ap.b2 = b2; ap.eps = eps;
+  const int rc = wgrad3_group_run(items, n, workspace, workspace_bytes, table_host, table_dev, defer_upload, &ap, st);
+  if (rc != EDM_OK) return rc;
+  for (int k = 0; k < n; ++k) fused_out[k] = items[k].I * 9 <= F3_WPF * 256;
   return EDM_OK;
 }

@@ -92,9 +92,10 @@ __global__ void k_loss(const float* __restrict__ Dn, const float* __restrict__ c
   }
 }
 
-struct AdamArgs {
-  float lr, b1, b2, eps, bc1, bc2sqrt, ema_beta, grad_scale;
-};
+// (struct AdamArgs and the per-element update adam_ema_update: common.h, shared with conv_wgrad3.hip)
+// k_adam_ema keeps its own text of the update below (the same expressions as adam_ema_update): written over the shared
+// function the compiler packs one more multiply-add pair of the quad into v_pk_fma_f32, which moves last bits against
+// k_adam_ema_phema (the bitwise comparison of tests/test_posthoc_ema_gpu.py) and against every earlier result of this kernel.
 // fused multi-tensor Adam + EMA over the flat arenas: 5 streams read, 4 written, one pass
 // zero_grad: the gradient arena is cleared in the same pass (saves the separate fill of optimizer.zero_grad()).
 __global__ void k_adam_ema(float* __restrict__ theta, float* __restrict__ grad, float* __restrict__ m,
@@ -140,6 +141,70 @@ __global__ void k_adam_ema(float* __restrict__ theta, float* __restrict__ grad, 
       }
     }
   }
+  if (health && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(health, 1u);
+}
+
+// The same pass over a SET OF RANGES of the arenas (the rest of the arena when the 3x3 weight-gradient finish has updated its
+// rows itself: conv_wgrad3.hip k_wgrad3_finish<true>).  Driven by a device table, as k_weight_prep_multi is by `groups`:
+// ranges[r] = (first element, length), chunks[c] = (range id, offset inside the range); workgroup c takes up to ADAM_CHUNK
+// elements from there: the elements up to the first 16-byte boundary and behind the last one singly, the quads between as
+// dwordx4.  Elements outside the ranges are neither read nor written; a chunk that would leave [0, n) is skipped whole.
+constexpr int ADAM_CHUNK = 1024;        // = ops.ADAM_RANGE_CHUNK: 256 threads x one quad
+struct AdamRange {
+  long start, len;
+};
+__global__ __launch_bounds__(256) void k_adam_ema_ranges(float* __restrict__ theta, float* __restrict__ grad,
+                                                         float* __restrict__ m, float* __restrict__ v,
+                                                         float* __restrict__ ema, long n,
+                                                         const AdamRange* __restrict__ ranges, int n_ranges,
+                                                         const int2* __restrict__ chunks, AdamArgs a,
+                                                         const StepParams* __restrict__ dyn, int zero_grad,
+                                                         unsigned* __restrict__ health) {
+  if (dyn) adam_args_from(a, dyn);
+  const float step_size = a.lr / a.bc1;
+  const int2 c = chunks[blockIdx.x];
+  if (c.x < 0 || c.x >= n_ranges || c.y < 0) return;
+  const AdamRange r = ranges[c.x];
+  const long first = r.start + c.y;
+  const long left = r.len - c.y;
+  const int cnt = (int)(left < ADAM_CHUNK ? left : ADAM_CHUNK);
+  if (r.start < 0 || cnt <= 0 || first + cnt > n) return;
+  const int head = (int)((4 - (first & 3)) & 3) < cnt ? (int)((4 - (first & 3)) & 3) : cnt;   // singles before the first quad
+  const int nq = (cnt - head) >> 2;
+  bool bad = false;
+  auto single = [&](long e) {
+    float tj = theta[e], mj = m[e], vj = v[e], ej = ema ? ema[e] : 0.f;
+    bad |= adam_ema_update(tj, grad[e], mj, vj, ej, ema != nullptr, a, step_size);
+    m[e] = mj;
+    v[e] = vj;
+    theta[e] = tj;
+    if (zero_grad) grad[e] = 0.f;
+    if (ema) ema[e] = ej;
+  };
+  if ((int)threadIdx.x < nq) {
+    const long i = first + head + 4 * (long)threadIdx.x;
+    f32x4 t = *reinterpret_cast<f32x4*>(theta + i);
+    f32x4 g = *reinterpret_cast<const f32x4*>(grad + i);
+    if (zero_grad) *reinterpret_cast<f32x4*>(grad + i) = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 mm = *reinterpret_cast<f32x4*>(m + i);
+    f32x4 vv = *reinterpret_cast<f32x4*>(v + i);
+    f32x4 ee = {0.f, 0.f, 0.f, 0.f};
+    if (ema) ee = *reinterpret_cast<f32x4*>(ema + i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float tj = t[j], mj = mm[j], vj = vv[j], ej = ee[j];
+      bad |= adam_ema_update(tj, g[j], mj, vj, ej, ema != nullptr, a, step_size);
+      t[j] = tj; mm[j] = mj; vv[j] = vj; ee[j] = ej;
+    }
+    *reinterpret_cast<f32x4*>(theta + i) = t;
+    *reinterpret_cast<f32x4*>(m + i) = mm;
+    *reinterpret_cast<f32x4*>(v + i) = vv;
+    if (ema) *reinterpret_cast<f32x4*>(ema + i) = ee;
+  }
+  // at most 3 singles in front and 3 behind: one thread each, counted from the far end of the workgroup
+  const int tail0 = head + 4 * nq, k = 255 - (int)threadIdx.x;
+  if (k < head) single(first + k);
+  else if (k - head < cnt - tail0) single(first + tail0 + (k - head));
   if (health && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(health, 1u);
 }
 
@@ -894,6 +959,33 @@ extern "C" int edm_adam_ema(float* theta, float* grad, float* m, float* v, float
   hipLaunchKernelGGL(k_adam_ema, dim3(grid_for(n4, 256)), dim3(256), 0, st, theta, grad, m, v, ema, n4, n, a,
                      (const StepParams*)dyn, zero_grad, health);
   EDM_CHECK_LAUNCH("adam_ema");
+  return EDM_OK;
+}
+// edm_adam_ema over element ranges only (k_adam_ema_ranges): ranges = DEVICE array of n_ranges (first element, length)
+// pairs of longs, chunks = DEVICE array of n_chunks (range id, offset inside the range) pairs of ints, one per 1024
+// elements.  Both must stay valid and unchanged until the launch has executed (for a captured stream: for the life of the
+// graph).  n_chunks == 0 launches nothing.  Everything else as edm_adam_ema.
+extern "C" int edm_adam_ema_ranges(float* theta, float* grad, float* m, float* v, float* ema, long n, const long* ranges,
+                                   int n_ranges, const int* chunks, int n_chunks, float lr, float b1, float b2,
+                                   float eps, int step, float ema_beta, float grad_scale, const void* dyn,
+                                   int zero_grad, unsigned* health, hipStream_t st) {
+  EDM_REQUIRE(theta && grad && m && v && n > 0 && step >= 1, "adam_ema_ranges: bad args");
+  EDM_REQUIRE(n_ranges >= 0 && n_chunks >= 0 && (n_chunks == 0 || (ranges && chunks && n_ranges > 0)),
+              "adam_ema_ranges: %d chunks over %d ranges need both tables", n_chunks, n_ranges);
+  EDM_REQUIRE(((uintptr_t)theta % 16 == 0) && ((uintptr_t)grad % 16 == 0) && ((uintptr_t)m % 16 == 0) &&
+                  ((uintptr_t)v % 16 == 0) && (!ema || (uintptr_t)ema % 16 == 0),
+              "adam_ema_ranges: arenas must be 16-byte aligned");
+  if (n_chunks == 0) return EDM_OK;
+  AdamArgs a;
+  a.lr = lr; a.b1 = b1; a.b2 = b2; a.eps = eps;
+  a.bc1 = (float)(1.0 - pow((double)b1, (double)step));
+  a.bc2sqrt = (float)sqrt(1.0 - pow((double)b2, (double)step));
+  a.ema_beta = ema_beta;
+  a.grad_scale = grad_scale;
+  static_assert(sizeof(AdamRange) == 2 * sizeof(long), "ranges are pairs of longs");
+  hipLaunchKernelGGL(k_adam_ema_ranges, dim3((unsigned)n_chunks), dim3(256), 0, st, theta, grad, m, v, ema, n,
+                     (const AdamRange*)ranges, n_ranges, (const int2*)chunks, a, (const StepParams*)dyn, zero_grad, health);
+  EDM_CHECK_LAUNCH("adam_ema_ranges");
   return EDM_OK;
 }
 // edm_adam_ema plus K (1..4) post-hoc EMA profile arenas of n floats each: profiles is a HOST array of K device pointers

@@ -161,6 +161,7 @@ class FusedAdam(torch.optim.Optimizer):
         self.v = torch.zeros_like(self.arena.theta)
         self.step_count = 0
         self.grad_scale = 1.0
+        self._complement_tables = {}    # fused set -> (ranges, chunks, lo, hi): the rest of the arena (_complement_table)
 
     # fuse_zero_grad = True: `step()` clears the gradient arena in the pass that reads it (it is the last reader) and the
     # `zero_grad()` that follows is free -- instead of a separate 142 MB fill (Trainer.fit and bench.py switch it on;
@@ -188,9 +189,24 @@ class FusedAdam(torch.optim.Optimizer):
         if self._cleared and not _grads_written_since_clear(self):
             self._cleared = False
             self.arena.rebind_grads()
+            self._note_clear()
             return
         self._cleared = False
         self.arena.zero_grad()
+        self._note_clear()
+
+    # "The arena is all zero and no gradient-producing pass has started since": what lets graph.CapturedTrainStep apply the
+    # update inside the weight-gradient finish kernels, which never read the arena rows they cover.  Every clearing call
+    # notes the forward epoch; a Denoiser forward with autograd on (training or eval mode) moves it on.
+    _clear_epoch = -1
+
+    def _note_clear(self):
+        from . import networks
+        self._clear_epoch = networks.FORWARD_EPOCH
+
+    def arena_known_clear(self) -> bool:
+        from . import networks
+        return self._clear_epoch == networks.FORWARD_EPOCH
 
     @torch.no_grad()
     def step(self, closure=None, ema: Optional[torch.Tensor] = None, ema_beta: float = 0.0):
@@ -208,21 +224,62 @@ class FusedAdam(torch.optim.Optimizer):
         self._cleared = bool(self.fuse_zero_grad)
         from . import networks
         self._fwd_epoch_at_clear = networks.FORWARD_EPOCH
+        if self.fuse_zero_grad:
+            self._note_clear()
         networks.bump_weight_epoch()
         return loss
 
     @torch.no_grad()
-    def step_dyn(self, dyn: torch.Tensor, ema: Optional[torch.Tensor] = None):
+    def step_dyn(self, dyn: torch.Tensor, ema: Optional[torch.Tensor] = None, fused=None):
         """The same update with lr / bias corrections / ema_beta / grad_scale read from the device record `dyn`
         (edm_step_params) and the gradient arena cleared in the same pass: the form a captured step replays
-        (graph.CapturedTrainStep owns the host-side counters)."""
+        (graph.CapturedTrainStep owns the host-side counters).
+
+        fused: the (offset, numel) arena slices that the weight-gradient finish kernels of this backward pass have
+        already updated (networks.FusedOptPass.updated): the pass then runs over the rest of the arena only."""
         g = self.param_groups[0]
         self.arena.rebind_grads()
         if self.phema is not None:      # (the profile betas: uploaded by the caller, PowerProfiles.upload)
+            if fused:
+                raise RuntimeError("FusedAdam.step_dyn: post-hoc EMA profiles are updated by the whole-arena pass only")
             self._adam_phema(ema, max(1, self.step_count), 0.0, 1.0, dyn, True)
-            return
-        ops.adam_ema(self.arena.theta, self.arena.grad, self.m, self.v, ema, g["lr"], g["betas"][0], g["betas"][1],
-                     g["eps"], max(1, self.step_count), 0.0, 1.0, dyn=dyn, zero_grad=True)
+        elif fused:
+            # the rest of the arena: its longest contiguous stretch through the plain kernel (grid-stride quads, no table),
+            # the scattered remainder through the table-driven one
+            ranges, chunks, lo, hi = self._complement_table(fused)
+            args = (g["lr"], g["betas"][0], g["betas"][1], g["eps"], max(1, self.step_count), 0.0, 1.0)
+            if hi > lo:
+                ops.adam_ema(self.arena.theta[lo:hi], self.arena.grad[lo:hi], self.m[lo:hi], self.v[lo:hi],
+                             None if ema is None else ema[lo:hi], *args, dyn=dyn, zero_grad=True)
+            ops.adam_ema_ranges(self.arena.theta, self.arena.grad, self.m, self.v, ema, ranges, chunks, *args, dyn=dyn,
+                                zero_grad=True)
+        else:
+            ops.adam_ema(self.arena.theta, self.arena.grad, self.m, self.v, ema, g["lr"], g["betas"][0], g["betas"][1],
+                         g["eps"], max(1, self.step_count), 0.0, 1.0, dyn=dyn, zero_grad=True)
+        self._note_clear()
+
+    def _complement_table(self, fused):
+        """(ranges, chunks, lo, hi): the arena OUTSIDE the slices of `fused` as its longest stretch [lo, hi) (lo on a 16-byte
+        boundary, for ops.adam_ema) and a device table of everything else (ops.adam_ema_ranges).  Built once per set and kept
+        for the life of the optimizer: a captured graph goes on reading the table (a model has a handful of sets, ~50 KB
+        each).  A new set allocates and uploads, which a stream capture cannot do (the launch-table rule of DESIGN 3.7: the
+        table must not live in the capturing graph's pool) -- the warm-up steps of a captured step run the same set eagerly
+        first."""
+        key = tuple(sorted(fused))
+        tab = self._complement_tables.get(key)
+        if tab is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("FusedAdam: the set of layers updated by the weight-gradient finish differs from every "
+                                   "eager step before this capture; its range table cannot be built under stream capture")
+            n = self.arena.theta.numel()
+            lo = hi = 0
+            for start, length in ops.complement_ranges(key, n):
+                a = (start + 3) // 4 * 4
+                if start + length - a > hi - lo:
+                    lo, hi = a, start + length
+            ranges, chunks = ops.adam_ranges_table(key + (((lo, hi - lo),) if hi > lo else ()), n, self.arena.theta.device)
+            tab = self._complement_tables[key] = (ranges, chunks, lo, hi)
+        return tab
 
     def state_dict(self):
         # "offsets": where each parameter's slice sits in m / v.  Layout 3 derives them from a Python attribute of the

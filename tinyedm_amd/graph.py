@@ -16,7 +16,9 @@ Reference call sites this replaces: the Lightning automatic-optimisation loop ar
 """
 from __future__ import annotations
 
+import contextlib
 import math
+import os
 from typing import NamedTuple
 
 import numpy as np
@@ -73,6 +75,8 @@ class _CapturedStep(NamedTuple):
     loss: torch.Tensor      # static: rewritten by every replay
     token: object           # launch-table slots and plan pins of the capture (ops.release_capture)
     aug: object = None      # static copy of the batch's augment labels (a 3-element batch), or None
+    path: str = "unfused"   # the form of the optimizer update the graph holds (CapturedTrainStep.path) ...
+    fused_slices: tuple = ()   # ... and the arena slices its weight-gradient finish kernels update
 
 
 class CapturedTrainStep:
@@ -95,7 +99,6 @@ class CapturedTrainStep:
         # wgrad_fork: keep the weight-gradient side stream (networks.WGRAD_STREAM) as a BRANCH of the captured graph.  None:
         # EDM_GRAPH_FORK (default off: the CIFAR-10 step replays 2.6 % slower with the branch; the 272 M ImageNet net is the
         # other way round -- round 6 measurements in DESIGN 6).
-        import os
         self.wgrad_fork = (os.environ.get("EDM_GRAPH_FORK", "0") == "1") if wgrad_fork is None else bool(wgrad_fork)
         self.model = model
         self.opt = optimizer
@@ -122,6 +125,31 @@ class CapturedTrainStep:
         # True once a capture failed on ANY rank of a multi-rank job: every rank then runs the eager step from here on
         # (ranks replaying captured collectives beside a rank that issues none would hang)
         self.fallback = False
+        # The 3x3 weight-gradient finish applies Adam + EMA to the rows it holds and the optimizer kernel runs over the
+        # rest of the arena.  EDM_FUSED_OPT=0: the whole-arena optimizer pass (A/B runs, bisecting).
+        self.fused_opt = os.environ.get("EDM_FUSED_OPT", "1") != "0"
+        self._fused = False
+        self.last_path = None           # "fused" / "unfused": which form the latest step took ...
+        self.fused_slices = ()          # ... and the (arena offset, numel) of the weights its finish kernels updated
+
+    def path(self) -> str:
+        """the form the NEXT step takes.  "fused" needs this class to own the whole update with nothing between the finish
+        and the optimizer (no gradient all-reduce), no second consumer of the new weights in the optimizer pass (post-hoc
+        EMA profiles), and a gradient arena known to be all zero: the fused rows never read it."""
+        ok = (self.fused_opt and self.reducer is None and self.base.phema is None and self.base.fuse_zero_grad
+              and self.base.arena_known_clear() and not networks._DGRAD_ONLY[0])
+        return "fused" if ok else "unfused"
+
+    def _opt_pass(self):
+        if not self._fused:
+            return contextlib.nullcontext(None)
+        return networks.fused_opt_pass(self.base, self.ema.ema_arena if self.ema is not None else None, self.params.dev)
+
+    def _step_dyn(self, fo):
+        self.base.step_dyn(self.params.dev, ema=self.ema.ema_arena if self.ema is not None else None,
+                           fused=None if fo is None else fo.updated)
+        self.last_path = "unfused" if fo is None else "fused"
+        self.fused_slices = () if fo is None else tuple(sorted(fo.updated))
 
     # ---- host-side bookkeeping identical to the eager path
     def _upload(self):
@@ -164,11 +192,12 @@ class CapturedTrainStep:
         side, networks.WGRAD_STREAM = networks.WGRAD_STREAM, self.wgrad_fork   # the launch structure of the capture that follows
         try:
             with torch.cuda.stream(self.stream):
-                loss = self.model.training_step(batch, 0)
-                _backward(self.model, loss)
+                with self._opt_pass() as fo:
+                    loss = self.model.training_step(batch, 0)
+                    _backward(self.model, loss)
                 if self.reducer is not None:
                     self.reducer.finish()   # joins the comm stream; 1/world rides in the device record (grad_scale)
-                self.base.step_dyn(self.params.dev, ema=self.ema.ema_arena if self.ema is not None else None)
+                self._step_dyn(fo)
                 loss = loss.detach()        # drop the autograd graph (and with it the AccumulateGrad nodes) now
         except BaseException:
             if self.reducer is not None:
@@ -211,6 +240,11 @@ class CapturedTrainStep:
         key = (tuple(x.shape), x.dtype, None if y is None else (tuple(y.shape), y.dtype))
         if a is not None:                   # (a 2-element batch keeps the key it always had)
             key += ((tuple(a.shape), a.dtype),)
+        # the two forms are different launch sequences: a step that may not take the fused one (e.g. gradients of an
+        # eval-mode backward wait in the arena) does not replay a graph that would ignore them
+        self._fused = self.path() == "fused"    # (read by _eager / _capture: their signatures are what subclasses override)
+        if self._fused:
+            key += ("fused",)
         self._upload()
         networks.rng.dyn = self.params.dev
         try:
@@ -233,6 +267,8 @@ class CapturedTrainStep:
                 if ent.aug is not None:
                     ent.aug.copy_(a, non_blocking=True)
                 ent.graph.replay()
+                self.last_path, self.fused_slices = ent.path, ent.fused_slices
+                self.base._note_clear()     # (the replayed optimizer pass cleared the arena, as step_dyn notes for an eager one)
         finally:
             networks.rng.dyn = None
         self._calls += 1
@@ -262,11 +298,12 @@ class CapturedTrainStep:
         try:
             # (a failed capture leaves no graph: capturing() gives its launch-table slots back)
             with ops.capturing(graph, stream=self.stream, capture_error_mode=mode) as capture:
-                loss = self.model.training_step((sx, sy) if sa is None else (sx, sy, sa), 0)
-                _backward(self.model, loss)     # the reducer's hooks fork the comm stream off the capture stream ...
+                with self._opt_pass() as fo:
+                    loss = self.model.training_step((sx, sy) if sa is None else (sx, sy, sa), 0)
+                    _backward(self.model, loss)     # the reducer's hooks fork the comm stream off the capture stream ...
                 if self.reducer is not None:
                     self.reducer.finish()       # ... and this joins it: the all-reduces are nodes of the graph
-                self.base.step_dyn(self.params.dev, ema=self.ema.ema_arena if self.ema is not None else None)
+                self._step_dyn(fo)
                 loss = loss.detach()
         except BaseException:
             if self.reducer is not None:
@@ -275,7 +312,7 @@ class CapturedTrainStep:
         finally:
             networks.WGRAD_STREAM = side
             self._restore(snap)
-        return graph, sx, sy, loss, capture.token, sa
+        return graph, sx, sy, loss, capture.token, sa, self.last_path, self.fused_slices
 
     def _drop(self, key):
         ops.drop_capture(self._graphs, key)

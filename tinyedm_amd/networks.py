@@ -14,6 +14,7 @@ Reference citations are ``file:line`` of ``/root/reference/src/tinyedm/networks.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 from typing import Optional
@@ -212,6 +213,42 @@ def _run_on_side(device, fn, tensors=()):
         fn()
 
 
+class FusedOptPass:
+    """One backward pass of graph.CapturedTrainStep in which the 3x3 weight-gradient finish applies the Adam + EMA update
+    itself (csrc/conv_wgrad3.hip, k_wgrad3_finish<true>): the optimizer whose arenas the rows live in, the device step
+    record, and `updated`, the (arena offset, numel) of every weight the pass has updated so far -- FusedAdam.step_dyn runs
+    over the rest.  Set by fused_opt_pass() for the duration of that step's forward and backward only: a plain
+    loss.backward() never sees it, and never updates a weight."""
+
+    def __init__(self, base, ema, dyn):
+        self.base, self.ema, self.dyn = base, ema, dyn
+        self.updated = []
+
+
+_fused_opt = [None]     # the running FusedOptPass, or None
+
+
+@contextlib.contextmanager
+def fused_opt_pass(base, ema, dyn):
+    prev, _fused_opt[0] = _fused_opt[0], FusedOptPass(base, ema, dyn)
+    try:
+        yield _fused_opt[0]
+    finally:
+        _fused_opt[0] = prev
+
+
+def _w3_apply(fo, args):
+    """the group through the apply form: every weight must be an arena slice this pass has not updated yet"""
+    theta = fo.base.arena.theta
+    g = fo.base.param_groups[0]
+    slices = [((w.data_ptr() - theta.data_ptr()) // 4, w.numel()) for _, _, w, *_rest in args]
+    if len(set(slices)) != len(slices) or set(slices) & set(fo.updated):
+        raise RuntimeError("tinyedm_amd: a 3x3 weight takes part twice in one backward pass; the optimizer update cannot "
+                           "ride in its weight-gradient finish (EDM_FUSED_OPT=0 switches that off)")
+    done = ops.wgrad3_group_apply(args, theta, fo.base.m, fo.base.v, fo.ema, fo.dyn, g["betas"][0], g["betas"][1], g["eps"])
+    fo.updated.extend(s for s, f in zip(slices, done) if f)
+
+
 def _flush_w3(key):
     """Launch the pending 3x3 weight gradients of device `key` as one group (arena mode: results accumulate
     straight into the gradient arena), then tell the data-parallel reducer that those gradients are final."""
@@ -221,7 +258,8 @@ def _flush_w3(key):
     dev = items[0][0].weight.device
     args = [(x, dy, m.weight.data, m.weight.grad, m._perm, scale, True) for m, x, dy, scale in items]
     keep = [t for _, x, dy, _ in items for t in (x, dy)]
-    _run_on_side(dev, lambda: ops.wgrad3_group(args), keep)
+    fo = _fused_opt[0]
+    _run_on_side(dev, (lambda: ops.wgrad3_group(args)) if fo is None else (lambda: _w3_apply(fo, args)), keep)
     _flush_fin(key)             # the small gradients of the same stretch of the backward pass ride along
     for m, _, _, _ in items:
         m.weight._edm_deferred = False

@@ -209,7 +209,7 @@ class _LaunchTables:
                 raise RuntimeError("tinyedm_amd: the launch-table pools of this device do not exist yet and cannot be "
                                    "created under stream capture (pinned + device allocations): run one eager step first, "
                                    "or bracket the capture with ops.capture_begin() / capture_end()")
-            nb = max(int(_lib.call("edm_wgrad3_table_bytes")), int(_lib.call("edm_conv_wgrad_1x1_group_table_bytes")),
+            nb = max(int(_lib.call("edm_wgrad3_apply_table_bytes")), int(_lib.call("edm_conv_wgrad_1x1_group_table_bytes")),
                      int(_lib.call("edm_wgrad_finish_multi_table_bytes")), int(_lib.call("edm_skip_gate_wgrad_multi_table_bytes")),
                      int(_lib.call("edm_skip_gate_fwd_multi_table_bytes")), int(_lib.call("edm_skip_gate_bwd_multi_table_bytes")))
             nb = (nb + 255) // 256 * 256
@@ -1380,6 +1380,12 @@ def wgrad3_group(items):
     items: sequence of (x, dy, w, grad, perm, scale, accumulate) with x (B,H,W,Cin) / dy (B,H,W,Cout) NHWC bf16,
     w the fp32 master weight (Cout, I, 3, 3) with I <= Cin, grad an fp32 tensor like w that receives (accumulate=0)
     or accumulates (1) the projected gradient, perm the optional packed-row permutation (int32)."""
+    arr, n, flops, nbytes = _wgrad3_items(items)
+    return _wgrad3_launch(items, arr, n, flops, nbytes, "edm_wgrad3_group")
+
+
+def _wgrad3_items(items):
+    """the host descriptor array of a group (WGrad3Item per layer) after the shape checks, with its flop / byte counts"""
     n = len(items)
     if not 0 < n <= W3_MAX_LAYERS:
         raise ValueError(f"wgrad3_group: 1..{W3_MAX_LAYERS} layers per group")
@@ -1408,6 +1414,12 @@ def wgrad3_group(items):
                                  int(bool(accumulate)))
         flops += 2.0 * B * H * W * Cin * Cout * 9
         nbytes += 2.0 * B * H * W * (Cin + Cout) + 4.0 * w.numel()
+    return arr, n, flops, nbytes
+
+
+def _wgrad3_launch(items, arr, n, flops, nbytes, entry, *extra):
+    """workspace, launch table and (when profiling) the kernel-only events around `entry`, edm_wgrad3_group or its
+    apply form; `extra` are the arguments the apply form takes between defer_upload and the stream"""
     nb = _lib.call("edm_wgrad3_workspace", ctypes.byref(arr), n)
     if nb <= 0:
         raise _lib.HipKernelError(f"edm_wgrad3_workspace failed: {_lib.lib().edm_last_error().decode()}")
@@ -1423,12 +1435,42 @@ def wgrad3_group(items):
             ev.record()             # (torch creates the hipEvent_t on the first record)
         _lib.call("edm_wgrad3_probe", ctypes.c_void_p(probe[0].cuda_event), ctypes.c_void_p(probe[1].cuda_event))
     with _prof("conv3x3_wgrad", flops, nbytes):
-        _lib.call("edm_wgrad3_group", ctypes.byref(arr), n, _p(work), nb, ctypes.c_void_p(th), ctypes.c_void_p(td), defer,
+        _lib.call(entry, ctypes.byref(arr), n, _p(work), nb, ctypes.c_void_p(th), ctypes.c_void_p(td), defer, *extra,
                   _stream())
     if probe is not None:
         PROFILE.setdefault("conv3x3_wgrad_kernel", []).append((probe[0], probe[1], flops, nbytes))
     release()
     return work
+
+
+def wgrad3_group_apply(items, theta, m, v, ema, dyn, b1, b2, eps):
+    """wgrad3_group whose finish pass applies the Adam + EMA update (ops.adam_ema's expressions, g = projected gradient
+    * grad_scale) to the weight rows it holds instead of writing their gradient: theta, m, v and ema rows are rewritten,
+    the gradient arena is not touched for them.  Every `w` of items is a slice of the flat arena `theta`; m, v and ema
+    (None: no EMA) are arenas laid out like theta, and lr / ema_beta / grad_scale / bias corrections come from the device
+    record `dyn` (edm_step_params).  A layer whose rows (I * 9 floats) exceed the kernel's register prefetch (7168) keeps the plain finish into its `grad`
+    (accumulate as given).  The health word of the device gets bit 0 on a non-finite gradient or weight.
+    Returns one bool per layer: True = updated here, False = its gradient is in `grad`."""
+    arr, n, flops, nbytes = _wgrad3_items(items)
+    _chk(theta, f32, "theta")
+    if dyn is None:
+        raise ValueError("wgrad3_group_apply: the device step record `dyn` is required")
+    for t, name in ((m, "m"), (v, "v"), (ema, "ema")):
+        if t is not None:
+            _chk(t, f32, name, theta.shape)
+    if m is None or v is None:
+        raise ValueError("wgrad3_group_apply: m and v arenas are required")
+    opt = (_lib.WGrad3Opt * n)()
+    base, total = theta.data_ptr(), theta.numel()
+    for k, (_, _, w, *_rest) in enumerate(items):
+        off = w.data_ptr() - base
+        if off < 0 or off % 4 or off // 4 + w.numel() > total:
+            raise ValueError(f"wgrad3_group_apply: weight {k} is not a slice of the parameter arena")
+        opt[k] = _lib.WGrad3Opt(m.data_ptr() + off, v.data_ptr() + off, None if ema is None else ema.data_ptr() + off)
+    fused = (ctypes.c_int * n)()
+    _wgrad3_launch(items, arr, n, flops, nbytes, "edm_wgrad3_group_apply", ctypes.byref(opt), _p(dyn), float(b1),
+                   float(b2), float(eps), _p(health(theta.device)), fused)
+    return [bool(f) for f in fused]
 
 
 # ------------------------------------------------------------------ weights
@@ -1804,6 +1846,52 @@ def adam_ema(theta, grad, m, v, ema, lr, b1, b2, eps, step, ema_beta, grad_scale
     _lib.call("edm_adam_ema", _p(theta), _p(grad), _p(m), _p(v), _p(ema), theta.numel(), float(lr), float(b1), float(b2),
               float(eps), int(step), float(ema_beta), float(grad_scale), _dyn(dyn), int(bool(zero_grad)),
               _p(health(theta.device)), _stream())
+
+
+ADAM_RANGE_CHUNK = 1024         # csrc/optim.hip ADAM_CHUNK: elements per workgroup of k_adam_ema_ranges
+
+
+def complement_ranges(excluded, n):
+    """[0, n) minus the `excluded` (offset, numel) slices, as a list of (first element, length)"""
+    ranges, pos = [], 0
+    for off, cnt in sorted((int(o), int(c)) for o, c in excluded):
+        if cnt <= 0:
+            continue
+        if off < pos or off + cnt > n:
+            raise ValueError(f"complement_ranges: slice ({off}, {cnt}) overlaps another or leaves the arena of {n}")
+        if off > pos:
+            ranges.append((pos, off - pos))
+        pos = off + cnt
+    if pos < n:
+        ranges.append((pos, n - pos))
+    return ranges
+
+
+def adam_ranges_table(excluded, n, device):
+    """Device table that drives adam_ema_ranges over [0, n) minus the `excluded` (offset, numel) slices: (ranges, chunks)
+    with ranges int64 [R][2] = (first element, length) and chunks int32 [C][2] = (range id, offset inside the range), one
+    entry per ADAM_RANGE_CHUNK elements.  Allocates and uploads: build it once per set, outside any stream capture."""
+    ranges = complement_ranges(excluded, n)
+    chunks = [(r, o) for r, (_, length) in enumerate(ranges) for o in range(0, length, ADAM_RANGE_CHUNK)]
+    rt = torch.tensor(ranges, dtype=torch.int64).reshape(-1, 2).to(device)
+    ct = torch.tensor(chunks, dtype=torch.int32).reshape(-1, 2).to(device)
+    return rt, ct
+
+
+def adam_ema_ranges(theta, grad, m, v, ema, ranges, chunks, lr, b1, b2, eps, step, ema_beta, grad_scale=1.0, dyn=None,
+                    zero_grad=False):
+    """adam_ema over the element ranges of an adam_ranges_table only; everything outside them is left as it is (an empty
+    table launches nothing).  Same expressions, health bit and zero_grad behaviour as adam_ema on the covered elements."""
+    for t in (grad, m, v) + ((ema,) if ema is not None else ()):
+        if t.numel() != theta.numel():
+            raise ValueError("adam_ema_ranges: arena size mismatch")
+    _chk(ranges, torch.int64, "ranges")
+    _chk(chunks, torch.int32, "chunks")
+    if ranges.dim() != 2 or ranges.shape[1] != 2 or chunks.dim() != 2 or chunks.shape[1] != 2:
+        raise ValueError("adam_ema_ranges: ranges is int64 [R][2], chunks int32 [C][2]")
+    _lib.call("edm_adam_ema_ranges", _p(theta), _p(grad), _p(m), _p(v), _p(ema), theta.numel(), _p(ranges),
+              ranges.shape[0], _p(chunks), chunks.shape[0], float(lr), float(b1), float(b2), float(eps), int(step),
+              float(ema_beta), float(grad_scale), _p(dyn), int(bool(zero_grad)), _p(health(theta.device)), _stream())
 
 
 PHEMA_MAX_PROFILES = 4          # edm_adam_ema_phema: K

@@ -1,5 +1,5 @@
 """Per-kernel time of ONE training step from a rocprofv3 kernel-trace csv of bench.py: steps are delimited by the
-k_adam_ema launches; prints the median-span step's kernels grouped by name (ms per step, launches, average us).
+optimizer (k_adam_ema*) launches; prints the median-span step's kernels grouped by name (ms per step, launches, average us).
     python tools/step_breakdown.py <kernel_trace.csv> [top]"""
 import collections
 import csv
@@ -9,7 +9,9 @@ import sys
 rows = list(csv.DictReader(open(sys.argv[1])))
 top = int(sys.argv[2]) if len(sys.argv) > 2 else 45
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-idx = [i for i, r in enumerate(rows) if "k_adam_ema" in r["Kernel_Name"]]
+# (the LAST optimizer launch of a step: the fused-optimizer step runs k_adam_ema and k_adam_ema_ranges back to back)
+idx = [i for i, r in enumerate(rows) if "k_adam_ema" in r["Kernel_Name"]
+       and not (i + 1 < len(rows) and "k_adam_ema" in rows[i + 1]["Kernel_Name"])]
 steps = []
 for a, b in zip(idx[:-1], idx[1:]):
     seg = rows[a + 1:b + 1]
