@@ -819,6 +819,43 @@ int edm_u8_knn_partial(const void* queries, const void* refs, long Q, long R, in
 int edm_knn_merge(const unsigned long long* keys, int n_lists, long Q, int k, unsigned* dist, int* idx,
                   edm_stream_t stream);
 
+/* ---------------------------------------------------------------- ideal denoiser of a training set (csrc/ideal.hip) */
+/* D*(x; sigma) = sum_i w_i y_i with w = softmax_i(-|x - y_i|^2 / (2 sigma^2)) over the rows y_i = (u_i / 255 - mean) / std of
+ * a resident uint8 set, and per query lse = log sum_i exp(l_i), ent = -sum w_i log w_i, the largest weight and its index (ties
+ * to the lower index).  The reference has no call site; Karras et al. 2022 App. B.3.
+ * Both products run on the fp32 MFMA (v_mfma_f32_16x16x4_f32) in units of one grey level around 128, where the uint8 side is an
+ * exact integer; the logit's three terms meet in fp64; softmax, statistics and the output are fp32 with max subtraction.  No
+ * floating-point atomics, every output element leaves by an ordinary store, and with the chunking fixed the bits of a row
+ * depend on that row's operands and the reference set alone.  A call walks the reference set in chunks of Rc rows:
+ *   begin, then per chunk (logits, softmax, accumulate), then finish; the workspace S is [Q][ld] floats, ld >= Rc.
+ * Layouts: x fp32 [Q][K] and refs u8 [R][K] row-contiguous, K = C H W of NCHW; sigma fp32 [Q]; labels int64 [Q] or null;
+ * ref_labels int32 [R] or null; qd fp64 [Q][2]; state fp32 [Q][8]; rnorms int32: edm_u8_norms of the rows passed.
+ * refs may sit at any byte alignment: 16-byte / 8-byte loads run when x (P for accumulate) and refs are 16-byte aligned and
+ * K % 16 == 0, element loads otherwise, with the same results.  Limits, status -1 and nothing launched otherwise:
+ * 1 <= K <= 32768, 1 <= Q <= 65535 * 64, 1 <= Rc, ref_base + Rc <= 2^31 - 128, ld >= Rc (accumulate: ld % 4 == 0 and S 16-byte
+ * aligned), mean finite, std finite and > 0, num_classes >= 1 with labels.  Status -2: the launch failed.
+ * Bad values never index memory: sigma <= 0 or non-finite, a non-finite x row or a class outside [0, num_classes) make that
+ * row NaN (top_idx -1), leave the other rows alone and set bit 1 of the health word (as edm_eval_diffuse for a bad level);
+ * classes are compared with ref_labels, never used as an index.  No host synchronisation, no host reads: capture-safe.
+ * edm_ideal_begin: per query |z|^2 and a^2 / (2 sigma^2) -> qd, the bad flag and the empty running state -> state.
+ * edm_ideal_logits: S[q][j] = the logit of query q against row j of the chunk `refs` (u8 [Rc][K]).
+ * edm_ideal_softmax: S -> the weights exp(l - running max) in place (a row of another class: 0, taking no part in max, sum or
+ *   statistics); state moves on by the chunk.  ref_base: the set index of the chunk's row 0.  Masking needs ref_labels AND
+ *   labels; with either null every row takes part.
+ * edm_ideal_accumulate: acc[q][k] = alpha_q acc[q][k] + sum_j S[q][j] (refs[j][k] - 128); first != 0: acc is written, not read.
+ * edm_ideal_finish: D = acc / (255 std s) + (128 / 255 - mean) / std (D may be acc), lse / ent / top_w fp32 [Q], top_idx
+ *   int32 [Q]; sets the health bit on a non-finite output too. */
+int edm_ideal_begin(const float* x, const float* sigma, const long long* labels, int num_classes, long Q, int K, float mean,
+                    float stdv, double* qd, float* state, unsigned* health, edm_stream_t stream);
+int edm_ideal_logits(const float* x, const void* refs, const int* rnorms, const double* qd, long Q, long Rc, int K,
+                     float mean, float stdv, float* S, long ld, edm_stream_t stream);
+int edm_ideal_softmax(float* S, long ld, long Q, long Rc, long ref_base, const int* ref_labels, const long long* labels,
+                      float* state, edm_stream_t stream);
+int edm_ideal_accumulate(const float* P, long ld, const void* refs, const float* state, long Q, long Rc, int K, int first,
+                         float* acc, edm_stream_t stream);
+int edm_ideal_finish(const float* acc, const float* state, long Q, int K, float mean, float stdv, float* D, float* lse,
+                     float* ent, float* top_w, int* top_idx, unsigned* health, edm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,7 @@ __version__ = "0.1.0"
 from . import _runtime_env  # noqa: F401  (first: sets HIP runtime flags before anything can initialise the GPU)
 from .edm import EDM, Diffuser
 from .ema import EMA, EMAOptimizer, FusedAdam, sigma_rel_to_gamma
+from .ideal import IdealDenoiser
 from .metric import WeightedMeanSquaredError
 from .networks import Conv2d, Denoiser, DenoiserWrapper, Embedding, Linear, manual_seed
 from .solvers import DeterministicSolver, GaussianBlur, LinearDegradation, MultistepSolver, StochasticSolver
@@ -13,6 +14,6 @@ from .trainer import LightningModule, Trainer
 from .vjp import input_vjp
 from . import config, networks, ops
 
-__all__ = ["EDM", "Diffuser", "DeterministicSolver", "StochasticSolver", "MultistepSolver", "LinearDegradation", "GaussianBlur", "input_vjp", "WeightedMeanSquaredError", "Denoiser", "Linear", "Conv2d",
+__all__ = ["EDM", "Diffuser", "DeterministicSolver", "StochasticSolver", "MultistepSolver", "LinearDegradation", "GaussianBlur", "input_vjp", "IdealDenoiser", "WeightedMeanSquaredError", "Denoiser", "Linear", "Conv2d",
            "Embedding", "DenoiserWrapper", "EMA", "EMAOptimizer", "FusedAdam", "Trainer", "LightningModule",
            "sigma_rel_to_gamma", "manual_seed", "config", "networks", "ops"]

@@ -193,6 +193,12 @@ SIGNATURES = {
     "edm_u8_norms": [P, L, I, P, P],
     "edm_u8_knn_partial": [P, P, L, L, I, I, I, L, I, I, P, P, P, P],
     "edm_knn_merge": [P, I, L, I, P, P, P],
+    # ideal.hip
+    "edm_ideal_begin": [P, P, P, I, L, I, F, F, P, P, P, P],
+    "edm_ideal_logits": [P, P, P, P, L, L, I, F, F, P, L, P],
+    "edm_ideal_softmax": [P, L, L, L, L, P, P, P, P],
+    "edm_ideal_accumulate": [P, L, P, P, L, L, I, I, P, P],
+    "edm_ideal_finish": [P, P, L, I, F, F, P, P, P, P, P, P, P],
 }
 # include/tinyedm_hip_diag.h: tools-only entry points, bound on demand by call()
 DIAG_SIGNATURES = {

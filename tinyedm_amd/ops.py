@@ -3074,3 +3074,98 @@ def u8_knn(queries, refs, k, exclude_self=False, splits=None, *, ref_chunk=None,
         at += s
     _lib.call("edm_knn_merge", _p(keys), at, Q, k, _p(dist), _p(idx), _stream())
     return (dist, idx) if out is not None else (dist.to(torch.int64), idx.to(torch.int64))
+
+
+# ------------------------------------------------------------------ ideal denoiser of a training set (csrc/ideal.hip)
+IDEAL_MAX_K = 32768              # elements per image (edm_u8_norms' limit: |u - 128|^2 summed in an int)
+IDEAL_MAX_Q = 65535 * 64         # one grid row per 64 queries
+IDEAL_MAX_R = 2 ** 31 - 128      # reference indices are 32-bit ints
+IDEAL_REF_CHUNK = 8192           # default rows per chunk: the workspace is Q * chunk floats
+IDEAL_STATE = 8                  # floats of running state per query
+
+
+def ideal_check(Q, R, K, ref_chunk=None):
+    """the limits of an ideal-denoiser call of Q queries against R references of K elements, as the library states them
+    -> the chunk length"""
+    if not 1 <= K <= IDEAL_MAX_K:
+        raise ValueError(f"ideal_denoise: images must hold 1 to {IDEAL_MAX_K} elements, got {K}")
+    if not 1 <= Q <= IDEAL_MAX_Q:
+        raise ValueError(f"ideal_denoise: expected 1 to {IDEAL_MAX_Q} queries, got {Q}")
+    if not 1 <= R <= IDEAL_MAX_R:
+        raise ValueError(f"ideal_denoise: expected 1 to 2^31 - 128 references, got {R}")
+    if ref_chunk is not None and (isinstance(ref_chunk, bool) or not isinstance(ref_chunk, int) or ref_chunk < 1):
+        raise ValueError(f"ideal_denoise: ref_chunk must be None or an integer >= 1, got {ref_chunk!r}")
+    return min(IDEAL_REF_CHUNK if ref_chunk is None else ref_chunk, R)
+
+
+def ideal_norm_check(mean, std):
+    mean, std = float(mean), float(std)
+    if not (math.isfinite(mean) and math.isfinite(std) and std > 0.0):
+        raise ValueError(f"ideal_denoise: mean must be finite and std finite and > 0, got {mean}, {std}")
+    return mean, std
+
+
+def u8_norms(x):
+    """int32 [N]: sum_j (x_j - 128)^2 of the rows of a uint8 [N, ...] tensor (edm_u8_norms)"""
+    x2 = _knn_rows(x, "x")
+    if not 1 <= x2.shape[1] <= KNN_MAX_D or x2.shape[0] > KNN_MAX_R:
+        raise ValueError(f"u8_norms: expected at most 2^31 - 128 rows of 1 to {KNN_MAX_D} elements, got {tuple(x2.shape)}")
+    out = torch.empty(x2.shape[0], dtype=torch.int32, device=x.device)
+    _lib.call("edm_u8_norms", _p(x2), x2.shape[0], x2.shape[1], _p(out), _stream())
+    return out
+
+
+def ideal_denoise(x, sigma, refs, rnorms, mean=0.5, std=0.5, *, ref_labels=None, labels=None, num_classes=None,
+                  ref_chunk=None):
+    """The ideal denoiser D*(x; sigma) of the uint8 set `refs` (y = (u / 255 - mean) / std) and its statistics ->
+    (D fp32 like x, lse fp32 [Q], ent fp32 [Q], top_w fp32 [Q], top_idx int32 [Q]).  x: contiguous fp32 [Q, ...] with the
+    trailing shape of refs (uint8 [R, ...], contiguous, any byte alignment); sigma: fp32 [Q]; rnorms: int32 [R], u8_norms
+    of refs.  ref_labels (int32 [R]) with labels (int64 [Q]) and num_classes restrict the softmax of query q to the
+    references of class labels[q]; labels=None uses every reference.  The references are walked ref_chunk rows at a time
+    (None: 8192) with a Q x ref_chunk workspace.  A sigma <= 0 or non-finite, a non-finite x row or a label outside
+    [0, num_classes) gives that row NaN (top_idx -1) and sets the health bit (check_health)."""
+    _chk_eval(x, f32, "x")
+    if x.dim() < 2 or x.numel() == 0:
+        raise ValueError(f"x: expected a non-empty [Q, ...] tensor, got {tuple(x.shape)}")
+    dev = x.device
+    _chk_eval(refs, torch.uint8, "refs", None, dev)
+    if refs.dim() < 2 or refs.numel() == 0 or tuple(refs.shape[1:]) != tuple(x.shape[1:]):
+        raise ValueError(f"ideal_denoise: refs {tuple(refs.shape)} must be a non-empty [R, ...] set of x's image shape "
+                         f"{tuple(x.shape[1:])}")
+    Q, R = x.shape[0], refs.shape[0]
+    K = x.numel() // Q
+    chunk = ideal_check(Q, R, K, ref_chunk)
+    mean, std = ideal_norm_check(mean, std)
+    _chk_eval(sigma, f32, "sigma", (Q,), dev)
+    _chk_eval(rnorms, torch.int32, "rnorms", (R,), dev)
+    ncls = 0
+    if labels is not None:
+        if ref_labels is None:
+            raise ValueError("ideal_denoise: labels need ref_labels (the classes of the references)")
+        ncls = _chk_classes(num_classes)
+        if ncls >= 1 << 31:
+            raise ValueError(f"ideal_denoise: num_classes must be below 2**31, got {ncls}")
+        _chk_eval(labels, torch.int64, "labels", (Q,), dev)
+    if ref_labels is not None:
+        _chk_eval(ref_labels, torch.int32, "ref_labels", (R,), dev)
+    r2 = refs.view(R, K)
+    ld = (chunk + 3) // 4 * 4
+    S = torch.empty(Q, ld, dtype=f32, device=dev)
+    qd = torch.empty(Q, 2, dtype=torch.float64, device=dev)
+    state = torch.empty(Q, IDEAL_STATE, dtype=f32, device=dev)
+    D = torch.empty_like(x)
+    lse, ent, top_w = (torch.empty(Q, dtype=f32, device=dev) for _ in range(3))
+    top_idx = torch.empty(Q, dtype=torch.int32, device=dev)
+    hw, st = _p(health(dev)), _stream()
+    masked = labels is not None
+    _lib.call("edm_ideal_begin", _p(x), _p(sigma), _p(labels), ncls, Q, K, mean, std, _p(qd), _p(state), hw, st)
+    with _prof("ideal", 4.0 * Q * R * K, float(R) * K * 2 * ((Q + 63) // 64)):
+        for a in range(0, R, chunk):
+            n = min(chunk, R - a)
+            _lib.call("edm_ideal_logits", _p(x), _p(r2[a:a + n]), _p(rnorms[a:a + n]), _p(qd), Q, n, K, mean, std, _p(S),
+                      ld, st)
+            _lib.call("edm_ideal_softmax", _p(S), ld, Q, n, a, _p(ref_labels) if masked else None,
+                      _p(labels) if masked else None, _p(state), st)
+            _lib.call("edm_ideal_accumulate", _p(S), ld, _p(r2[a:a + n]), _p(state), Q, n, K, int(a == 0), _p(D), st)
+    _lib.call("edm_ideal_finish", _p(D), _p(state), Q, K, mean, std, _p(D), _p(lse), _p(ent), _p(top_w), _p(top_idx), hw, st)
+    return D, lse, ent, top_w, top_idx
