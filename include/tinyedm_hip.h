@@ -690,6 +690,48 @@ int edm_eval_sqerr_classes(const float* D, const float* clean, int P, int C, lon
                            unsigned* health, edm_stream_t stream);
 int edm_scale_f32(const float* x, float s, float* y, long n, edm_stream_t stream);
 
+/* ---------------------------------------------------------------- adaptive ODE solver (adaptive.hip)
+ * The embedded Heun(2) / Euler(1) pair with local extrapolation, every sample at its own time and step size; the hot
+ * path reads nothing on the host.  x, D, dx, x1, y are contiguous fp32 [B, CHW].
+ * state: DEVICE, EDM_ADAPT_ROWS rows of B 32-bit words, row r at (uint32*)state + r * B:
+ *   0 t (fp32, the current time), 1 t1 (fp32, the trial time), 2 h (fp32, signed, the next proposal), 3 err (fp32, the
+ *   last E), 4 status (uint32: 0 active, 1 done, 2 failed), 5 accepted, 6 rejected (uint32 counters), 7 after_reject
+ *   (uint32: the last controlled step was a rejection).
+ * Snap rule: the trial time of a step h from t is t + h (fp64 sum, rounded to fp32), but t_end exactly when t + h passes
+ *   t_end or comes within 0.01 |h| of it.  A sample that is not active has t1 == t.
+ * edm_adapt_begin: t = t_start, h = h0 (non-zero, pointing from t_start to t_end; both times > 0), status = active,
+ *   counters and err zero, t1 by the snap rule.
+ * edm_adapt_euler: edm_heun_euler with t0 = t[b], t1 = t1[b] (DEVICE fp32 [B]) read per sample: with every sample at one
+ *   pair (t0, t1) it gives edm_heun_euler's bits.  A sample with t1[b] == t[b] gets x1 = x, dx = 0 whatever D holds.
+ *   dwordx4 when CHW % 4 == 0 and x, D, dx, x1 are 16-byte aligned, the same bits element by element otherwise.  Same
+ *   health bit as the Heun updates.
+ * edm_adapt_correct: y = x + (t1 - t0)(dx/2 + ((x1 - D1)/t1)/2) with edm_heun_correct's bits under the same condition
+ *   (y = x where t1[b] == t[b]), and part[b][chunk] = the chunk's share of
+ *   sum_j ((y_j - x1_j) / (atol + rtol max(|x_j|, |y_j|)))^2, every term in fp64 from the fp32 values.  part: DEVICE
+ *   workspace of B * EDM_NLL_MAX_CHUNKS doubles; the chunking depends on CHW alone and there are no floating-point
+ *   atomics, so a sample's sum has the same bits whatever B, its row, its neighbours or the memory path (the rule of
+ *   edm_eval_sqerr).  B <= 65535; atol, rtol >= 0, not both 0.  Same health bit.
+ * edm_adapt_control: one thread per ACTIVE sample, fp64: E = sqrt(sum_chunks part[b][.] / CHW) in index order; accept iff
+ *   E <= 1 (a NaN E rejects); factor = clamp(safety / sqrt(E), fac_min, top), top = fac_max, or 1 on a rejection and on
+ *   the step after one (a NaN factor is fac_min); h = (t1 - t) * factor; on accept t = t1, accepted++, status = done when
+ *   t == t_end; otherwise rejected++.  A sample still active with |h| < h_floor |t| becomes failed and sets the health
+ *   bit of the Heun updates.  Then t1 by the snap rule (t1 = t unless active).  accept: DEVICE uint8 [B], WRITTEN for
+ *   every sample (0 for one that was not active); active: DEVICE int32, += the number of samples still active.
+ *   0 < safety <= 1, 0 < fac_min < 1 <= fac_max < inf, 0 <= h_floor < 1.
+ * edm_adapt_commit: x = accept[b] ? y : x in place; a sample with accept[b] == 0 is not written.  dwordx4 when
+ *   CHW % 4 == 0 and x, y are 16-byte aligned. */
+#define EDM_ADAPT_ROWS 8
+int edm_adapt_begin(float t_start, float t_end, float h0, int B, void* state, edm_stream_t stream);
+int edm_adapt_euler(const float* x, const float* D, const float* t, const float* t1, int B, long CHW, float* dx,
+                    float* x1, unsigned* health, edm_stream_t stream);
+int edm_adapt_correct(const float* x, const float* dx, const float* x1, const float* D1, const float* t, const float* t1,
+                      int B, long CHW, double atol, double rtol, float* y, double* part, unsigned* health,
+                      edm_stream_t stream);
+int edm_adapt_control(const double* part, int B, long CHW, float t_end, double safety, double fac_min, double fac_max,
+                      double h_floor, void* state, unsigned char* accept, int* active, unsigned* health,
+                      edm_stream_t stream);
+int edm_adapt_commit(float* x, const float* y, const unsigned char* accept, int B, long CHW, edm_stream_t stream);
+
 /* ---------------------------------------------------------------- reference-precision evaluation (eval_f32.hip)
  * The reference samples / validates in fp32 (generate.py:39-44, callbacks.py:41-49, solvers.py:43-59).  These entry
  * points are the exact-fp32 forward: NHWC fp32 activations [pixels][channels], fp32 effective weights (the w_hat arrays

@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("EDM_LIB_PATH") or os.path.join(_HERE, "libtinyedm_hip
 
 P, I, L, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
 U, U64 = ctypes.c_uint, ctypes.c_ulonglong
+D = ctypes.c_double
 
 # name -> argtypes (every function returns int status unless listed in _RET)
 SIGNATURES = {
@@ -144,6 +145,12 @@ SIGNATURES = {
     "edm_eval_diffuse_classes": [P, P, P, P, I, P, I, I, L, P, P, P, P],
     "edm_eval_sqerr_classes": [P, P, I, I, L, P, P, P, P],
     "edm_scale_f32": [P, F, P, L, P],
+    # adaptive.hip
+    "edm_adapt_begin": [F, F, F, I, P, P],
+    "edm_adapt_euler": [P, P, P, P, I, L, P, P, P, P],
+    "edm_adapt_correct": [P, P, P, P, P, P, I, L, D, D, P, P, P, P],
+    "edm_adapt_control": [P, I, L, F, D, D, D, D, P, P, P, P, P],
+    "edm_adapt_commit": [P, P, P, I, L, P],
     # restore.hip
     "edm_degrade": [P, P, I, I, I, I, I, I, P],
     "edm_project_denoised": [P, P, P, P, P, I, I, I, I, I, I, P, P],

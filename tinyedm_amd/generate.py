@@ -41,6 +41,13 @@ Multistep sampling (MultistepSolver, DPM-Solver++ of Lu et al. 2022): `--solver 
 default, DPM-Solver++(2M)) or 3 spends one network evaluation per step, N in all against Heun's 2N - 1.  It combines
 with every guidance flag; a nonzero `--S_churn` with it is an error.  `--solver heun` (the default) is the Heun solver,
 byte-identical to a run without these flags.
+Adaptive sampling (AdaptiveSolver): `--solver adaptive` integrates sigma_max -> sigma_min of the `--num_steps` table to a
+tolerance, `--rtol` (1e-3) and `--atol` (1e-4), every image at its own step size, at most `--max_iterations` (1024)
+controlled steps of two network evaluations each, and ends with the table's closing step; the loop is eager.
+`--solver_report FILE.json` records {"accepted", "rejected": per image, "iterations": per batch, the totals and
+"rejected_share"}.  It combines with `--guidance`, `--guide_unconditional` / a guide network and `--invert_to` (the
+latents then close the loop with an adaptive solve); `--guidance_interval`, `--S_churn`, `--init_dir` without
+`--invert_to`, `--start_step`, `--mask_box`, `--restore_*`, `--dps_scale` and `--likelihood_to` are errors.
 
     python -m tinyedm.generate --ckpt_path last.ckpt --load_ema --solver dpmpp --solver_order 2 --num_steps 32 \\
         --output_dir samples --num_samples 50000 --image_size 32 --num_classes 10 --batch_size 512
@@ -111,10 +118,10 @@ CIFAR_STD = (0.24703223, 0.24348513, 0.26158784)
 
 def _check_solver(solver, S_churn) -> None:
     """the sampler choices that need nothing loaded: checked before any checkpoint or network is"""
-    if solver not in ("heun", "dpmpp"):
-        raise ValueError(f"generate: solver must be 'heun' or 'dpmpp', got {solver!r}")
-    if solver == "dpmpp" and float(S_churn) != 0.0:
-        raise ValueError(f"generate: --solver dpmpp is deterministic; --S_churn must be 0, got {S_churn} (stochastic "
+    if solver not in ("heun", "dpmpp", "adaptive"):
+        raise ValueError(f"generate: solver must be 'heun', 'dpmpp' or 'adaptive', got {solver!r}")
+    if solver in ("dpmpp", "adaptive") and float(S_churn) != 0.0:
+        raise ValueError(f"generate: --solver {solver} is deterministic; --S_churn must be 0, got {S_churn} (stochastic "
                          "sampling is --solver heun)")
 
 
@@ -139,7 +146,7 @@ def _check_conditioning(init_dir, start_step, mask_box, invert_to, solver, S_chu
             raise ValueError(f"generate: --mask_box X0 Y0 X1 Y1 needs integers with 0 <= X0 < X1 <= {image_size} and "
                              f"0 <= Y0 < Y1 <= {image_size}, got {mask_box}")
     if invert_to is not None:
-        if solver != "heun" or float(S_churn) != 0.0:
+        if solver not in ("heun", "adaptive") or float(S_churn) != 0.0:
             raise ValueError("generate: --invert_to runs the deterministic Heun solver upwards: no --solver dpmpp, no "
                              "--S_churn")
         if mask_box is not None:
@@ -161,6 +168,34 @@ def _check_conditioning(init_dir, start_step, mask_box, invert_to, solver, S_chu
     if network_dtype == "bf16":
         raise ValueError("generate: --likelihood_to needs --network_dtype f32x3 or f32 (a difference quotient at bf16 "
                          "evaluation error is meaningless)")
+
+
+def _check_adaptive(solver, guidance_interval, init_dir, start_step, mask_box, invert_to, likelihood_to,
+                    restore_scale, restore_gray, dps_scale, rtol, atol, max_iterations, solver_report) -> None:
+    """the choices of --solver adaptive that need nothing loaded"""
+    import math
+    if solver != "adaptive":
+        for flag, on in (("--rtol", rtol is not None), ("--atol", atol is not None),
+                         ("--max_iterations", max_iterations is not None), ("--solver_report", solver_report is not None)):
+            if on:
+                raise ValueError(f"generate: {flag} needs --solver adaptive")
+        return
+    for flag, on in (("--guidance_interval", guidance_interval is not None), ("--mask_box", mask_box is not None),
+                     ("--restore_scale / --restore_gray", restore_scale != 1 or bool(restore_gray)),
+                     ("--dps_scale", dps_scale is not None), ("--likelihood_to", likelihood_to is not None),
+                     ("--start_step", start_step != 0),
+                     ("--init_dir without --invert_to", init_dir is not None and invert_to is None)):
+        if on:
+            raise ValueError(f"generate: --solver adaptive does not take {flag} (it integrates sigma_max <-> sigma_min, every "
+                             "sample at its own sigma); use --solver heun")
+    for flag, v in (("--rtol", rtol), ("--atol", atol)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0):
+            raise ValueError(f"generate: {flag} must be a finite number >= 0, got {v!r}")
+    if rtol == 0 and atol == 0:
+        raise ValueError("generate: --rtol and --atol must not both be 0")
+    if max_iterations is not None and (isinstance(max_iterations, bool) or not isinstance(max_iterations, int) or
+                                       max_iterations < 1):
+        raise ValueError(f"generate: --max_iterations must be an integer >= 1, got {max_iterations!r}")
 
 
 def _check_labels_to(labels_to, init_dir) -> None:
@@ -263,10 +298,13 @@ def load_images(init_dir, mean, std, image_size, channels) -> torch.Tensor:
 
 def _validate(*, solver, S_churn, init_dir, start_step, num_steps, mask_box, invert_to, likelihood_to, network_dtype,
               num_probes, dequantize, image_size, dps_scale, blur_std, blur_radius, measurement_noise, restore_scale,
-              restore_gray, save_degraded, restore_report, labels_to, guided) -> tuple:
+              restore_gray, save_degraded, restore_report, labels_to, guided, guidance_interval=None, rtol=None, atol=None,
+              max_iterations=None, solver_report=None) -> tuple:
     """every choice that needs nothing loaded, checked once and in one order for generate() and the command line; returns
     (posterior, restoring): whether the run samples with DPS, and whether it restores (DDNM or DPS)"""
     _check_solver(solver, S_churn)
+    _check_adaptive(solver, guidance_interval, init_dir, start_step, mask_box, invert_to, likelihood_to,
+                    restore_scale, restore_gray, dps_scale, rtol, atol, max_iterations, solver_report)
     _check_conditioning(init_dir, start_step, mask_box, invert_to, solver, S_churn, image_size,
                         likelihood_to=likelihood_to, network_dtype=network_dtype, num_probes=num_probes,
                         dequantize=dequantize)
@@ -374,6 +412,20 @@ def _run_restore(model, datamodule, op, solve_kw, noise, rank_seed, back, stat, 
     print(f"[rank {where[0]}] wrote the {what} {where[1]} to {output_dir}", flush=True)
 
 
+def _solver_report(stats, solver, first) -> dict:
+    """--solver_report: per image the accepted and rejected steps of the adaptive solver, per batch its iterations, and
+    the totals (``stats``: the AdaptiveStats of every solve, in batch order)"""
+    accepted = [int(v) for s in stats for v in s.accepted]
+    rejected = [int(v) for s in stats for v in s.rejected]
+    steps = sum(accepted) + sum(rejected)
+    return {"accepted": accepted, "rejected": rejected, "iterations": [s.iterations for s in stats],
+            "accepted_total": sum(accepted), "rejected_total": sum(rejected),
+            "rejected_share": sum(rejected) / steps if steps else None,
+            "evaluations": sum(s.evaluations for s in stats), "guide_evaluations": sum(s.guide_evaluations for s in stats),
+            "rtol": solver.rtol, "atol": solver.atol, "max_iterations": solver.max_iterations, "first_index": first,
+            "num_images": len(accepted)}
+
+
 def _run_sample(model, datamodule, writer, n_local, where, output_dir, labels_to, labels, num_samples) -> None:
     """plain sampling through Trainer.predict; ``labels()`` (unless None) gives what --labels_to records"""
     from .trainer import Trainer
@@ -393,12 +445,13 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
              solver_order=2, init_dir=None, start_step=0, mask_box=None, invert_to=None, likelihood_to=None,
              num_probes=1, dequantize=False, restore_scale=1, restore_gray=False, save_degraded=None,
              restore_report=None, labels_to=None, dps_scale=None, blur_std=None, blur_radius=2,
-             measurement_noise=0.0) -> None:
+             measurement_noise=0.0, rtol=None, atol=None, max_iterations=None, solver_report=None) -> None:
     from . import _runtime_env
     from .callbacks import PreditionWriter
     from .datamodules import RandomNoiseDataModule
     from .edm import EDM
-    from .solvers import DeterministicSolver, GaussianBlur, LinearDegradation, MultistepSolver, StochasticSolver
+    from .solvers import (AdaptiveSolver, DeterministicSolver, GaussianBlur, LinearDegradation, MultistepSolver,
+                          StochasticSolver)
 
     posterior, restoring = _validate(
         solver=solver, S_churn=S_churn, init_dir=init_dir, start_step=start_step, num_steps=num_steps, mask_box=mask_box,
@@ -406,7 +459,8 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
         dequantize=dequantize, image_size=image_size, dps_scale=dps_scale, blur_std=blur_std, blur_radius=blur_radius,
         measurement_noise=measurement_noise, restore_scale=restore_scale, restore_gray=restore_gray,
         save_degraded=save_degraded, restore_report=restore_report, labels_to=labels_to,
-        guided=guide is not None or guide_ckpt_path is not None)
+        guided=guide is not None or guide_ckpt_path is not None, guidance_interval=guidance_interval, rtol=rtol, atol=atol,
+        max_iterations=max_iterations, solver_report=solver_report)
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -431,7 +485,18 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
             print(f"[rank {rank}] guidance 1.0: the guide network is unused", flush=True)
     rank_seed = seed + 1000003 * rank
     common = dict(num_steps=num_steps, guide=guide, guidance=guidance, guidance_interval=guidance_interval, seed=rank_seed)
-    if solver == "dpmpp":
+    adaptive_stats = []
+    if solver == "adaptive":
+        tol = {k: v for k, v in (("rtol", rtol), ("atol", atol), ("max_iterations", max_iterations)) if v is not None}
+        model.solver = AdaptiveSolver(**common, **tol)
+        graph = False               # the adaptive loop is eager: the host reads the active count every iteration
+        for name in ("solve", "invert"):    # every solve's statistics, in batch order, for --solver_report
+            def recorded(*a, _run=getattr(model.solver, name), **kw):
+                out = _run(*a, **kw)
+                adaptive_stats.append(model.solver.last_stats)
+                return out
+            setattr(model.solver, name, recorded)
+    elif solver == "dpmpp":
         model.solver = MultistepSolver(order=solver_order, **common)
     elif float(S_churn) != 0.0:     # (a negative or non-finite S_churn reaches the solver's validation)
         model.solver = StochasticSolver(S_churn=S_churn, S_min=S_min, S_max=S_max, S_noise=S_noise, **common)
@@ -492,6 +557,10 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
         labels = None if labels_to is None or rank != 0 else functools.partial(
             _drawn_labels, batch_size, num_workers, image_size, num_samples, num_classes, C, seed, world)
         _run_sample(model, datamodule, writer(output_dir), n_local, where, output_dir, labels_to, labels, num_samples)
+    if solver_report is not None:
+        _write_json(_rank_path(solver_report, rank, world), _solver_report(adaptive_stats, model.solver, first))
+        print(f"[rank {rank}] wrote the step counts of images {where[1]} to {_rank_path(solver_report, rank, world)}",
+              flush=True)
 
 
 def main(argv=None):
@@ -536,11 +605,19 @@ def main(argv=None):
     parser.add_argument("--S_max", type=float, default=float("inf"), help="churn only steps with t_i <= S_max (default inf)")
     parser.add_argument("--S_noise", type=float, default=1.0, help="scale of the churn noise (default 1)")
     # multistep sampling
-    parser.add_argument("--solver", choices=["heun", "dpmpp"], default="heun",
+    parser.add_argument("--solver", choices=["heun", "dpmpp", "adaptive"], default="heun",
                         help="heun (default): EDM's 2nd-order Heun, 2N-1 network evaluations; dpmpp: DPM-Solver++ "
-                             "multistep, N evaluations")
+                             "multistep, N evaluations; adaptive: Heun/Euler pair with per-sample step control to "
+                             "--rtol / --atol")
     parser.add_argument("--solver_order", type=int, choices=[1, 2, 3], default=2,
                         help="order of --solver dpmpp (default 2: DPM-Solver++(2M))")
+    # adaptive sampling
+    parser.add_argument("--rtol", type=float, default=None, help="--solver adaptive: relative tolerance (default 1e-3)")
+    parser.add_argument("--atol", type=float, default=None, help="--solver adaptive: absolute tolerance (default 1e-4)")
+    parser.add_argument("--max_iterations", type=int, default=None,
+                        help="--solver adaptive: controlled steps before the solve gives up (default 1024)")
+    parser.add_argument("--solver_report", type=str, default=None, metavar="FILE.json",
+                        help="--solver adaptive: write the accepted and rejected steps of every image and the totals")
     # image-conditioned sampling
     parser.add_argument("--init_dir", type=str, default=None,
                         help="directory of <index>.png images to start from (as this program writes them)")
@@ -624,7 +701,8 @@ def main(argv=None):
              likelihood_to=args.likelihood_to, num_probes=args.num_probes, dequantize=args.dequantize,
              restore_scale=args.restore_scale, restore_gray=args.restore_gray, save_degraded=args.save_degraded,
              restore_report=args.restore_report, labels_to=args.labels_to, dps_scale=args.dps_scale,
-             blur_std=args.blur_std, blur_radius=args.blur_radius, measurement_noise=args.measurement_noise)
+             blur_std=args.blur_std, blur_radius=args.blur_radius, measurement_noise=args.measurement_noise,
+             rtol=args.rtol, atol=args.atol, max_iterations=args.max_iterations, solver_report=args.solver_report)
 
 
 if __name__ == "__main__":

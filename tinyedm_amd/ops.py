@@ -2571,6 +2571,142 @@ def scale_f32(x, s):
 
 
 # ------------------------------------------------------------------ reference-precision evaluation (csrc/eval_f32.hip)
+ADAPT_ROWS = 8                  # EDM_ADAPT_ROWS: 32-bit words of per-sample state of the adaptive solver
+ADAPT_ACTIVE, ADAPT_DONE, ADAPT_FAILED = 0, 1, 2
+
+
+class AdaptRows(types.SimpleNamespace):
+    """the rows of an adaptive solver's device state as [B] views that share its memory: t, t1, h, err (fp32), status,
+    accepted, rejected, after_reject (int32 holding the uint32 bits)"""
+
+
+def adapt_rows(state) -> AdaptRows:
+    _adapt_state(state, 0, None)
+    f = state.view(f32)
+    return AdaptRows(t=f[0], t1=f[1], h=f[2], err=f[3], status=state[4], accepted=state[5], rejected=state[6],
+                     after_reject=state[7])
+
+
+def _adapt_state(state, B, device):
+    _chk_eval(state, torch.int32, "state", None, device)
+    if state.dim() != 2 or state.shape[0] != ADAPT_ROWS or state.shape[1] < 1 or (B and state.shape[1] != B):
+        raise ValueError(f"state: expected an int32 [{ADAPT_ROWS}, {B or 'B'}] tensor (ops.adapt_begin), got "
+                         f"{tuple(state.shape)}")
+
+
+def _adapt_batch(x, name="x"):
+    _chk_eval(x, f32, name)
+    if x.dim() < 2 or x.numel() == 0:
+        raise ValueError(f"{name}: expected a non-empty [B, ...] tensor, got {tuple(x.shape)}")
+    return x.shape[0], x.numel() // x.shape[0]
+
+
+def _adapt_times(t, t1, B, device):
+    for v, name in ((t, "t"), (t1, "t1")):
+        _chk_eval(v, f32, name, (B,), device)
+
+
+def adapt_begin(B, t_start, t_end, h0, device):
+    """The device state of an adaptive solve of B samples from t_start to t_end (both > 0) with the first proposal h0
+    (signed, pointing at t_end): an int32 [ADAPT_ROWS, B] tensor (ops.adapt_rows names its rows)."""
+    if isinstance(B, bool) or not isinstance(B, int) or B < 1:
+        raise ValueError(f"adapt_begin: B must be a positive integer, got {B!r}")
+    t_start, t_end, h0 = float(t_start), float(t_end), float(h0)
+    if not (all(math.isfinite(v) for v in (t_start, t_end, h0)) and t_start > 0 and t_end > 0 and t_start != t_end):
+        raise ValueError(f"adapt_begin: t_start and t_end must be finite, > 0 and different, got {t_start}, {t_end}")
+    if h0 == 0.0 or (h0 > 0) != (t_end > t_start):
+        raise ValueError(f"adapt_begin: h0 must be non-zero and point from t_start to t_end, got {h0}")
+    state = torch.empty((ADAPT_ROWS, B), dtype=torch.int32, device=device)
+    _adapt_state(state, B, None)            # (a host tensor ends here: there is no CPU path)
+    _lib.call("edm_adapt_begin", t_start, t_end, h0, B, _p(state), _stream())
+    return state
+
+
+def adapt_euler(x, D, t, t1):
+    """heun_euler with the times of sample b read from t[b], t1[b] (fp32 [B] on the device): (dx, x1).  A sample with
+    t1[b] == t[b] gets x1 = x and dx = 0 whatever D holds."""
+    B, CHW = _adapt_batch(x)
+    _chk_eval(D, f32, "D", x.shape, x.device)
+    _adapt_times(t, t1, B, x.device)
+    dx, x1 = torch.empty_like(x), torch.empty_like(x)
+    _lib.call("edm_adapt_euler", _p(x), _p(D), _p(t), _p(t1), B, CHW, _p(dx), _p(x1), _p(health(x.device)), _stream())
+    return dx, x1
+
+
+def adapt_correct(x, dx, x1, D1, t, t1, atol, rtol, part=None):
+    """heun_correct with per-sample times, and the error partials of the step: returns (y, part) with part an fp64
+    [B, NLL_MAX_CHUNKS] workspace whose row b holds, in its first chunks, the order-fixed partial sums of
+    ((y - x1) / (atol + rtol max(|x|, |y|)))^2 over sample b (adapt_control adds them up)."""
+    B, CHW = _adapt_batch(x)
+    if B > 65535:
+        raise ValueError(f"adapt_correct takes at most 65535 samples per call, got {B}")
+    for v, name in ((dx, "dx"), (x1, "x1"), (D1, "D1")):
+        _chk_eval(v, f32, name, x.shape, x.device)
+    _adapt_times(t, t1, B, x.device)
+    atol, rtol = float(atol), float(rtol)
+    if not (math.isfinite(atol) and math.isfinite(rtol) and atol >= 0 and rtol >= 0 and atol + rtol > 0):
+        raise ValueError(f"adapt_correct: atol and rtol must be finite, >= 0 and not both 0, got {atol}, {rtol}")
+    if part is None:
+        part = torch.empty((B, NLL_MAX_CHUNKS), dtype=torch.float64, device=x.device)
+    else:
+        _chk_eval(part, torch.float64, "part", (B, NLL_MAX_CHUNKS), x.device)
+    y = torch.empty_like(x)
+    _lib.call("edm_adapt_correct", _p(x), _p(dx), _p(x1), _p(D1), _p(t), _p(t1), B, CHW, atol, rtol, _p(y), _p(part),
+              _p(health(x.device)), _stream())
+    return y, part
+
+
+def adapt_chunks(CHW: int) -> int:
+    """how many entries of a row of `part` a sample of CHW elements fills (a function of CHW alone)"""
+    return min(((CHW + 3) // 4 + 255) // 256, NLL_MAX_CHUNKS)
+
+
+def adapt_control(part, CHW, state, t_end, active, *, safety=0.9, fac_min=0.2, fac_max=5.0, h_floor=1e-6, accept=None):
+    """The step controller, one thread per sample in fp64: E from `part`, accept iff E <= 1, the next h, t and t1 written
+    to `state`, counters updated (see include/tinyedm_hip.h).  Returns the accept flags, uint8 [B]; adds the number of
+    samples still active to `active`, a one-element int32 tensor on the device."""
+    _adapt_state(state, 0, None)
+    B = state.shape[1]
+    _chk_eval(part, torch.float64, "part", (B, NLL_MAX_CHUNKS), state.device)
+    _chk_eval(active, torch.int32, "active", None, state.device)
+    if active.numel() != 1:
+        raise ValueError(f"active: expected a one-element int32 tensor, got {tuple(active.shape)}")
+    if isinstance(CHW, bool) or not isinstance(CHW, int) or CHW < 1:
+        raise ValueError(f"adapt_control: CHW must be a positive integer, got {CHW!r}")
+    t_end, safety, fac_min, fac_max, h_floor = (float(v) for v in (t_end, safety, fac_min, fac_max, h_floor))
+    check_controller(safety, fac_min, fac_max, h_floor)
+    if not (math.isfinite(t_end) and t_end > 0):
+        raise ValueError(f"adapt_control: t_end must be finite and > 0, got {t_end}")
+    if accept is None:
+        accept = torch.empty(B, dtype=torch.uint8, device=state.device)
+    else:
+        _chk_eval(accept, torch.uint8, "accept", (B,), state.device)
+    _lib.call("edm_adapt_control", _p(part), B, CHW, t_end, safety, fac_min, fac_max, h_floor, _p(state), _p(accept),
+              _p(active), _p(health(state.device)), _stream())
+    return accept
+
+
+def check_controller(safety, fac_min, fac_max, h_floor=0.0) -> None:
+    """the controller constants of the adaptive solver, on the host"""
+    vals = (safety, fac_min, fac_max, h_floor)
+    if any(isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) for v in vals):
+        raise ValueError(f"adaptive controller: safety, fac_min, fac_max and h_floor must be finite numbers, got {vals}")
+    if not (0 < safety <= 1 and 0 < fac_min < 1 <= fac_max and 0 <= h_floor < 1):
+        raise ValueError(f"adaptive controller: needs 0 < safety <= 1, 0 < fac_min < 1 <= fac_max and 0 <= h_floor < 1, "
+                         f"got safety={safety}, fac_min={fac_min}, fac_max={fac_max}, h_floor={h_floor}")
+
+
+def adapt_commit(x, y, accept):
+    """x <- accept[b] ? y : x in place; a sample that was not accepted is not written.  Returns x."""
+    B, CHW = _adapt_batch(x)
+    _chk_eval(y, f32, "y", x.shape, x.device)
+    _chk_eval(accept, torch.uint8, "accept", (B,), x.device)
+    if x.data_ptr() == y.data_ptr():
+        raise ValueError("adapt_commit: y must not alias x")
+    _lib.call("edm_adapt_commit", _p(x), _p(y), _p(accept), B, CHW, _stream())
+    return x
+
+
 def _nhwc32(t, name):
     _chk(t, f32, name)
     if t.dim() != 4:

@@ -1008,3 +1008,179 @@ class MultistepSolver(DeterministicSolver):
         return ops.dpm_multistep(x, D, a, c0, c1, c2, Dg=Dg, w_dev=None if Dg is None else w_dev,
                                  m1=hist[(i - 1) % L] if k >= 2 else None, m2=hist[(i - 2) % L] if k >= 3 else None,
                                  m_out=hist[i % L] if L and i < self.num_steps - 1 else None)
+
+
+class AdaptiveStats(NamedTuple):
+    """what the last adaptive solve did (AdaptiveSolver.last_stats)"""
+    accepted: torch.Tensor      # int64 [B] on the host: accepted steps per sample
+    rejected: torch.Tensor      # int64 [B] on the host: rejected steps per sample
+    iterations: int             # controlled steps of the batch = max(accepted + rejected)
+    evaluations: int            # calls of the network, one per batch call (2 per iteration, + 1 for solve's closing step)
+    guide_evaluations: int      # calls of the guide, counted apart
+
+
+class AdaptiveSolver(DeterministicSolver):
+    """The probability-flow ODE integrated to a tolerance instead of on a table: the embedded Heun(2) / Euler(1) pair
+    with local extrapolation, every sample at its own time and step size, the step controller on the device
+    (csrc/adaptive.hip).  A trial step from t to t1 takes the Euler result x1 and the Heun result y, measures
+
+        E = sqrt(mean_j ((y_j - x1_j) / (atol + rtol max(|x_j|, |y_j|)))^2)        (per sample, fp64, order-fixed)
+
+    and is accepted iff E <= 1: then x <- y (the second-order result: local extrapolation), t <- t1.  Either way the
+    next step is h <- (t1 - t) clamp(safety E^(-1/2), fac_min, fac_max), with fac_max replaced by 1 on a rejection and on
+    the step after one; a step that would pass t_end, or come within 1 % of |h| of it, ends on t_end exactly.  One
+    iteration is two network evaluations of the whole batch plus four small kernels; samples that are done ride along
+    unchanged.  The loop is eager: after each iteration the host reads the 4-byte count of samples still active.
+
+    ``solve`` starts from sigma_max * x0, integrates sigma_max -> sigma_min (the ends of the parent's Karras table for
+    ``num_steps``, whose first step is also the first proposal h0) and finishes with the table's closing Euler step
+    sigma_min -> 0.  ``invert`` takes the image as the state at sigma_min, integrates upwards (h0: the table's last
+    step, reversed) and returns x / sigma_max, so ``solve(model, invert(model, img))`` closes the loop; only D_main is
+    evaluated there.  Plain guidance (``guide``, ``guidance``) mixes D = Dg + w (Dm - Dg) before the update;
+    ``guidance_interval`` raises ValueError (it would be per sample), and so do graph=True, start_step, image, mask,
+    degradation, operator / dps_scale, end_step and log_likelihood, on the host before any launch.  RuntimeError when
+    ``max_iterations`` is reached with samples still active or a sample's step fell under ``h_floor`` |t|.
+    ``last_stats`` (AdaptiveStats) describes the last solve or inversion."""
+
+    def __init__(self, num_steps: int = 18, sigma_min: float = 0.002, sigma_max: float = 80.0, rho: float = 7.0,
+                 dtype: str | None = None, *, guide=None, guidance: float = 1.0,
+                 guidance_interval: tuple[float, float] | None = None, seed: int = 0, rtol: float = 1e-3,
+                 atol: float = 1e-4, max_iterations: int = 1024, safety: float = 0.9, fac_min: float = 0.2,
+                 fac_max: float = 5.0, h_floor: float = 1e-6):
+        self.rtol, self.atol, self.max_iterations = rtol, atol, max_iterations
+        self.safety, self.fac_min, self.fac_max, self.h_floor = safety, fac_min, fac_max, h_floor
+        self.last_stats = None
+        if isinstance(num_steps, bool) or not isinstance(num_steps, int) or num_steps < 2:
+            raise ValueError(f"AdaptiveSolver: needs num_steps >= 2 (the table whose first step is h0), got {num_steps!r}")
+        super().__init__(num_steps, sigma_min, sigma_max, rho, dtype, guide=guide, guidance=guidance,
+                         guidance_interval=guidance_interval, seed=seed)
+
+    def guided_evaluations(self) -> tuple[bool, ...]:
+        """(whether the evaluations are guided,): all of them or none.  Host only; raises ValueError on an invalid
+        guidance or tolerance setting."""
+        if self.guidance_interval is not None:
+            raise ValueError("AdaptiveSolver: guidance_interval is not implemented (every sample is at its own sigma, so the "
+                             "interval would hold per sample)")
+        flags = super().guided_evaluations()
+        self._check_adaptive()
+        return (any(flags),)
+
+    def _check_adaptive(self) -> None:
+        for name in ("rtol", "atol"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+                raise ValueError(f"AdaptiveSolver: {name} must be a finite number >= 0, got {v!r}")
+        if not self.rtol + self.atol > 0:
+            raise ValueError("AdaptiveSolver: rtol and atol must not both be 0")
+        m = self.max_iterations
+        if isinstance(m, bool) or not isinstance(m, int) or m < 1:
+            raise ValueError(f"AdaptiveSolver: max_iterations must be an integer >= 1, got {m!r}")
+        ops.check_controller(self.safety, self.fac_min, self.fac_max, self.h_floor)
+        lo, hi = self.t_steps[self.num_steps - 1].item(), self.t_steps[0].item()
+        if not (math.isfinite(lo) and math.isfinite(hi) and 0 < lo < hi):
+            raise ValueError(f"AdaptiveSolver: needs 0 < sigma_min < sigma_max, got {self.sigma_min}, {self.sigma_max}")
+
+    def span(self, upwards: bool = False) -> tuple[float, float, float]:
+        """(t_start, t_end, h0) of ``solve`` (or of ``invert``, upwards) as the fp32 table values"""
+        ts = self.t_steps.tolist()
+        N = self.num_steps
+        return (ts[N - 1], ts[0], ts[N - 2] - ts[N - 1]) if upwards else (ts[0], ts[N - 1], ts[1] - ts[0])
+
+    @staticmethod
+    def _refuse(who: str, **given) -> None:
+        for name, on in given.items():
+            if on:
+                raise ValueError(f"AdaptiveSolver.{who}: {name} is not implemented for the adaptive solver (it integrates "
+                                 "sigma_max <-> sigma_min eagerly, every sample at its own sigma); use DeterministicSolver")
+
+    def _integrate(self, model, x, class_labels, span, guided, w_dev, who):
+        """x (fp32, owned: advanced in place) from t_start to t_end; returns x and the counting evaluation of (x, sigma),
+        guidance mix included; last_stats is written"""
+        t_start, t_end, h0 = span
+        B, CHW, dev = x.shape[0], x.numel() // x.shape[0], x.device
+        calls = [0, 0]
+
+        def evaluate(xs, sigma):
+            calls[0] += 1
+            D = model(xs, sigma, class_labels).float().contiguous()
+            if not guided:
+                return D
+            calls[1] += 1
+            Dg = self._guide_eval(model, xs, sigma, class_labels)
+            return ops.dpm_multistep(xs, D, 0.0, 1.0, 0.0, 0.0, Dg=Dg, w_dev=w_dev)     # (the mix, bit for bit)
+        state = ops.adapt_begin(B, t_start, t_end, h0, dev)
+        rows = ops.adapt_rows(state)
+        active = torch.zeros(1, dtype=torch.int32, device=dev)
+        part = torch.empty((B, ops.NLL_MAX_CHUNKS), dtype=torch.float64, device=dev)
+        accept = torch.empty(B, dtype=torch.uint8, device=dev)
+        iterations, seen, left = 0, 0, B
+        while left and iterations < self.max_iterations:
+            D = evaluate(x, rows.t)
+            dx, x1 = ops.adapt_euler(x, D, rows.t, rows.t1)
+            D1 = evaluate(x1, rows.t1)
+            y, _ = ops.adapt_correct(x, dx, x1, D1, rows.t, rows.t1, self.atol, self.rtol, part)
+            ops.adapt_control(part, CHW, state, t_end, active, safety=self.safety, fac_min=self.fac_min,
+                              fac_max=self.fac_max, h_floor=self.h_floor, accept=accept)
+            ops.adapt_commit(x, y, accept)
+            iterations += 1
+            total = int(active.item())          # the one host read of an iteration: 4 bytes
+            seen, left = total, total - seen
+        host = state.cpu()
+        status, t = host[4], host.view(torch.float32)[0]
+        self.last_stats = AdaptiveStats(host[5].long(), host[6].long(), iterations, calls[0], calls[1])
+        failed, live = status == ops.ADAPT_FAILED, status == ops.ADAPT_ACTIVE
+        if bool(failed.any()):
+            ops.health(dev).zero_()             # (the controller raised the bit for the failed samples: reported here)
+            raise RuntimeError(f"AdaptiveSolver.{who}: the step of {int(failed.sum())} of {B} samples fell under h_floor = "
+                               f"{self.h_floor} |t| at t = {t[failed].tolist()} (a non-finite state, or a tolerance "
+                               "the fp32 state cannot meet)")
+        if bool(live.any()):
+            raise RuntimeError(f"AdaptiveSolver.{who}: {int(live.sum())} of {B} samples are still active after "
+                               f"max_iterations = {self.max_iterations}, at t = {t[live].tolist()}")
+        return x, evaluate
+
+    @torch.no_grad()
+    def solve(self, model, x0, class_labels=None, graph: bool = False, *, start_step: int = 0, image=None, mask=None,
+              degradation=None, measurement=None, operator=None, dps_scale=None):
+        self._refuse("solve", **{"graph=True": graph, "start_step": start_step != 0, "image": image is not None,
+                                 "mask": mask is not None, "degradation": degradation is not None,
+                                 "measurement": measurement is not None, "operator": operator is not None,
+                                 "dps_scale": dps_scale is not None})
+        guided, = self.guided_evaluations()
+        _check_float("solve", "x0", x0)
+        if x0.dim() < 2 or x0.numel() == 0:
+            raise ValueError(f"solve: x0 must be a non-empty [B, ...] tensor, got {tuple(x0.shape)}")
+        _check_gpu("AdaptiveSolver", "x0", x0)
+        if guided:
+            self._check_guide(model, x0.device, class_labels)
+        span = self.span()
+        w_dev = torch.full((1,), float(self.guidance), device=x0.device) if guided else None
+        x = ops.scale_f32(x0.float().contiguous(), span[0])
+        x, evaluate = self._integrate(model, x, class_labels, span, guided, w_dev, "solve")
+        # the table's closing Euler step sigma_min -> 0: one batch evaluation
+        D = evaluate(x, torch.full((1,), span[1], device=x.device))
+        out = ops.heun_euler(x, D, span[1], 0.0)[1]
+        self.last_stats = self.last_stats._replace(evaluations=self.last_stats.evaluations + 1,
+                                                   guide_evaluations=self.last_stats.guide_evaluations + int(guided))
+        ops.check_health(x.device, "AdaptiveSolver.solve")
+        return out.to(x0.dtype)
+
+    @torch.no_grad()
+    def invert(self, model, image, class_labels=None, graph: bool = False, *, end_step: int = 0):
+        """Encode: the image, taken as the state at sigma_min, integrated upwards to sigma_max at the solver's tolerance;
+        returns the unit-scale latent x / sigma_max.  Only D_main is evaluated (``guide`` and ``guidance`` are ignored)."""
+        self._refuse("invert", **{"graph=True": graph, "end_step": end_step != 0})
+        self._check_adaptive()
+        _check_float("invert", "image", image)
+        if image.dim() < 2 or image.numel() == 0:
+            raise ValueError(f"invert: image must be a non-empty [B, ...] tensor, got {tuple(image.shape)}")
+        _check_gpu("AdaptiveSolver", "image", image)
+        span = self.span(upwards=True)
+        x = image.float().contiguous().clone()
+        x, _ = self._integrate(model, x, class_labels, span, False, None, "invert")
+        ops.check_health(x.device, "AdaptiveSolver.invert")
+        return ops.scale_f32(x, 1.0 / span[1]).to(image.dtype)
+
+    def log_likelihood(self, *args, **kwargs):
+        raise ValueError("AdaptiveSolver.log_likelihood: an adaptive likelihood is not implemented (the divergence would "
+                         "have to be integrated per sample); use DeterministicSolver")
