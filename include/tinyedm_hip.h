@@ -524,6 +524,46 @@ int edm_adam_ema_ranges(float* theta, float* grad, float* m, float* v, float* em
 int edm_adam_ema_phema(float* theta, float* grad, float* m, float* v, float* ema, float* const* profiles, int K,
                        const float* betas, long n, float lr, float b1, float b2, float eps, int step, float ema_beta,
                        float grad_scale, const void* dyn, int zero_grad, unsigned* health, edm_stream_t stream);
+/* Guarded optimizer step (grad_guard.hip).  edm_grad_guard reads the gradient arena once and leaves, in DEVICE memory, the
+ * per-tensor sums of squares and this 64-byte record; the *_guarded optimizer entry points read the record in the same
+ * stream, so a hipGraph-replayed step clips or skips without the host seeing a gradient.
+ *   sumsq = sum over tensors of sum (fp32(g) * grad_scale)^2, every square and sum in fp64, in a fixed order (no
+ *   floating-point atomics: bit-identical from run to run);  norm = sqrt(sumsq);
+ *   coef = min(1, max_norm / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_; exactly 1 when max_norm is +inf);
+ *   skip = skip_nonfinite && (an element is NaN, or |g| or |g * grad_scale| exceeds 3e38).
+ * steps / skipped / clipped / consecutive_skips advance when count != 0 (one thread, plain stores). */
+typedef struct {
+  float coef;
+  unsigned skip;
+  float norm;
+  float clip_value;
+  double sumsq;
+  unsigned long long steps, skipped, clipped;
+  unsigned consecutive_skips;
+  unsigned pad[3];
+} edm_grad_guard_record;
+/* grad: n floats at any 4-byte-aligned address.  chunks: DEVICE table of n_chunks (tensor id, first element, length)
+ * triples of longs, no chunk straddling two tensors or covering padding (elements outside the chunks are not read; a chunk
+ * that leaves [0, n) is skipped whole); tensors: DEVICE table of n_tensors (first chunk, number of chunks, first block,
+ * number of blocks) int quadruples.  The sums are taken over blocks of 1024 elements counted from each tensor's first
+ * element (n_blocks in all; every chunk but a tensor's last is a multiple of 1024 long), so the result does not depend on
+ * the chunk length.  Both tables stay valid and unchanged until the launches have executed (captured stream: for the life
+ * of the graph).  grad_scale / dyn: as edm_adam_ema.  max_norm, clip_value: >= 0, +inf = off.  part (n_blocks doubles) and
+ * flags (n_blocks + n_tensors words) are scratch; sumsq (n_tensors doubles) and record (zeroed once by the caller) are the
+ * outputs.  Three launches. */
+int edm_grad_guard(const float* grad, long n, const long* chunks, int n_chunks, const int* tensors, int n_tensors,
+                   int n_blocks, float grad_scale, const void* dyn, float max_norm, float clip_value, int skip_nonfinite,
+                   int count, double* part, unsigned* flags, double* sumsq, void* record, edm_stream_t stream);
+/* edm_adam_ema / edm_adam_ema_phema behind the guard: the same update expressions with grad_scale * record->coef as the
+ * gradient scale and every scaled element limited to +-record->clip_value.  record->skip != 0: theta, m, v, ema and the
+ * profiles stay bit for bit, the gradient arena is still cleared when zero_grad != 0, the health word is not touched. */
+int edm_adam_ema_guarded(float* theta, float* grad, float* m, float* v, float* ema, long n, float lr, float b1, float b2,
+                         float eps, int step, float ema_beta, float grad_scale, const void* dyn, int zero_grad,
+                         const void* record, unsigned* health, edm_stream_t stream);
+int edm_adam_ema_phema_guarded(float* theta, float* grad, float* m, float* v, float* ema, float* const* profiles, int K,
+                               const float* betas, long n, float lr, float b1, float b2, float eps, int step,
+                               float ema_beta, float grad_scale, const void* dyn, int zero_grad, const void* record,
+                               unsigned* health, edm_stream_t stream);
 /* post-hoc EMA reconstruction: acc_l += w_l * snap for l < L <= 8.  acc: device fp64 [L][n], snap: device fp32 [n],
  * w: HOST array of L doubles.  edm_phema_finish rounds n fp64 values to fp32. */
 int edm_phema_accumulate(double* acc, const float* snap, const double* w, int L, long n, edm_stream_t stream);

@@ -145,6 +145,10 @@ SIGNATURES = {
     "edm_eval_diffuse_classes": [P, P, P, P, I, P, I, I, L, P, P, P, P],
     "edm_eval_sqerr_classes": [P, P, I, I, L, P, P, P, P],
     "edm_scale_f32": [P, F, P, L, P],
+    # grad_guard.hip
+    "edm_grad_guard": [P, L, P, I, P, I, I, F, P, F, F, I, I, P, P, P, P, P],
+    "edm_adam_ema_guarded": [P, P, P, P, P, L, F, F, F, F, I, F, F, P, I, P, P, P],
+    "edm_adam_ema_phema_guarded": [P, P, P, P, P, P, I, P, L, F, F, F, F, I, F, F, P, I, P, P, P],
     # adaptive.hip
     "edm_adapt_begin": [F, F, F, I, P, P],
     "edm_adapt_euler": [P, P, P, P, I, L, P, P, P, P],

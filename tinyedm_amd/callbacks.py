@@ -345,3 +345,51 @@ class ClassifierAccuracy(_FirstValidationImages):
                                                                for l, v in enumerate(res["level_accuracy"])]:
             pl_module.log(name, v)
             trainer.callback_metrics[name] = float(v)
+
+
+class GradNormMonitor:
+    """Every ``every_n_steps`` optimizer steps: one JSON line into ``path`` with the step, the norm of the whole gradient
+    and the ``top`` parameter tensors by gradient norm (name, numel, norm) -- which tensor's gradient blew up.  Reads the
+    per-tensor buffer that every guarded optimizer step fills on the device (FusedAdam.set_guard), which stays valid
+    after the step has cleared the gradient arena; a visit costs two small device-to-host copies.  If no guard is set when
+    training starts, one with every limit off is enabled (the step then takes the guarded, "unfused" path)."""
+
+    def __init__(self, every_n_steps: int = 100, path: str = "grad_norms.jsonl", top: int = 10):
+        if every_n_steps < 1 or top < 1:
+            raise ValueError("GradNormMonitor: every_n_steps and top must be >= 1")
+        self.every_n_steps, self.path, self.top = int(every_n_steps), str(path), int(top)
+        self.last = None
+
+    @staticmethod
+    def _base(trainer):
+        from .ema import EMAOptimizer, FusedAdam
+        opt = trainer.optimizers[0]
+        base = opt.optimizer if isinstance(opt, EMAOptimizer) else opt
+        if not isinstance(base, FusedAdam):
+            raise TypeError("GradNormMonitor needs the flat-arena tinyedm_amd FusedAdam")
+        return base
+
+    def on_train_start(self, trainer, pl_module) -> None:
+        base = self._base(trainer)
+        if base.guard is None:
+            base.set_guard(monitor=True)
+
+    def on_train_batch_end(self, trainer, pl_module, *args) -> None:
+        if trainer.global_step % self.every_n_steps or trainer.global_rank != 0:
+            return
+        import json
+        base = self._base(trainer)
+        if base.guard is None:          # (a guard removed mid-run: nothing fills the buffer)
+            return
+        names = {id(p): n for n, p in pl_module.named_parameters()}
+        norms = base.per_tensor_grad_norms().cpu().numpy()
+        stats = base.guard_stats()
+        order = np.argsort(-np.nan_to_num(norms, nan=np.inf))[:self.top]
+        params = base.arena.params
+        self.last = {"step": int(trainer.global_step), "grad_norm": float(stats["grad_norm"]),
+                     "skipped": bool(stats["skipped_last"]),
+                     "top": [{"name": names.get(id(params[i]), f"param{i}"), "numel": int(params[i].numel()),
+                              "grad_norm": float(norms[i])} for i in order]}
+        os.makedirs(os.path.dirname(os.path.abspath(self.path)), exist_ok=True)
+        with open(self.path, "a") as f:
+            f.write(json.dumps(self.last) + "\n")

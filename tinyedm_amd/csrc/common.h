@@ -209,6 +209,20 @@ __device__ __forceinline__ bool adam_ema_update(float& t, float g, float& m, flo
   if (has_ema) e = a.ema_beta * e + (1.f - a.ema_beta) * t;
   return !(fabsf(gj) <= 3.0e38f) || !(fabsf(t) <= 3.0e38f);
 }
+// Gradient guard (grad_guard.hip): what one reduction over the gradient arena leaves for the guarded optimizer kernels of
+// the same step and for the host's log interval.  64 bytes; mirrored by include/tinyedm_hip.h (edm_grad_guard_record) and
+// tinyedm_amd/ops.py (GUARD_RECORD).
+struct GuardRecord {
+  float coef;                 // min(1, max_norm / (norm + 1e-6)): multiplies grad_scale in the guarded kernels
+  uint32_t skip;              // 1: the guarded kernels leave theta / m / v / ema / profiles as they are
+  float norm;                 // sqrt(sumsq)
+  float clip_value;           // per-element limit of the scaled gradient (inf: off)
+  double sumsq;               // sum over the tensors of sum (g * grad_scale)^2, fp64
+  unsigned long long steps, skipped, clipped;
+  uint32_t consecutive_skips;
+  uint32_t pad[3];
+};
+static_assert(sizeof(GuardRecord) == 64, "edm_grad_guard_record is 64 bytes");
 struct ModEpilogue {
   const float* lin;   // [B][lin_stride] fp32 embed-linear output
   const float* gain;  // device scalar

@@ -150,6 +150,50 @@ class PowerProfiles:
         self._events[k] = ev
 
 
+class GradGuardBuffers:
+    """Device side of a FusedAdam's gradient guard: the chunk table over the arena's parameter tensors, the per-tensor
+    fp64 sums of squares and the 64-byte record (ops.grad_guard), plus a second record / buffer for FusedAdam.grad_norm().
+    Allocates and uploads, so it is built outside any stream capture (the rule of FusedAdam._complement_table), once per
+    optimizer, and never freed before it: a captured step goes on reading these addresses."""
+
+    def __init__(self, arena: FlatArena):
+        dev = arena.theta.device
+        self.table = ops.grad_guard_table(arena.offsets, [p.numel() for p in arena.params], arena.theta.numel(), dev)
+        P = len(arena.params)
+        self.sumsq = torch.zeros(P, dtype=torch.float64, device=dev)
+        self.record = ops.guard_record(dev)
+        self.probe_sumsq = torch.zeros(P, dtype=torch.float64, device=dev)
+        self.probe_record = ops.guard_record(dev)
+
+
+class GradGuard:
+    """the limits of FusedAdam.set_guard and the buffers they act through"""
+
+    def __init__(self, buf: GradGuardBuffers, max_norm, clip_value, skip_nonfinite: bool):
+        self.buf = buf
+        self.max_norm = None if max_norm is None else float(max_norm)
+        self.clip_value = None if clip_value is None else float(clip_value)
+        self.skip_nonfinite = bool(skip_nonfinite)
+
+    def key(self):
+        """what a captured launch freezes: a graph captured under other limits must not be replayed"""
+        return (self.max_norm, self.clip_value, self.skip_nonfinite)
+
+    def state(self) -> dict:
+        r = ops.read_guard_record(self.buf.record)
+        return {"max_norm": self.max_norm, "clip_value": self.clip_value, "skip_nonfinite": self.skip_nonfinite,
+                "steps": r["steps"], "skipped": r["skipped"], "clipped": r["clipped"],
+                "consecutive_skips": r["consecutive_skips"]}
+
+    def load_counters(self, st: dict):
+        rec = np.zeros(1, dtype=ops.GUARD_RECORD)
+        rec["coef"] = 1.0
+        rec["clip_value"] = np.inf
+        for k in ("steps", "skipped", "clipped", "consecutive_skips"):
+            rec[k] = int(st.get(k, 0))
+        self.buf.record.copy_(torch.from_numpy(rec.view(np.int64).copy()))
+
+
 class FusedAdam(torch.optim.Optimizer):
     """Adam (no weight decay / amsgrad) with torch.optim.Adam semantics, one launch over the arena."""
 
@@ -175,6 +219,83 @@ class FusedAdam(torch.optim.Optimizer):
         """start tracking post-hoc EMA profiles with these gammas: every later step() / step_dyn() updates them"""
         self.phema = PowerProfiles(self.arena.theta, gammas)
         return self.phema
+
+    # gradient guard (GradGuard), enabled by set_guard(); None: step() / step_dyn() run exactly the unguarded kernels
+    guard: Optional["GradGuard"] = None
+
+    def set_guard(self, max_norm: Optional[float] = None, clip_value: Optional[float] = None,
+                  skip_nonfinite: bool = False, monitor: bool = False):
+        """Guard every later step() / step_dyn(): one reduction over the gradient arena leaves the norm of the whole
+        gradient, the clip coefficient and the skip decision in a device record, and the guarded optimizer kernel reads
+        it -- no host synchronisation, so the sequence replays inside a hipGraph.
+
+        max_norm: clip the gradient to this 2-norm (torch.nn.utils.clip_grad_norm_: coef = min(1, max_norm / (norm + 1e-6))).
+        clip_value: limit every element of the scaled gradient to +-clip_value (clip_grad_value_).
+        skip_nonfinite: a step whose gradient holds a NaN or an infinity changes nothing (weights, moments, EMA and
+            post-hoc EMA profiles stay bit for bit; the gradient arena is cleared as usual).
+        monitor: keep the reduction running with every limit off (what GradNormMonitor asks for).
+        `set_guard()` with no argument removes the guard.
+
+        The host does not know that a step was skipped: the Adam step count, the EMA step, the LR schedule and the Philox
+        step advance on a skipped step as on any other, so the bias corrections after k skips are those of step t + k.
+        While a guard is set a captured step takes the "unfused" path (graph.CapturedTrainStep.path)."""
+        for name, x in (("max_norm", max_norm), ("clip_value", clip_value)):
+            if x is not None and not float(x) >= 0.0:
+                raise ValueError(f"FusedAdam.set_guard: {name} must be >= 0, got {x}")
+        if max_norm is None and clip_value is None and not skip_nonfinite and not monitor:
+            self.guard = None
+            return None
+        if self._guard_buffers is None:     # built once, kept for the life of the optimizer: captured graphs read them
+            self._guard_buffers = GradGuardBuffers(self.arena)
+        self.guard = GradGuard(self._guard_buffers, max_norm, clip_value, bool(skip_nonfinite))
+        return self.guard
+
+    _guard_buffers: Optional["GradGuardBuffers"] = None
+
+    def _run_guard(self, grad_scale, dyn):
+        gd = self.guard
+        ops.grad_guard(self.arena.grad, gd.buf.table, gd.buf.sumsq, gd.buf.record, grad_scale=grad_scale, dyn=dyn,
+                       max_norm=gd.max_norm, clip_value=gd.clip_value, skip_nonfinite=gd.skip_nonfinite)
+
+    def _adam_guarded(self, ema, step, ema_beta, grad_scale, dyn, zero_grad):
+        """the guard's reduction, then the guarded form of the optimizer kernel (with the profiles when they are tracked)"""
+        g = self.param_groups[0]
+        self._run_guard(grad_scale, dyn)
+        args = (g["lr"], g["betas"][0], g["betas"][1], g["eps"], step, ema_beta, grad_scale)
+        if self.phema is None:
+            ops.adam_ema_guarded(self.arena.theta, self.arena.grad, self.m, self.v, ema, self.guard.buf.record, *args,
+                                 dyn=dyn, zero_grad=zero_grad)
+        else:
+            ops.adam_ema_phema_guarded(self.arena.theta, self.arena.grad, self.m, self.v, ema,
+                                       self.phema.arenas.unbind(0), self.phema.betas, self.guard.buf.record, *args,
+                                       dyn=dyn, zero_grad=zero_grad)
+
+    def guard_stats(self) -> dict:
+        """what the guard's device record holds after the latest step (one D2H copy of 64 bytes, which waits for the stream)"""
+        if self.guard is None:
+            raise RuntimeError("FusedAdam.guard_stats: no guard is set (set_guard)")
+        r = ops.read_guard_record(self.guard.buf.record)
+        return {"grad_norm": r["norm"], "clip_coef": r["coef"], "skipped_steps": r["skipped"], "clipped_steps": r["clipped"],
+                "consecutive_skips": r["consecutive_skips"], "steps": r["steps"], "skipped_last": bool(r["skip"])}
+
+    def per_tensor_grad_norms(self) -> torch.Tensor:
+        """2-norm of every parameter's scaled gradient as the latest guarded step saw it (device fp64 [P], arena order):
+        the guard's per-tensor buffer, which stays valid after the step has cleared the arena"""
+        if self.guard is None:
+            raise RuntimeError("FusedAdam.per_tensor_grad_norms: no guard is set (set_guard)")
+        return self.guard.buf.sumsq.sqrt()
+
+    def grad_norm(self, per_tensor: bool = False) -> torch.Tensor:
+        """The guard's reduction alone, for a loop of your own: the 2-norm of grad * grad_scale over the arena as it is now
+        (fp64, on the device; nothing is read back), or the P per-parameter norms.  It neither needs nor disturbs a guard
+        that is set: it has its own record and counts no step."""
+        if self._guard_buffers is None:
+            self._guard_buffers = GradGuardBuffers(self.arena)
+        b = self._guard_buffers
+        ops.grad_guard(self.arena.grad, b.table, b.probe_sumsq, b.probe_record, grad_scale=self.grad_scale, count=False)
+        if per_tensor:
+            return b.probe_sumsq.sqrt()
+        return b.probe_record.view(torch.float64)[2].sqrt()       # (the record's fp64 `sumsq` field)
 
     def _adam_phema(self, ema, step, ema_beta, grad_scale, dyn, zero_grad):
         g = self.param_groups[0]
@@ -214,7 +335,13 @@ class FusedAdam(torch.optim.Optimizer):
         g = self.param_groups[0]
         self.arena.rebind_grads()
         self.step_count += 1
-        if self.phema is None:
+        if self.guard is not None:
+            if self.phema is not None:
+                self.phema.upload(self.phema.count + 1)
+            self._adam_guarded(ema, self.step_count, ema_beta, self.grad_scale, None, self.fuse_zero_grad)
+            if self.phema is not None:
+                self.phema.count += 1
+        elif self.phema is None:
             ops.adam_ema(self.arena.theta, self.arena.grad, self.m, self.v, ema, g["lr"], g["betas"][0], g["betas"][1],
                          g["eps"], self.step_count, ema_beta, self.grad_scale, zero_grad=self.fuse_zero_grad)
         else:
@@ -239,7 +366,12 @@ class FusedAdam(torch.optim.Optimizer):
         already updated (networks.FusedOptPass.updated): the pass then runs over the rest of the arena only."""
         g = self.param_groups[0]
         self.arena.rebind_grads()
-        if self.phema is not None:      # (the profile betas: uploaded by the caller, PowerProfiles.upload)
+        if self.guard is not None:      # the norm of the WHOLE gradient comes first: no row may have been updated yet
+            if fused:
+                raise RuntimeError("FusedAdam.step_dyn: a guarded step needs the whole-arena pass (the weight-gradient "
+                                   "finish must not have updated rows before the gradient norm exists)")
+            self._adam_guarded(ema, max(1, self.step_count), 0.0, 1.0, dyn, True)
+        elif self.phema is not None:    # (the profile betas: uploaded by the caller, PowerProfiles.upload)
             if fused:
                 raise RuntimeError("FusedAdam.step_dyn: post-hoc EMA profiles are updated by the whole-arena pass only")
             self._adam_phema(ema, max(1, self.step_count), 0.0, 1.0, dyn, True)
@@ -289,7 +421,8 @@ class FusedAdam(torch.optim.Optimizer):
                 "offsets": list(self.arena.offsets), "numels": [p.numel() for p in self.arena.params],
                 "param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups],
                 **({} if self.phema is None else {"phema": {"profiles": self.phema.arenas, "count": self.phema.count,
-                                                             "gammas": list(self.phema.gammas)}})}
+                                                             "gammas": list(self.phema.gammas)}}),
+                **({} if self.guard is None else {"guard": self.guard.state()})}
 
     def load_state_dict(self, sd):
         """Accepts this class's own layout ({m, v, step}: flat arenas) or torch.optim.Adam's
@@ -339,6 +472,8 @@ class FusedAdam(torch.optim.Optimizer):
             raise KeyError("optimizer state dict has neither this build's {m, v, step} nor torch Adam's {state, param_groups}")
         for g, s in zip(self.param_groups, sd["param_groups"]):
             g.update({k: v for k, v in s.items() if k != "params"})
+        if self.guard is not None and "guard" in sd:       # the counters continue; the limits are those of this run
+            self.guard.load_counters(sd["guard"])
 
 
     def _load_profiles(self, sd, old_offsets):

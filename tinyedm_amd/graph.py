@@ -135,8 +135,10 @@ class CapturedTrainStep:
     def path(self) -> str:
         """the form the NEXT step takes.  "fused" needs this class to own the whole update with nothing between the finish
         and the optimizer (no gradient all-reduce), no second consumer of the new weights in the optimizer pass (post-hoc
-        EMA profiles), and a gradient arena known to be all zero: the fused rows never read it."""
-        ok = (self.fused_opt and self.reducer is None and self.base.phema is None and self.base.fuse_zero_grad
+        EMA profiles), no gradient guard (FusedAdam.set_guard: the finish kernels would update rows before the norm of the
+        whole gradient exists), and a gradient arena known to be all zero: the fused rows never read it."""
+        ok = (self.fused_opt and self.reducer is None and self.base.phema is None and self.base.guard is None
+              and self.base.fuse_zero_grad
               and self.base.arena_known_clear() and not networks._DGRAD_ONLY[0])
         return "fused" if ok else "unfused"
 
@@ -245,6 +247,8 @@ class CapturedTrainStep:
         self._fused = self.path() == "fused"    # (read by _eager / _capture: their signatures are what subclasses override)
         if self._fused:
             key += ("fused",)
+        if self.base.guard is not None:     # (the guard's limits are by-value arguments of the launches a graph holds)
+            key += (("guard",) + self.base.guard.key(),)
         self._upload()
         networks.rng.dyn = self.params.dev
         try:

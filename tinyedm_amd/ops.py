@@ -10,8 +10,9 @@ import functools
 import math
 import os
 import types
-from typing import Optional
+from typing import NamedTuple, Optional
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1925,6 +1926,163 @@ def adam_ema_phema(theta, grad, m, v, ema, profiles, betas, lr, b1, b2, eps, ste
     _lib.call("edm_adam_ema_phema", _p(theta), _p(grad), _p(m), _p(v), _p(ema), ptrs, K, _p(betas), theta.numel(),
               float(lr), float(b1), float(b2), float(eps), int(step), float(ema_beta), float(grad_scale), _dyn(dyn),
               int(bool(zero_grad)), _p(health(theta.device)), _stream())
+
+
+# ---- guarded optimizer step (csrc/grad_guard.hip)
+GUARD_BLOCK = 1024              # csrc/grad_guard.hip GUARD_BLOCK: elements per wave-level partial sum, counted from a tensor's start
+GUARD_CHUNK = 4096              # default elements per workgroup of k_grad_guard_chunks: a table parameter (a multiple of
+                                # GUARD_BLOCK) that moves work between workgroups, never a bit of the result
+# edm_grad_guard_record (include/tinyedm_hip.h, csrc/common.h GuardRecord): 64 bytes
+GUARD_RECORD = np.dtype([("coef", "<f4"), ("skip", "<u4"), ("norm", "<f4"), ("clip_value", "<f4"), ("sumsq", "<f8"),
+                         ("steps", "<u8"), ("skipped", "<u8"), ("clipped", "<u8"), ("consecutive_skips", "<u4"),
+                         ("pad", "<u4", (3,))])
+assert GUARD_RECORD.itemsize == 64
+
+
+class GuardTable(NamedTuple):
+    """device tables and scratch of grad_guard over one arena layout (grad_guard_table)"""
+    chunks: torch.Tensor        # int64 [C][3] = (tensor id, first element, length)
+    tensors: torch.Tensor       # int32 [P][4] = (first chunk, number of chunks, first block, number of blocks)
+    part: torch.Tensor          # float64 [NB]: block partials (scratch)
+    flags: torch.Tensor         # int32 [NB + P]: non-finite flags of the blocks, then of the tensors (scratch)
+    n: int                      # elements of the arena the table was built for
+
+
+def grad_guard_chunks(offsets, numels, n, chunk=GUARD_CHUNK):
+    """Host side of grad_guard_table: (chunks int64 [C][3], tensors int32 [P][4]) for parameter tensors at `offsets` with
+    `numels` elements in an arena of n.  Tensor p is tiled exactly by consecutive chunks of at most `chunk` elements (a
+    multiple of GUARD_BLOCK); no chunk straddles two tensors and none covers the padding between them.  tensors[p] also
+    names the tensor's run of GUARD_BLOCK-element blocks in the partial-sum scratch.  Overlapping or outlying slices are
+    refused (as by adam_ranges_table)."""
+    offsets, numels, n, chunk = [int(o) for o in offsets], [int(c) for c in numels], int(n), int(chunk)
+    if len(offsets) != len(numels) or not offsets:
+        raise ValueError("grad_guard_table: one offset per tensor, at least one tensor")
+    if chunk < GUARD_BLOCK or chunk % GUARD_BLOCK:
+        raise ValueError(f"grad_guard_table: the chunk length must be a positive multiple of {GUARD_BLOCK}, got {chunk}")
+    if any(c < 0 for c in numels):
+        raise ValueError("grad_guard_table: negative tensor size")
+    complement_ranges(zip(offsets, numels), n)        # raises on a slice that overlaps another or leaves [0, n)
+    if any(c > 0 and (o < 0 or o + c > n) for o, c in zip(offsets, numels)):
+        raise ValueError(f"grad_guard_table: a slice leaves the arena of {n}")
+    chunks, tensors, blocks = [], [], 0
+    for p, (off, cnt) in enumerate(zip(offsets, numels)):
+        first, nb = len(chunks), (cnt + GUARD_BLOCK - 1) // GUARD_BLOCK
+        chunks.extend((p, off + o, min(chunk, cnt - o)) for o in range(0, cnt, chunk))
+        tensors.append((first, len(chunks) - first, blocks, nb))
+        blocks += nb
+    if not chunks:
+        raise ValueError("grad_guard_table: every tensor is empty")
+    if blocks >= 2 ** 31 or len(chunks) >= 2 ** 31:
+        raise ValueError("grad_guard_table: the arena has too many blocks for the int32 table")
+    return np.asarray(chunks, dtype=np.int64).reshape(-1, 3), np.asarray(tensors, dtype=np.int32).reshape(-1, 4)
+
+
+def grad_guard_table(offsets, numels, n, device, chunk=GUARD_CHUNK) -> GuardTable:
+    """Device chunk table (and scratch) that drives grad_guard over the parameter tensors of an arena of n elements.
+    Allocates and uploads: build it once per optimizer, outside any stream capture."""
+    if torch.device(device).type == "cuda" and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("grad_guard_table: the chunk table cannot be built under stream capture")
+    ch, tn = grad_guard_chunks(offsets, numels, n, chunk)
+    nb = int(tn[:, 3].sum())
+    return GuardTable(torch.from_numpy(ch).to(device), torch.from_numpy(tn).to(device),
+                      torch.zeros(nb, dtype=torch.float64, device=device),
+                      torch.zeros(nb + tn.shape[0], dtype=torch.int32, device=device), int(n))
+
+
+def guard_record(device) -> torch.Tensor:
+    """a zeroed device edm_grad_guard_record (8 int64 words: 64 bytes, 8-byte aligned)"""
+    return torch.zeros(8, dtype=torch.int64, device=device)
+
+
+def read_guard_record(record) -> dict:
+    """the fields of a device guard record as Python numbers (one D2H copy, which waits for the stream)"""
+    r = np.frombuffer(record.cpu().numpy().tobytes(), dtype=GUARD_RECORD)[0]
+    return {k: r[k].item() for k in GUARD_RECORD.names if k != "pad"}
+
+
+def _guard_record_ptr(record):
+    if (not isinstance(record, torch.Tensor) or not record.is_cuda or not record.is_contiguous()
+            or record.numel() * record.element_size() < 64 or record.data_ptr() % 8):
+        raise ValueError("record: expected a contiguous, 8-byte-aligned device buffer of >= 64 bytes (ops.guard_record)")
+    return ctypes.c_void_p(record.data_ptr())
+
+
+def _guard_limit(x, name):
+    """None / inf: off"""
+    x = float("inf") if x is None else float(x)
+    if not x >= 0.0:
+        raise ValueError(f"grad_guard: {name} must be >= 0 (None or inf: off), got {x}")
+    return x
+
+
+def grad_guard(grad, table: GuardTable, sumsq, record, grad_scale=1.0, dyn=None, max_norm=None, clip_value=None,
+               skip_nonfinite=False, count=True):
+    """One reduction over the gradient arena `grad` (fp32, any 4-byte-aligned view): sumsq[p] = sum (g * grad_scale)^2 of
+    tensor p in fp64 and the device `record` (norm, clip coefficient, skip decision, counters) that adam_ema_guarded reads.
+    Fixed summation order: bit-identical from run to run and for any chunk length of the table.  Nothing is read back;
+    three launches on the current stream."""
+    _chk(grad, f32, "grad")
+    if grad.numel() != table.n:
+        raise ValueError(f"grad_guard: the table was built for an arena of {table.n} elements, grad has {grad.numel()}")
+    C, P, NB = table.chunks.shape[0], table.tensors.shape[0], table.part.shape[0]
+    _chk(table.chunks, torch.int64, "chunks", (C, 3))
+    _chk(table.tensors, torch.int32, "tensors", (P, 4))
+    _chk(table.part, torch.float64, "part", (NB,))
+    _chk(table.flags, torch.int32, "flags", (NB + P,))
+    _chk(sumsq, torch.float64, "sumsq", (P,))
+    for t in (table.chunks, table.tensors, table.part, table.flags, sumsq, record):
+        if t.device != grad.device:
+            raise ValueError(f"grad_guard: tables, sums and record must live on {grad.device}")
+    _lib.call("edm_grad_guard", _p(grad), grad.numel(), _p(table.chunks), C, _p(table.tensors), P, NB, float(grad_scale),
+              _dyn(dyn), _guard_limit(max_norm, "max_norm"), _guard_limit(clip_value, "clip_value"),
+              int(bool(skip_nonfinite)), int(bool(count)), _p(table.part), _p(table.flags), _p(sumsq),
+              _guard_record_ptr(record), _stream())
+
+
+def adam_ema_guarded(theta, grad, m, v, ema, record, lr, b1, b2, eps, step, ema_beta, grad_scale=1.0, dyn=None,
+                     zero_grad=False):
+    """adam_ema behind a grad_guard `record` of the same stream: gradient scale grad_scale * coef, each scaled element
+    limited to +-clip_value; a record with skip set leaves theta / m / v / ema bit for bit (grad is still cleared when
+    zero_grad, the health word is not touched)."""
+    for t, nme in ((theta, "theta"), (grad, "grad"), (m, "m"), (v, "v")):
+        _chk(t, f32, nme)
+        if t.numel() != theta.numel():
+            raise ValueError("adam_ema_guarded: arena size mismatch")
+    if ema is not None:
+        _chk(ema, f32, "ema")
+        if ema.numel() != theta.numel():
+            raise ValueError("adam_ema_guarded: arena size mismatch")
+    _lib.call("edm_adam_ema_guarded", _p(theta), _p(grad), _p(m), _p(v), _p(ema), theta.numel(), float(lr), float(b1),
+              float(b2), float(eps), int(step), float(ema_beta), float(grad_scale), _dyn(dyn), int(bool(zero_grad)),
+              _guard_record_ptr(record), _p(health(theta.device)), _stream())
+
+
+def adam_ema_phema_guarded(theta, grad, m, v, ema, profiles, betas, record, lr, b1, b2, eps, step, ema_beta,
+                           grad_scale=1.0, dyn=None, zero_grad=False):
+    """adam_ema_phema behind a grad_guard `record` (see adam_ema_guarded); a skipped step leaves the profiles alone too."""
+    for t, nme in ((theta, "theta"), (grad, "grad"), (m, "m"), (v, "v")):
+        _chk(t, f32, nme)
+        if t.numel() != theta.numel():
+            raise ValueError("adam_ema_phema_guarded: arena size mismatch")
+    if ema is not None:
+        _chk(ema, f32, "ema")
+        if ema.numel() != theta.numel():
+            raise ValueError("adam_ema_phema_guarded: arena size mismatch")
+    profiles = list(profiles)
+    K = len(profiles)
+    if not 1 <= K <= PHEMA_MAX_PROFILES:
+        raise ValueError(f"adam_ema_phema_guarded: 1 to {PHEMA_MAX_PROFILES} profiles, got {K}")
+    for k, p in enumerate(profiles):
+        _chk(p, f32, f"profiles[{k}]")
+        if p.numel() != theta.numel() or p.device != theta.device:
+            raise ValueError(f"adam_ema_phema_guarded: profiles[{k}] must be an arena of {theta.numel()} floats on {theta.device}")
+    _chk(betas, f32, "betas", (K,))
+    if betas.device != theta.device:
+        raise ValueError(f"adam_ema_phema_guarded: betas must live on {theta.device}")
+    ptrs = (ctypes.c_void_p * K)(*[p.data_ptr() for p in profiles])
+    _lib.call("edm_adam_ema_phema_guarded", _p(theta), _p(grad), _p(m), _p(v), _p(ema), ptrs, K, _p(betas), theta.numel(),
+              float(lr), float(b1), float(b2), float(eps), int(step), float(ema_beta), float(grad_scale), _dyn(dyn),
+              int(bool(zero_grad)), _guard_record_ptr(record), _p(health(theta.device)), _stream())
 
 
 def phema_accumulate(acc, snap, weights):

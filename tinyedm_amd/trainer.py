@@ -13,7 +13,7 @@ import torch
 import torch.distributed as dist
 
 from .ddp import GradReducer
-from .ema import EMAOptimizer, FusedAdam
+from .ema import EMAOptimizer, FusedAdam, MisconfigurationException
 
 
 class LightningModule(torch.nn.Module):
@@ -79,12 +79,33 @@ class _ConstLR:
 class Trainer:
     """``Trainer(max_epochs=, max_steps=, accumulate_grad_batches=, check_val_every_n_epoch=, callbacks=,
     devices=, accelerator=, strategy=, precision=, logger=)`` -- the kwargs of conf/*.yaml ``trainer:``.
-    ``precision`` is accepted for config compatibility: the HIP path always runs the bf16-mixed policy."""
+    ``precision`` is accepted for config compatibility: the HIP path always runs the bf16-mixed policy.
+
+    ``gradient_clip_val`` / ``gradient_clip_algorithm`` ("norm": the 2-norm of the whole gradient, "value": every
+    element) are Lightning's; ``skip_nonfinite_steps`` makes a step whose gradient holds a NaN or an infinity change
+    nothing.  All three act on the device through FusedAdam.set_guard, in the eager loop and in the hipGraph replay
+    alike.  The host does not know that a step was skipped: global_step, the Adam step count, the EMA step, the LR
+    schedule and the Philox step advance as on any other step, so later bias corrections are those of t + skips.
+    ``max_consecutive_skips`` skipped steps in a row end the run with GraphCorruptionError at the next health check."""
 
     def __init__(self, max_epochs: int = 1, max_steps: int = -1, accumulate_grad_batches: int = 1,
                  check_val_every_n_epoch: int = 1, callbacks: Optional[List[Any]] = None, devices: Any = 1,
                  accelerator: str = "gpu", strategy: str = "auto", precision: Any = "bf16-mixed", logger: Any = None,
-                 log_every_n_steps: int = 50, **_ignored):
+                 log_every_n_steps: int = 50, gradient_clip_val: Optional[float] = None,
+                 gradient_clip_algorithm: Optional[str] = "norm", skip_nonfinite_steps: bool = False,
+                 max_consecutive_skips: int = 10, **_ignored):
+        if gradient_clip_val is not None and not float(gradient_clip_val) >= 0.0:
+            raise ValueError(f"Trainer: gradient_clip_val must be >= 0, got {gradient_clip_val}")
+        gradient_clip_algorithm = "norm" if gradient_clip_algorithm is None else str(gradient_clip_algorithm).lower()
+        if gradient_clip_algorithm not in ("norm", "value"):
+            raise ValueError(f"Trainer: gradient_clip_algorithm must be 'norm' or 'value', got {gradient_clip_algorithm!r}")
+        if int(max_consecutive_skips) < 1:
+            raise ValueError(f"Trainer: max_consecutive_skips must be >= 1, got {max_consecutive_skips}")
+        # (Lightning: a gradient_clip_val of 0 means "no clipping")
+        self.gradient_clip_val = float(gradient_clip_val) if gradient_clip_val else None
+        self.gradient_clip_algorithm = gradient_clip_algorithm
+        self.skip_nonfinite_steps = bool(skip_nonfinite_steps)
+        self.max_consecutive_skips = int(max_consecutive_skips)
         self.max_epochs, self.max_steps = max_epochs, max_steps
         self.accumulate_grad_batches = accumulate_grad_batches
         self.check_val_every_n_epoch = check_val_every_n_epoch
@@ -195,6 +216,7 @@ class Trainer:
         opt = self.optimizers[0]
         base = opt.optimizer if isinstance(opt, EMAOptimizer) else opt
         model.train()
+        self._set_guard(base)
         if isinstance(base, FusedAdam):
             base.fuse_zero_grad = True        # step() is always followed by zero_grad() here
         opt.zero_grad()
@@ -257,11 +279,18 @@ class Trainer:
                     self.global_step += 1
                     if self.scheduler_interval == "step":
                         self.lr_scheduler.step()
+                    guard_line = ""
                     if self.global_step % self.log_every_n_steps == 0:
-                        self._check_health(model, loss)
+                        stats = self._guard_stats(base)
+                        self._check_health(model, loss, stats)
+                        if stats is not None:
+                            self.callback_metrics.update(grad_norm=stats["grad_norm"], grad_clip_coef=stats["clip_coef"],
+                                                         skipped_steps=stats["skipped_steps"])
+                            guard_line = (f" grad_norm {stats['grad_norm']:.4g} clip_coef {stats['clip_coef']:.4g} "
+                                          f"skipped {stats['skipped_steps']}")
                     if self.global_rank == 0 and self.global_step % self.log_every_n_steps == 0:
                         print(f"[fit] epoch {epoch} step {self.global_step} loss {float(loss.detach()):.4f} "
-                              f"{imgs / (time.time() - t0):.1f} img/s", flush=True)
+                              f"{imgs / (time.time() - t0):.1f} img/s{guard_line}", flush=True)
                     # Lightning's hook, here once per completed optimizer step (posthoc_ema.PostHocEMA writes its snapshots)
                     self._call("on_train_batch_end", model, loss, batch, bi)
                     if 0 < self.max_steps <= self.global_step:
@@ -290,14 +319,47 @@ class Trainer:
             self.reducer.close()              # hooks off the parameters, networks.W3_TAIL back (the next fit() builds its own)
         self._call("on_fit_end", model)
 
-    def _check_health(self, model, loss=None):
+    def _set_guard(self, base):
+        """gradient_clip_val / skip_nonfinite_steps -> FusedAdam.set_guard; with neither, a guard that the user or a callback set stays as it is"""
+        if self.gradient_clip_val is None and not self.skip_nonfinite_steps:
+            return
+        if not isinstance(base, FusedAdam):
+            raise MisconfigurationException("Trainer: gradient_clip_val / skip_nonfinite_steps act inside the fused "
+                                            f"optimizer kernel and need tinyedm_amd.FusedAdam, not {type(base).__name__}")
+        by_norm = self.gradient_clip_algorithm == "norm"
+        base.set_guard(max_norm=self.gradient_clip_val if by_norm else None,
+                       clip_value=None if by_norm else self.gradient_clip_val, skip_nonfinite=self.skip_nonfinite_steps)
+
+    @staticmethod
+    def _guard_stats(base):
+        """the guard's device record (one 64-byte read), or None without a guard"""
+        if not isinstance(base, FusedAdam) or base.guard is None or not torch.cuda.is_available():
+            return None
+        return base.guard_stats()
+
+    def _check_health(self, model, loss=None, guard_stats=None):
         """The sentinel of the (graph-replayed or eager) step: the optimizer kernel leaves a bit in the device health
         word when a non-finite gradient / weight went through it; read here, at the log interval and at epoch ends,
-        it turns a diverged or corrupted run into an exception instead of a checkpoint full of NaN."""
+        it turns a diverged or corrupted run into an exception instead of a checkpoint full of NaN.
+
+        With a guard that skips non-finite steps the guard's record is read at the same points: a non-finite loss of a
+        step the guard skipped is not an error (nothing was updated), `max_consecutive_skips` skips in a row are."""
         if not torch.cuda.is_available():
             return
         from . import ops
         ops.check_health(model.device, f"Trainer.fit (epoch {self.current_epoch}, step {self.global_step})")
+        opt = self.optimizers[0] if self.optimizers else None
+        base = opt.optimizer if isinstance(opt, EMAOptimizer) else opt
+        skipping = isinstance(base, FusedAdam) and base.guard is not None and base.guard.skip_nonfinite
+        if skipping:
+            st = guard_stats if guard_stats is not None else base.guard_stats()
+            if st["consecutive_skips"] >= self.max_consecutive_skips:
+                raise ops.GraphCorruptionError(
+                    f"Trainer.fit: the last {st['consecutive_skips']} optimizer steps were skipped for non-finite gradients "
+                    f"(max_consecutive_skips={self.max_consecutive_skips}) at step {self.global_step}; "
+                    f"{st['skipped_steps']} skipped in all")
+            if st["skipped_last"]:
+                return
         if loss is not None and not bool(torch.isfinite(loss.detach()).all()):
             raise ops.GraphCorruptionError(f"Trainer.fit: loss is not finite at step {self.global_step}")
 

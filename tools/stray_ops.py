@@ -1,6 +1,6 @@
 """Which torch (aten) kernels are still launched inside a training step, and from where: one eager step under torch.profiler
 with Python stacks; prints every aten op that launched a device kernel with the innermost frames of tinyedm_amd / bench code.
-    python tools/stray_ops.py"""
+    python tools/stray_ops.py [--guard]     (--guard: with a gradient guard set, FusedAdam.set_guard)"""
 import os
 import sys
 
@@ -18,6 +18,8 @@ model, cfg = bench.build_model(dev)
 model.train()
 base = model.configure_optimizers()["optimizer"]
 opt = EMAOptimizer(base, device=dev, gamma=tinyedm.sigma_rel_to_gamma(model.ema_length), every_n_steps=model.every_n_steps) if model.use_ema else base
+if "--guard" in sys.argv:
+    base.set_guard(max_norm=1.0, skip_nonfinite=True)
 red = GradReducer(base.arena)
 x = 0.5 * torch.randn(128, 3, 32, 32, device=dev)
 
