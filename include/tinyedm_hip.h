@@ -900,6 +900,20 @@ int edm_u8_knn_partial(const void* queries, const void* refs, long Q, long R, in
                        edm_stream_t stream);
 int edm_knn_merge(const unsigned long long* keys, int n_lists, long Q, int k, unsigned* dist, int* idx,
                   edm_stream_t stream);
+/* Ball membership counts on the same exact distance tile: the one operation that improved precision and recall
+ * (Kynkaanniemi et al. 2019, "Improved Precision and Recall Metric for Assessing Generative Models") and density and coverage
+ * (Naeem et al. 2020, "Reliable Fidelity and Diversity Metrics for Generative Models") need beyond a k-NN search; the
+ * reference has no call site for it.
+ * edm_u8_ball_count_partial: queries, refs, qnorms, rnorms, exclude_self, ref_base, splits and the two load paths as in
+ *   edm_u8_knn_partial; radii uint32 [R], one closed ball per REFERENCE row, any value up to 2^32 - 1 (d2 < 2^31 is compared
+ *   unsigned).  Writes counts int32 [splits][Q]: counts[s][q] = the number of references r in share s with
+ *   d2(q, r) <= radii[r], the reference with ref_base + r == q left out when exclude_self is set.  Every element is written
+ *   by an ordinary store, an empty share writes 0, and there are no atomics; the total is the caller's integer sum over the
+ *   shares (and over the chunks of a chunked call), so it depends on neither.  Limits, status -1 otherwise: 1 <= D <= 32768,
+ *   1 <= Q <= 65535 * 128, R >= 1, ref_base >= 0, ref_base + R <= 2^31 - 128, 1 <= splits <= 1024, no null pointers. */
+int edm_u8_ball_count_partial(const void* queries, const void* refs, long Q, long R, int D, const unsigned* radii,
+                              int exclude_self, long ref_base, int splits, const int* qnorms, const int* rnorms, int* counts,
+                              edm_stream_t stream);
 
 /* ---------------------------------------------------------------- ideal denoiser of a training set (csrc/ideal.hip) */
 /* D*(x; sigma) = sum_i w_i y_i with w = softmax_i(-|x - y_i|^2 / (2 sigma^2)) over the rows y_i = (u_i / 255 - mean) / std of

@@ -204,6 +204,7 @@ SIGNATURES = {
     "edm_u8_norms": [P, L, I, P, P],
     "edm_u8_knn_partial": [P, P, L, L, I, I, I, L, I, I, P, P, P, P],
     "edm_knn_merge": [P, I, L, I, P, P, P],
+    "edm_u8_ball_count_partial": [P, P, L, L, I, P, I, L, I, P, P, P, P],
     # ideal.hip
     "edm_ideal_begin": [P, P, P, I, L, I, F, F, P, P, P, P],
     "edm_ideal_logits": [P, P, P, P, L, L, I, F, F, P, L, P],

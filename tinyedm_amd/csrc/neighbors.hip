@@ -345,6 +345,143 @@ __global__ __launch_bounds__(64) void k_knn_merge(const u64* __restrict__ keys, 
   }
 }
 
+// Ball membership counts: counts[s][q] = the number of references r in share s of the 128-reference tiles with
+// d2(q, r) <= radii[r], a radius per REFERENCE (the k-NN radius of r inside its own set), which no top-k list can answer.
+// The distance tile is k_u8_knn's, step for step (same staging, swizzle, prefetch, fragments and MFMAs, through the same
+// helpers; its own copy of the K loop so that k_u8_knn's register allocation is not touched).  The epilogue is smaller: a lane
+// holds 16 query rows x 4 reference columns of a tile; each d2 is compared with its column's radius and the 0/1 results add
+// up in 16 per-lane registers (one per query row) that live across the share's tiles.  d2 < 2^31 but a radius may be anything
+// up to 2^32 - 1: the compare is UNSIGNED.  After the last tile the 16 lanes that hold a query row and the two waves that
+// share the query half meet in LDS (the staging area, free by then): red[128][32 (+1 pad)] ints, one thread per query sums
+// its 32 partial counts and stores one int.  Every counts[s][q], q < Q, is written by an ordinary store; an empty share writes
+// 0.  No atomics of any kind.
+constexpr int BALL_RED_STRIDE = 33;   // ints per query row of the final reduction: odd, so the 128 owners hit different banks
+static_assert(KNN_TILE * BALL_RED_STRIDE * 4 <= KNN_STAGE_BYTES, "the final reduction reuses the staging area");
+
+template <bool VEC>
+__global__ __launch_bounds__(256, 2) void k_u8_ball_count(const unsigned char* __restrict__ Qm,
+                                                        const unsigned char* __restrict__ Rm, const int* __restrict__ qn,
+                                                        const int* __restrict__ rn, const uint32_t* __restrict__ radii, int Q,
+                                                        int R, int D, int exclude_self, int ref_base, int* __restrict__ counts) {
+  __shared__ __attribute__((aligned(16))) char smem[KNN_STAGE_BYTES];
+  char* sA = smem;
+  char* sB = smem + KNN_TILE * KNN_BK;
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wq = (wave >> 1) * 64, wr = (wave & 1) * 64;   // the wave's 64 x 64 block inside the tile
+  const int l15 = lane & 15, lq = lane >> 4;
+  const int S = gridDim.x, s = blockIdx.x;   // this workgroup's share of the reference tiles
+  const int q0 = blockIdx.y * KNN_TILE;
+  const int n_rt = (R + KNN_TILE - 1) / KNN_TILE;
+  const int rt_lo = (int)((long)n_rt * s / S), rt_hi = (int)((long)n_rt * (s + 1) / S);
+
+  int cnt[4][4];   // [i][r]: query wq + 16 i + 4 lq + r, summed over this lane's reference columns of every tile so far
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) cnt[i][r] = 0;
+
+  const int n_kt = (D + KNN_BK - 1) / KNN_BK;
+  for (int rt = rt_lo; rt < rt_hi; ++rt) {
+    const int r0 = rt * KNN_TILE;
+    i32x4 acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = i32x4{0, 0, 0, 0};
+
+    // ---- the distance tile of k_u8_knn (see there for the staging, the prefetch and the fragment map)
+    const unsigned char* qbase = Qm + (long)q0 * D;
+    const unsigned char* rbase = Rm + (long)r0 * D;
+    u32x4 ra[4], rb[4];
+    auto fetch = [&](int kt) {
+#pragma unroll
+      for (int n = 0; n < 4; ++n) {
+        const int row = (tid >> 3) + 32 * n, c = tid & 7;
+        const int kb = kt * KNN_BK + c * 16;
+        const bool q_ok = q0 + row < Q, r_ok = r0 + row < R;   // (a missing row reads the tile's first row and is zeroed)
+        ra[n] = load_chunk_raw<VEC>(qbase + (unsigned)((q_ok ? row : 0) * D), kb, D, q_ok);
+        rb[n] = load_chunk_raw<VEC>(rbase + (unsigned)((r_ok ? row : 0) * D), kb, D, r_ok);
+      }
+    };
+    fetch(0);
+    for (int kt = 0; kt < n_kt; ++kt) {
+#pragma unroll
+      for (int n = 0; n < 4; ++n) {
+        const int id = tid + 256 * n, row = id >> 3, c = id & 7;
+        const int kb = kt * KNN_BK + c * 16;
+        *reinterpret_cast<u32x4*>(sA + stage_off(row, c)) = chunk_finish<VEC>(ra[n], kb, D, q0 + row < Q);
+        *reinterpret_cast<u32x4*>(sB + stage_off(row, c)) = chunk_finish<VEC>(rb[n], kb, D, r0 + row < R);
+      }
+      __syncthreads();
+      if (kt + 1 < n_kt) fetch(kt + 1);
+      i32x4 fa[2][4], fb[2][4];
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          fa[h][i] = *reinterpret_cast<const i32x4*>(sA + stage_off(wq + 16 * i + l15, 4 * h + lq));
+          fb[h][i] = *reinterpret_cast<const i32x4*>(sB + stage_off(wr + 16 * i + l15, 4 * h + lq));
+        }
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[h][i], fb[h][j], acc[i][j], 0, 0, 0);
+      __syncthreads();
+    }
+
+    // ---- membership: acc[i][j][r] is query wq + 16 i + 4 lq + r against reference wr + 16 j + l15
+    // (opaque copies of the lane coordinates, as in k_u8_knn: the norms, radii and row numbers are formed here, once per
+    // tile, and do not hold registers through the K loop)
+    int lq_c = lq, l15_c = l15, wq_c = wq, wr_c = wr;
+    asm volatile("" : "+v"(lq_c), "+v"(l15_c), "+v"(wq_c), "+v"(wr_c));
+    int rnorm[4], self_q[4];   // self_q: the query row that reference column j must skip (-1: none)
+    uint32_t rad[4];
+    bool col_ok[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int rr = r0 + wr_c + 16 * j + l15_c;
+      col_ok[j] = rr < R;
+      rnorm[j] = col_ok[j] ? rn[rr] : 0;
+      rad[j] = col_ok[j] ? radii[rr] : 0u;
+      self_q[j] = exclude_self ? ref_base + rr : -1;
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int q = q0 + wq_c + 16 * i + 4 * lq_c + r;
+        const bool row_ok = q < Q;
+        const int qnorm = row_ok ? qn[q] : 0;
+        int c = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const uint32_t d2 = (uint32_t)(qnorm + rnorm[j] - 2 * acc[i][j][r]);   // exact and < 2^31 for a real pair
+          c += (col_ok[j] && q != self_q[j] && d2 <= rad[j]) ? 1 : 0;           // unsigned: a radius may be >= 2^31
+        }
+        cnt[i][r] += row_ok ? c : 0;
+      }
+  }
+
+  // ---- the 16 lanes of a query row, and the two waves of a query half, meet in LDS.  The K loop ended with a barrier (and
+  // an empty share never touched the staging area), so the area is free.
+  int* red = reinterpret_cast<int*>(smem);
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) red[(wq + 16 * i + 4 * lq + r) * BALL_RED_STRIDE + (wave & 1) * 16 + l15] = cnt[i][r];
+  __syncthreads();
+  if (tid < KNN_TILE && q0 + tid < Q) {
+    int total = 0;
+#pragma unroll
+    for (int e = 0; e < 32; ++e) total += red[tid * BALL_RED_STRIDE + e];
+    counts[(long)s * Q + q0 + tid] = total;
+  }
+}
+
 constexpr long KNN_MAX_Q = 65535L * KNN_TILE;          // grid.y
 constexpr long KNN_MAX_INDEX = (1L << 31) - KNN_TILE;   // the last tile's row numbers (tile base + 127) stay in an int
 
@@ -417,6 +554,37 @@ extern "C" int edm_u8_knn_partial(const void* queries, const void* refs, long Q,
                        (int)ref_base, keys);
   }
   EDM_CHECK_LAUNCH("u8_knn_partial");
+  return EDM_OK;
+}
+
+// Ball membership counts (improved precision and recall, Kynkaanniemi et al. 2019; density and coverage, Naeem et al. 2020):
+// counts [splits][Q] int32, counts[s][q] = the number of references r in share s of the 128-reference tiles with
+// d2(q, r) <= radii[r] (closed balls, a radius per reference, uint32 [R], any value up to 2^32 - 1; the compare is unsigned).
+// queries, refs, qnorms, rnorms, exclude_self, ref_base and splits as in edm_u8_knn_partial, with the same two load paths.
+// Every element of counts is written by an ordinary store (an empty share writes 0); the caller adds the shares, an integer
+// sum, so that neither splits nor chunking can change the total.  Limits (status -1 otherwise): 1 <= Q <= 65535 * 128,
+// 1 <= D <= 32768, R >= 1, ref_base >= 0, ref_base + R <= 2^31 - 128, 1 <= splits <= 1024.
+extern "C" int edm_u8_ball_count_partial(const void* queries, const void* refs, long Q, long R, int D, const unsigned* radii,
+                                         int exclude_self, long ref_base, int splits, const int* qnorms, const int* rnorms,
+                                         int* counts, hipStream_t st) {
+  EDM_REQUIRE(queries && refs && radii && qnorms && rnorms && counts, "u8_ball_count_partial: null pointer");
+  EDM_REQUIRE(Q >= 1 && Q <= KNN_MAX_Q, "u8_ball_count_partial: Q must be in [1, %ld], got %ld", KNN_MAX_Q, Q);
+  EDM_REQUIRE(D >= 1 && D <= KNN_MAX_D, "u8_ball_count_partial: D must be in [1, %d], got %d", KNN_MAX_D, D);
+  EDM_REQUIRE(R >= 1 && ref_base >= 0 && ref_base + R <= KNN_MAX_INDEX,
+              "u8_ball_count_partial: need R >= 1 and ref_base + R <= 2^31 - 128, got R = %ld, ref_base = %ld", R, ref_base);
+  EDM_REQUIRE(splits >= 1 && splits <= KNN_MAX_SPLITS, "u8_ball_count_partial: splits must be in [1, %d], got %d",
+              KNN_MAX_SPLITS, splits);
+  const bool vec = D % 16 == 0 && ((uintptr_t)queries & 15) == 0 && ((uintptr_t)refs & 15) == 0;
+  const unsigned char* q = (const unsigned char*)queries;
+  const unsigned char* r = (const unsigned char*)refs;
+  const dim3 grid((unsigned)splits, (unsigned)((Q + KNN_TILE - 1) / KNN_TILE));
+  if (vec)
+    hipLaunchKernelGGL(k_u8_ball_count<true>, grid, dim3(256), 0, st, q, r, qnorms, rnorms, radii, (int)Q, (int)R, D,
+                       exclude_self, (int)ref_base, counts);
+  else
+    hipLaunchKernelGGL(k_u8_ball_count<false>, grid, dim3(256), 0, st, q, r, qnorms, rnorms, radii, (int)Q, (int)R, D,
+                       exclude_self, (int)ref_base, counts);
+  EDM_CHECK_LAUNCH("u8_ball_count_partial");
   return EDM_OK;
 }
 

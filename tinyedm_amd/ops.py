@@ -3370,6 +3370,60 @@ def u8_knn(queries, refs, k, exclude_self=False, splits=None, *, ref_chunk=None,
     return (dist, idx) if out is not None else (dist.to(torch.int64), idx.to(torch.int64))
 
 
+def ball_radii_u32(radii, R):
+    """radii: an int64 or uint32 tensor [R] with values in [0, 2^32 - 1] -> uint32 [R], contiguous (u8_ball_count's check)"""
+    if not isinstance(radii, torch.Tensor) or radii.dtype not in (torch.int64, torch.uint32):
+        raise ValueError(f"u8_ball_count: radii must be an int64 or uint32 tensor, got "
+                         f"{radii.dtype if isinstance(radii, torch.Tensor) else type(radii).__name__}")
+    if tuple(radii.shape) != (R,):
+        raise ValueError(f"u8_ball_count: radii must have shape ({R},), one per reference, got {tuple(radii.shape)}")
+    if radii.dtype == torch.int64:
+        if bool(((radii < 0) | (radii > 0xFFFFFFFF)).any()):
+            raise ValueError("u8_ball_count: radii must lie in [0, 2^32 - 1]")
+        radii = radii.to(torch.uint32)          # (the low 32 bits: exact in that range)
+    return radii.contiguous()
+
+
+def u8_ball_count(queries, refs, radii, exclude_self=False, splits=None, *, ref_chunk=None):
+    """For every row of queries (uint8 [Q, ...]) the number of rows r of refs (uint8 [R, ...], same trailing shape; inputs of
+    any rank >= 2 are taken as [N, D]) whose closed ball holds it: d2(q, r) <= radii[r], d2 the exact squared pixel distance
+    -> int64 [Q].  radii: int64 or uint32 [R] in [0, 2^32 - 1], one per reference.  exclude_self: refs is the query set
+    itself and row i does not count for itself.  splits and ref_chunk as in u8_knn: every share of every chunk writes its
+    own int32 counts and one integer sum folds them, so the result depends on neither."""
+    q2, r2 = _knn_rows(queries, "queries"), _knn_rows(refs, "refs")
+    if queries.shape[1:] != refs.shape[1:]:
+        raise ValueError(f"u8_ball_count: queries {tuple(queries.shape[1:])} and refs {tuple(refs.shape[1:])} differ in shape")
+    if refs.device != queries.device:
+        raise ValueError(f"u8_ball_count: queries on {queries.device}, refs on {refs.device}")
+    (Q, D), R = q2.shape, r2.shape[0]
+    knn_check(Q, R, D, 1)                        # the limits on Q, R and D are those of a k = 1 search
+    if not isinstance(radii, torch.Tensor) or radii.device != refs.device:
+        raise ValueError(f"u8_ball_count: radii must be a tensor on {refs.device}")
+    rad = ball_radii_u32(radii, R)
+    if ref_chunk is not None and (isinstance(ref_chunk, bool) or not isinstance(ref_chunk, int) or ref_chunk < 1):
+        raise ValueError(f"u8_ball_count: ref_chunk must be None or an integer >= 1, got {ref_chunk!r}")
+    chunk = R if ref_chunk is None else min(ref_chunk, R)
+    bounds = [(a, min(a + chunk, R)) for a in range(0, R, chunk)]
+    if splits is None:
+        shares = [u8_knn_splits(Q, b - a) for a, b in bounds]
+    elif isinstance(splits, bool) or not isinstance(splits, int) or not 1 <= splits <= KNN_MAX_SPLITS:
+        raise ValueError(f"u8_ball_count: splits must be an integer in [1, {KNN_MAX_SPLITS}], got {splits!r}")
+    else:
+        shares = [splits] * len(bounds)
+    dev = queries.device
+    norms = torch.empty(Q + R, dtype=torch.int32, device=dev)
+    qn, rn = norms[:Q], norms[Q:]
+    _lib.call("edm_u8_norms", _p(q2), Q, D, _p(qn), _stream())
+    _lib.call("edm_u8_norms", _p(r2), R, D, _p(rn), _stream())
+    counts = torch.empty(sum(shares), Q, dtype=torch.int32, device=dev)
+    at = 0
+    for (a, b), s in zip(bounds, shares):
+        _lib.call("edm_u8_ball_count_partial", _p(q2), _p(r2[a:b]), Q, b - a, D, _p(rad[a:b]), int(bool(exclude_self)), a, s,
+                  _p(qn), _p(rn[a:b]), _p(counts[at:at + s]), _stream())
+        at += s
+    return counts.sum(0, dtype=torch.int64)
+
+
 # ------------------------------------------------------------------ ideal denoiser of a training set (csrc/ideal.hip)
 IDEAL_MAX_K = 32768              # elements per image (edm_u8_norms' limit: |u - 128|^2 summed in an int)
 IDEAL_MAX_Q = 65535 * 64         # one grid row per 64 queries
