@@ -772,6 +772,41 @@ int edm_adapt_control(const double* part, int B, long CHW, float t_end, double s
                       edm_stream_t stream);
 int edm_adapt_commit(float* x, const float* y, const unsigned char* accept, int B, long CHW, edm_stream_t stream);
 
+/* ---------------------------------------------------------------- parallel-in-time sampling (picard.hip)
+ * Picard iteration of the Heun / Euler step over a window of P <= EDM_PICARD_MAX_WINDOW consecutive steps of a sigma
+ * table t_0 .. t_{N-1} (N >= 2), every sample with its own window start s_b; the hot path reads nothing on the host.
+ * Window position j = 0 .. P of sample b stands at table index s_b + j: position 0 is converged, the next
+ * L_b = min(P, N - 1 - s_b) are live, the rest are inactive.  Position-major buffers: X, Xnew fp32 [P + 1][B][CHW]; dx,
+ * X1, D, D1 fp32 [P][B][CHW] (row j: the Euler stage / network outputs of position j); T fp32 [P + 1][B],
+ * T[j][b] = t[min(s_b + j, N - 1)].
+ * state: DEVICE, EDM_PICARD_ROWS rows of B 32-bit words: 0 start (s_b), 1 status (0 active, 1 done), 2 iterations.
+ * edm_picard_scan: new_0 = X[0]; new_{j+1} = fma(t1 - t0, 0.5 dx_j + 0.5 (X1_j - D1_j) / t1, new_j) (D1 == NULL: the
+ *   Euler iteration fma(t1 - t0, dx_j, new_j)) for the live j, with edm_heun_correct's / edm_heun_euler's bits where
+ *   new_j == X[j]; inactive positions copy new_L and nothing of theirs but X is read.  part[b][j][chunk] (DEVICE doubles
+ *   [B][P][chunks], chunks = min(ceil(ceil(CHW / 4) / 256), EDM_NLL_MAX_CHUNKS)) = the chunk's share of
+ *   sum ((new - old) / (atol + rtol max(|old|, |new|)))^2 over position j + 1, fp64, order-fixed as edm_adapt_correct's (a
+ *   zero scale contributes 0 where new == old and +inf otherwise); 0 for an inactive position.  tol: DEVICE doubles
+ *   {atol, rtol}, both >= 0 (both 0: converged = unchanged bit for bit).  Health bit of the Heun updates on a non-finite
+ *   live state.  dwordx4 when CHW % 4 == 0 and the buffers are 16-byte aligned, the same bits otherwise.  B <= 65535.
+ * edm_picard_control: one thread per ACTIVE sample, fp64: E_j = sqrt(sum_chunks part[b][j-1][.] / CHW) in index order for
+ *   j = 1 .. L_b (written to err[b][j-1] when err != NULL); m = the leading positions with E_j <= 1 (NaN: not converged);
+ *   stride[b] = min(m + 1, L_b) (0 for a sample that was not active); s_b += stride, iterations++, done when
+ *   s_b == N - 1.  active: DEVICE int32, += the number of samples still active.
+ * edm_picard_slide: X[j] = Xnew[j + r] while j + r <= L (r = stride[b], L the live length before the slide, the state
+ *   already advanced); a position entering at table index i <= N - 1 gets fma(Xnew[L] - Dh, t_i / t_{s+L}, Dh) with
+ *   Dh = D[L-1]; indices past N - 1 copy Xnew[L]; T is rewritten.  X must not alias Xnew.  begin != 0: Xnew is the unit
+ *   noise [B][CHW]; X[j] = t_j * Xnew (copies of X[0] past N - 1), T and the state (s = 0, active, 0 iterations) are
+ *   written; D and stride are not read.  t_table: DEVICE fp32, >= N entries. */
+#define EDM_PICARD_ROWS 3
+#define EDM_PICARD_MAX_WINDOW 64
+int edm_picard_scan(const float* X, const float* dx, const float* X1, const float* D1, const float* T, const void* state,
+                    const double* tol, int B, int N, int P, long CHW, float* Xnew, double* part, unsigned* health,
+                    edm_stream_t stream);
+int edm_picard_control(const double* part, int B, long CHW, int N, int P, void* state, int* stride, double* err,
+                       int* active, edm_stream_t stream);
+int edm_picard_slide(const float* Xnew, const float* D, const int* stride, void* state, const float* t_table, int begin,
+                     int B, int N, int P, long CHW, float* X, float* T, edm_stream_t stream);
+
 /* ---------------------------------------------------------------- reference-precision evaluation (eval_f32.hip)
  * The reference samples / validates in fp32 (generate.py:39-44, callbacks.py:41-49, solvers.py:43-59).  These entry
  * points are the exact-fp32 forward: NHWC fp32 activations [pixels][channels], fp32 effective weights (the w_hat arrays

@@ -10,11 +10,12 @@ from .ideal import IdealDenoiser
 from .metric import WeightedMeanSquaredError
 from .networks import Conv2d, Denoiser, DenoiserWrapper, Embedding, Linear, manual_seed
 from .prdc import ManifoldMetrics
-from .solvers import AdaptiveSolver, DeterministicSolver, GaussianBlur, LinearDegradation, MultistepSolver, StochasticSolver
+from .solvers import (AdaptiveSolver, DeterministicSolver, GaussianBlur, LinearDegradation, MultistepSolver,
+                      ParallelSolver, ParallelStats, StochasticSolver)
 from .trainer import LightningModule, Trainer
 from .vjp import input_vjp
 from . import config, networks, ops
 
-__all__ = ["EDM", "Diffuser", "DeterministicSolver", "StochasticSolver", "MultistepSolver", "AdaptiveSolver", "LinearDegradation", "GaussianBlur", "input_vjp", "IdealDenoiser", "ManifoldMetrics", "WeightedMeanSquaredError", "Denoiser", "Linear", "Conv2d",
+__all__ = ["EDM", "Diffuser", "DeterministicSolver", "StochasticSolver", "MultistepSolver", "AdaptiveSolver", "ParallelSolver", "ParallelStats", "LinearDegradation", "GaussianBlur", "input_vjp", "IdealDenoiser", "ManifoldMetrics", "WeightedMeanSquaredError", "Denoiser", "Linear", "Conv2d",
            "Embedding", "DenoiserWrapper", "EMA", "EMAOptimizer", "FusedAdam", "Trainer", "LightningModule",
            "sigma_rel_to_gamma", "manual_seed", "config", "networks", "ops"]

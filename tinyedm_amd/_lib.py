@@ -155,6 +155,10 @@ SIGNATURES = {
     "edm_adapt_correct": [P, P, P, P, P, P, I, L, D, D, P, P, P, P],
     "edm_adapt_control": [P, I, L, F, D, D, D, D, P, P, P, P, P],
     "edm_adapt_commit": [P, P, P, I, L, P],
+    # picard.hip
+    "edm_picard_scan": [P, P, P, P, P, P, P, I, I, I, L, P, P, P, P],
+    "edm_picard_control": [P, I, L, I, I, P, P, P, P, P],
+    "edm_picard_slide": [P, P, P, P, P, I, I, I, I, L, P, P, P],
     # restore.hip
     "edm_degrade": [P, P, I, I, I, I, I, I, P],
     "edm_project_denoised": [P, P, P, P, P, I, I, I, I, I, I, P, P],

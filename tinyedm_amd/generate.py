@@ -51,6 +51,17 @@ latents then close the loop with an adaptive solve); `--guidance_interval`, `--S
 
     python -m tinyedm.generate --ckpt_path last.ckpt --load_ema --solver dpmpp --solver_order 2 --num_steps 32 \\
         --output_dir samples --num_samples 50000 --image_size 32 --num_classes 10 --batch_size 512
+Parallel-in-time sampling (ParallelSolver; ParaDiGMS, Shih et al. 2023): `--solver picard` holds `--window P` (16)
+consecutive steps of the table as unknowns, evaluates the network at all of them in one batch of P x batch_size rows
+and iterates until they move by less than `--rtol` (1e-3) / `--atol` (1e-4): the Heun table solve (`--solver_order 1`:
+Euler) at a sequential depth of 2 x iterations + 1 network calls instead of 2N - 1, for a few images at a time.
+`--rtol 0 --atol 0` iterates to the fixed point itself.  `--solver_report FILE.json` records {"iterations": per batch,
+"per_sample_iterations", "evaluations", "rows", "sequential_evaluations", ...}.  It combines with `--guidance`,
+`--guide_unconditional` / a guide network and the captured graph; the flags `--solver adaptive` refuses, `--init_dir`,
+`--invert_to`, `--S_churn` and `--solver_order 3` are errors.
+
+    python -m tinyedm.generate --ckpt_path last.ckpt --load_ema --solver picard --window 16 --num_steps 32 \\
+        --output_dir samples --num_samples 4 --image_size 32 --num_classes 10 --batch_size 4
 Image-conditioned sampling: `--init_dir DIR` reads PNGs as this program writes them (`<index>.png`, taken in numeric order
 of the index, normalised with `--mean/--std`), one per sample.  `--start_step K` (SDEdit / image-to-image) noises each
 image to sigma_K of the table and solves from there.  `--mask_box X0 Y0 X1 Y1` (inpainting) regenerates the pixels with
@@ -118,9 +129,9 @@ CIFAR_STD = (0.24703223, 0.24348513, 0.26158784)
 
 def _check_solver(solver, S_churn) -> None:
     """the sampler choices that need nothing loaded: checked before any checkpoint or network is"""
-    if solver not in ("heun", "dpmpp", "adaptive"):
-        raise ValueError(f"generate: solver must be 'heun', 'dpmpp' or 'adaptive', got {solver!r}")
-    if solver in ("dpmpp", "adaptive") and float(S_churn) != 0.0:
+    if solver not in ("heun", "dpmpp", "adaptive", "picard"):
+        raise ValueError(f"generate: solver must be 'heun', 'dpmpp', 'adaptive' or 'picard', got {solver!r}")
+    if solver in ("dpmpp", "adaptive", "picard") and float(S_churn) != 0.0:
         raise ValueError(f"generate: --solver {solver} is deterministic; --S_churn must be 0, got {S_churn} (stochastic "
                          "sampling is --solver heun)")
 
@@ -174,11 +185,14 @@ def _check_adaptive(solver, guidance_interval, init_dir, start_step, mask_box, i
                     restore_scale, restore_gray, dps_scale, rtol, atol, max_iterations, solver_report) -> None:
     """the choices of --solver adaptive that need nothing loaded"""
     import math
+    if solver == "picard":          # (_check_picard has these flags)
+        return
     if solver != "adaptive":
         for flag, on in (("--rtol", rtol is not None), ("--atol", atol is not None),
                          ("--max_iterations", max_iterations is not None), ("--solver_report", solver_report is not None)):
             if on:
-                raise ValueError(f"generate: {flag} needs --solver adaptive")
+                raise ValueError(f"generate: {flag} needs --solver adaptive" + (
+                    "" if flag == "--max_iterations" else " or --solver picard"))
         return
     for flag, on in (("--guidance_interval", guidance_interval is not None), ("--mask_box", mask_box is not None),
                      ("--restore_scale / --restore_gray", restore_scale != 1 or bool(restore_gray)),
@@ -196,6 +210,32 @@ def _check_adaptive(solver, guidance_interval, init_dir, start_step, mask_box, i
     if max_iterations is not None and (isinstance(max_iterations, bool) or not isinstance(max_iterations, int) or
                                        max_iterations < 1):
         raise ValueError(f"generate: --max_iterations must be an integer >= 1, got {max_iterations!r}")
+
+
+def _check_picard(solver, guidance_interval, init_dir, start_step, mask_box, invert_to, likelihood_to, restore_scale,
+                  restore_gray, dps_scale, S_churn, rtol, atol, max_iterations, window, solver_order) -> None:
+    """the choices of --solver picard that need nothing loaded"""
+    import math
+    if solver != "picard":
+        if window is not None:
+            raise ValueError("generate: --window needs --solver picard")
+        return
+    for flag, on in (("--guidance_interval", guidance_interval is not None), ("--mask_box", mask_box is not None),
+                     ("--restore_scale / --restore_gray", restore_scale != 1 or bool(restore_gray)),
+                     ("--dps_scale", dps_scale is not None), ("--likelihood_to", likelihood_to is not None),
+                     ("--invert_to", invert_to is not None), ("--start_step", start_step != 0),
+                     ("--init_dir", init_dir is not None), ("--S_churn", float(S_churn) != 0.0),
+                     ("--max_iterations", max_iterations is not None)):
+        if on:
+            raise ValueError(f"generate: --solver picard does not take {flag} (it iterates the plain table solve over a "
+                             "window of steps); use --solver heun")
+    for flag, v in (("--rtol", rtol), ("--atol", atol)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0):
+            raise ValueError(f"generate: {flag} must be a finite number >= 0, got {v!r}")
+    if window is not None and (isinstance(window, bool) or not isinstance(window, int) or not 1 <= window <= 64):
+        raise ValueError(f"generate: --window must be an integer in 1 .. 64, got {window!r}")
+    if isinstance(solver_order, bool) or solver_order not in (1, 2):
+        raise ValueError(f"generate: --solver picard takes --solver_order 1 (Euler) or 2 (Heun), got {solver_order!r}")
 
 
 def _check_labels_to(labels_to, init_dir) -> None:
@@ -299,12 +339,14 @@ def load_images(init_dir, mean, std, image_size, channels) -> torch.Tensor:
 def _validate(*, solver, S_churn, init_dir, start_step, num_steps, mask_box, invert_to, likelihood_to, network_dtype,
               num_probes, dequantize, image_size, dps_scale, blur_std, blur_radius, measurement_noise, restore_scale,
               restore_gray, save_degraded, restore_report, labels_to, guided, guidance_interval=None, rtol=None, atol=None,
-              max_iterations=None, solver_report=None) -> tuple:
+              max_iterations=None, solver_report=None, window=None, solver_order=2) -> tuple:
     """every choice that needs nothing loaded, checked once and in one order for generate() and the command line; returns
     (posterior, restoring): whether the run samples with DPS, and whether it restores (DDNM or DPS)"""
     _check_solver(solver, S_churn)
     _check_adaptive(solver, guidance_interval, init_dir, start_step, mask_box, invert_to, likelihood_to,
                     restore_scale, restore_gray, dps_scale, rtol, atol, max_iterations, solver_report)
+    _check_picard(solver, guidance_interval, init_dir, start_step, mask_box, invert_to, likelihood_to, restore_scale,
+                  restore_gray, dps_scale, S_churn, rtol, atol, max_iterations, window, solver_order)
     _check_conditioning(init_dir, start_step, mask_box, invert_to, solver, S_churn, image_size,
                         likelihood_to=likelihood_to, network_dtype=network_dtype, num_probes=num_probes,
                         dequantize=dequantize)
@@ -412,6 +454,16 @@ def _run_restore(model, datamodule, op, solve_kw, noise, rank_seed, back, stat, 
     print(f"[rank {where[0]}] wrote the {what} {where[1]} to {output_dir}", flush=True)
 
 
+def _picard_report(stats, solver, first) -> dict:
+    """--solver_report of --solver picard: the ParallelStats of every solve, in batch order, and the totals"""
+    per_sample = [int(v) for s in stats for v in s.per_sample_iterations]
+    return {"per_sample_iterations": per_sample, "iterations": [s.iterations for s in stats],
+            "evaluations": sum(s.evaluations for s in stats), "guide_evaluations": sum(s.guide_evaluations for s in stats),
+            "rows": sum(s.rows for s in stats), "sequential_evaluations": sum(s.sequential_evaluations for s in stats),
+            "window": solver.window, "order": solver.order, "rtol": solver.rtol, "atol": solver.atol, "first_index": first,
+            "num_images": len(per_sample)}
+
+
 def _solver_report(stats, solver, first) -> dict:
     """--solver_report: per image the accepted and rejected steps of the adaptive solver, per batch its iterations, and
     the totals (``stats``: the AdaptiveStats of every solve, in batch order)"""
@@ -445,13 +497,13 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
              solver_order=2, init_dir=None, start_step=0, mask_box=None, invert_to=None, likelihood_to=None,
              num_probes=1, dequantize=False, restore_scale=1, restore_gray=False, save_degraded=None,
              restore_report=None, labels_to=None, dps_scale=None, blur_std=None, blur_radius=2,
-             measurement_noise=0.0, rtol=None, atol=None, max_iterations=None, solver_report=None) -> None:
+             measurement_noise=0.0, rtol=None, atol=None, max_iterations=None, solver_report=None, window=None) -> None:
     from . import _runtime_env
     from .callbacks import PreditionWriter
     from .datamodules import RandomNoiseDataModule
     from .edm import EDM
     from .solvers import (AdaptiveSolver, DeterministicSolver, GaussianBlur, LinearDegradation, MultistepSolver,
-                          StochasticSolver)
+                          ParallelSolver, StochasticSolver)
 
     posterior, restoring = _validate(
         solver=solver, S_churn=S_churn, init_dir=init_dir, start_step=start_step, num_steps=num_steps, mask_box=mask_box,
@@ -460,7 +512,7 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
         measurement_noise=measurement_noise, restore_scale=restore_scale, restore_gray=restore_gray,
         save_degraded=save_degraded, restore_report=restore_report, labels_to=labels_to,
         guided=guide is not None or guide_ckpt_path is not None, guidance_interval=guidance_interval, rtol=rtol, atol=atol,
-        max_iterations=max_iterations, solver_report=solver_report)
+        max_iterations=max_iterations, solver_report=solver_report, window=window, solver_order=solver_order)
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -496,6 +548,15 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
                 adaptive_stats.append(model.solver.last_stats)
                 return out
             setattr(model.solver, name, recorded)
+    elif solver == "picard":
+        tol = {k: v for k, v in (("rtol", rtol), ("atol", atol), ("window", window)) if v is not None}
+        model.solver = ParallelSolver(**common, order=solver_order, **tol)
+
+        def recorded(*a, _run=model.solver.solve, **kw):        # every solve's statistics, for --solver_report
+            out = _run(*a, **kw)
+            adaptive_stats.append(model.solver.last_stats)
+            return out
+        model.solver.solve = recorded
     elif solver == "dpmpp":
         model.solver = MultistepSolver(order=solver_order, **common)
     elif float(S_churn) != 0.0:     # (a negative or non-finite S_churn reaches the solver's validation)
@@ -558,7 +619,8 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
             _drawn_labels, batch_size, num_workers, image_size, num_samples, num_classes, C, seed, world)
         _run_sample(model, datamodule, writer(output_dir), n_local, where, output_dir, labels_to, labels, num_samples)
     if solver_report is not None:
-        _write_json(_rank_path(solver_report, rank, world), _solver_report(adaptive_stats, model.solver, first))
+        report = _picard_report if solver == "picard" else _solver_report
+        _write_json(_rank_path(solver_report, rank, world), report(adaptive_stats, model.solver, first))
         print(f"[rank {rank}] wrote the step counts of images {where[1]} to {_rank_path(solver_report, rank, world)}",
               flush=True)
 
@@ -605,19 +667,25 @@ def main(argv=None):
     parser.add_argument("--S_max", type=float, default=float("inf"), help="churn only steps with t_i <= S_max (default inf)")
     parser.add_argument("--S_noise", type=float, default=1.0, help="scale of the churn noise (default 1)")
     # multistep sampling
-    parser.add_argument("--solver", choices=["heun", "dpmpp", "adaptive"], default="heun",
+    parser.add_argument("--solver", choices=["heun", "dpmpp", "adaptive", "picard"], default="heun",
                         help="heun (default): EDM's 2nd-order Heun, 2N-1 network evaluations; dpmpp: DPM-Solver++ "
                              "multistep, N evaluations; adaptive: Heun/Euler pair with per-sample step control to "
-                             "--rtol / --atol")
+                             "--rtol / --atol; picard: the Heun (or Euler) table solve iterated in parallel over a "
+                             "--window of steps until it moves by less than --rtol / --atol")
     parser.add_argument("--solver_order", type=int, choices=[1, 2, 3], default=2,
-                        help="order of --solver dpmpp (default 2: DPM-Solver++(2M))")
+                        help="order of --solver dpmpp (default 2: DPM-Solver++(2M)); --solver picard: 2 (Heun, default) "
+                             "or 1 (Euler)")
+    parser.add_argument("--window", type=int, default=None, metavar="P",
+                        help="--solver picard: the table steps iterated at once, 1 .. 64 (default 16); the network "
+                             "batch is P times --batch_size")
     # adaptive sampling
-    parser.add_argument("--rtol", type=float, default=None, help="--solver adaptive: relative tolerance (default 1e-3)")
-    parser.add_argument("--atol", type=float, default=None, help="--solver adaptive: absolute tolerance (default 1e-4)")
+    parser.add_argument("--rtol", type=float, default=None, help="--solver adaptive / picard: relative tolerance (default 1e-3)")
+    parser.add_argument("--atol", type=float, default=None, help="--solver adaptive / picard: absolute tolerance (default 1e-4)")
     parser.add_argument("--max_iterations", type=int, default=None,
                         help="--solver adaptive: controlled steps before the solve gives up (default 1024)")
     parser.add_argument("--solver_report", type=str, default=None, metavar="FILE.json",
-                        help="--solver adaptive: write the accepted and rejected steps of every image and the totals")
+                        help="--solver adaptive: write the accepted and rejected steps of every image and the totals; "
+                             "--solver picard: the iterations, evaluations and network rows")
     # image-conditioned sampling
     parser.add_argument("--init_dir", type=str, default=None,
                         help="directory of <index>.png images to start from (as this program writes them)")
@@ -702,7 +770,8 @@ def main(argv=None):
              restore_scale=args.restore_scale, restore_gray=args.restore_gray, save_degraded=args.save_degraded,
              restore_report=args.restore_report, labels_to=args.labels_to, dps_scale=args.dps_scale,
              blur_std=args.blur_std, blur_radius=args.blur_radius, measurement_noise=args.measurement_noise,
-             rtol=args.rtol, atol=args.atol, max_iterations=args.max_iterations, solver_report=args.solver_report)
+             rtol=args.rtol, atol=args.atol, max_iterations=args.max_iterations, solver_report=args.solver_report,
+             window=args.window)
 
 
 if __name__ == "__main__":

@@ -2865,6 +2865,186 @@ def adapt_commit(x, y, accept):
     return x
 
 
+# ------------------------------------------------------------------ parallel-in-time sampling (csrc/picard.hip)
+PICARD_ROWS = 3                 # EDM_PICARD_ROWS: 32-bit words of per-sample state of the parallel solver
+PICARD_MAX_WINDOW = 64          # EDM_PICARD_MAX_WINDOW
+PICARD_ACTIVE, PICARD_DONE = 0, 1
+
+
+class PicardRows(types.SimpleNamespace):
+    """the rows of a parallel solver's device state as [B] int32 views that share its memory: start (the table index of
+    window position 0), status, iterations"""
+
+
+def picard_rows(state) -> PicardRows:
+    _picard_state(state, 0, None)
+    return PicardRows(start=state[0], status=state[1], iterations=state[2])
+
+
+def _picard_state(state, B, device):
+    _chk_eval(state, torch.int32, "state", None, device)
+    if state.dim() != 2 or state.shape[0] != PICARD_ROWS or state.shape[1] < 1 or (B and state.shape[1] != B):
+        raise ValueError(f"state: expected an int32 [{PICARD_ROWS}, {B or 'B'}] tensor (ops.picard_begin), got "
+                         f"{tuple(state.shape)}")
+
+
+def _picard_dims(who, N, P):
+    if isinstance(N, bool) or not isinstance(N, int) or N < 2:
+        raise ValueError(f"{who}: N (the table's steps) must be an integer >= 2, got {N!r}")
+    if isinstance(P, bool) or not isinstance(P, int) or not 1 <= P <= PICARD_MAX_WINDOW:
+        raise ValueError(f"{who}: the window must be an integer in 1 .. {PICARD_MAX_WINDOW}, got {P!r}")
+
+
+def _picard_window(X, name="X"):
+    """(P, B, CHW) of a window buffer [P + 1, B, ...]"""
+    _chk_eval(X, f32, name)
+    if X.dim() < 3 or X.shape[0] < 2 or X.numel() == 0:
+        raise ValueError(f"{name}: expected a non-empty [P + 1, B, ...] window buffer, got {tuple(X.shape)}")
+    P, B = X.shape[0] - 1, X.shape[1]
+    if B > 65535:
+        raise ValueError(f"{name}: at most 65535 samples per call, got {B}")
+    return P, B, X.numel() // (X.shape[0] * B)
+
+
+def _picard_rows_of(v, name, P, B, CHW, device):
+    """a [P][B][CHW] operand, in whatever shape (the [P * B, C, H, W] of a network batch, for one)"""
+    _chk_eval(v, f32, name, None, device)
+    if v.numel() != P * B * CHW:
+        raise ValueError(f"{name}: expected {P} x {B} rows of {CHW} elements, got {tuple(v.shape)}")
+
+
+def picard_chunks(CHW: int) -> int:
+    """how many partials per window position a sample of CHW elements fills (a function of CHW alone; = adapt_chunks)"""
+    return adapt_chunks(CHW)
+
+
+def picard_tol(atol, rtol, device, out=None):
+    """{atol, rtol} as the fp64 [2] device tensor picard_scan reads (a captured iteration re-reads it at every replay)"""
+    for name, v in (("atol", atol), ("rtol", rtol)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+            raise ValueError(f"picard: {name} must be a finite number >= 0, got {v!r}")
+    host = torch.tensor([float(atol), float(rtol)], dtype=torch.float64)
+    if out is None:
+        out = torch.empty(2, dtype=torch.float64, device=device)
+    _chk_eval(out, torch.float64, "tol", (2,), None)
+    out.copy_(host)
+    return out
+
+
+def picard_begin(x0, t_table, N, P, *, X=None, T=None, state=None):
+    """The empty window at the head of the table: (X, T, state) with X[j] = t_j x0 for j = 0 .. min(P, N - 1) (one
+    rounding: X[0] is the table solver's first state bit for bit, the rest is the first guess x_j = X[0] t_j / t_0), copies
+    of X[0] past the table's end, T[j][b] = t[min(j, N - 1)] and every sample active at start 0.  x0: fp32 [B, ...] unit
+    noise; t_table: the fp32 sigma table on the device, at least N entries."""
+    _picard_dims("picard_begin", N, P)
+    B, CHW = _adapt_batch(x0, "x0")
+    if B > 65535:
+        raise ValueError(f"picard_begin: at most 65535 samples per call, got {B}")
+    _chk_eval(t_table, f32, "t_table", None, x0.device)
+    if t_table.dim() != 1 or t_table.numel() < N:
+        raise ValueError(f"t_table: expected a 1-d table of at least {N} entries, got {tuple(t_table.shape)}")
+    shape = (P + 1, *x0.shape)
+    if X is None:
+        X = torch.empty(shape, dtype=f32, device=x0.device)
+    else:
+        _chk_eval(X, f32, "X", shape, x0.device)
+    if T is None:
+        T = torch.empty((P + 1, B), dtype=f32, device=x0.device)
+    else:
+        _chk_eval(T, f32, "T", (P + 1, B), x0.device)
+    if state is None:
+        state = torch.empty((PICARD_ROWS, B), dtype=torch.int32, device=x0.device)
+    _picard_state(state, B, x0.device)
+    _lib.call("edm_picard_slide", _p(x0), None, None, _p(state), _p(t_table), 1, B, N, P, CHW, _p(X), _p(T), _stream())
+    return X, T, state
+
+
+def picard_scan(X, dx, X1, D1, T, state, atol=None, rtol=None, *, N, tol=None, Xnew=None, part=None):
+    """The prefix sum of one Picard iteration: (Xnew, part).  Xnew[0] = X[0], Xnew[j + 1] = fma(t1 - t0, slope_j, Xnew[j])
+    over the live positions with slope_j = 0.5 dx_j + 0.5 (X1_j - D1_j) / t1 from the old iterate (D1 None: slope_j = dx_j,
+    the Euler iteration), inactive positions copy the last live one.  part: fp64 [B, P, picard_chunks(CHW)], the
+    order-fixed partial sums of ((new - old) / (atol + rtol max(|old|, |new|)))^2 per position (picard_control adds them
+    up).  The tolerances are read from `tol` (ops.picard_tol) when given, else from atol and rtol."""
+    P, B, CHW = _picard_window(X)
+    _picard_dims("picard_scan", N, P)
+    _picard_rows_of(dx, "dx", P, B, CHW, X.device)
+    if D1 is not None:
+        _picard_rows_of(X1, "X1", P, B, CHW, X.device)
+        _picard_rows_of(D1, "D1", P, B, CHW, X.device)
+    _chk_eval(T, f32, "T", (P + 1, B), X.device)
+    _picard_state(state, B, X.device)
+    if tol is None:
+        tol = picard_tol(atol, rtol, X.device)
+    else:
+        _chk_eval(tol, torch.float64, "tol", (2,), X.device)
+    if Xnew is None:
+        Xnew = torch.empty_like(X)
+    else:
+        _chk_eval(Xnew, f32, "Xnew", X.shape, X.device)
+        if Xnew.data_ptr() == X.data_ptr():
+            raise ValueError("picard_scan: Xnew must not alias X")
+    pshape = (B, P, picard_chunks(CHW))
+    if part is None:
+        part = torch.empty(pshape, dtype=torch.float64, device=X.device)
+    else:
+        _chk_eval(part, torch.float64, "part", pshape, X.device)
+    _lib.call("edm_picard_scan", _p(X), _p(dx), _p(X1 if D1 is not None else None), _p(D1), _p(T), _p(state), _p(tol), B, N,
+              P, CHW, _p(Xnew), _p(part), _p(health(X.device)), _stream())
+    return Xnew, part
+
+
+def picard_control(part, CHW, state, N, P, active, *, stride=None, err=None):
+    """The window controller, one thread per sample in fp64: E_j of the live positions from `part`, the stride
+    min(leading converged + 1, live), the state advanced (see include/tinyedm_hip.h).  Returns the strides, int32 [B] (0
+    for a sample that was not active); adds the number of samples still active to `active`, a one-element int32 device
+    tensor.  err: optional fp64 [B, P] that receives E of the live positions."""
+    _picard_state(state, 0, None)
+    B = state.shape[1]
+    _picard_dims("picard_control", N, P)
+    if isinstance(CHW, bool) or not isinstance(CHW, int) or CHW < 1:
+        raise ValueError(f"picard_control: CHW must be a positive integer, got {CHW!r}")
+    _chk_eval(part, torch.float64, "part", (B, P, picard_chunks(CHW)), state.device)
+    _chk_eval(active, torch.int32, "active", None, state.device)
+    if active.numel() != 1:
+        raise ValueError(f"active: expected a one-element int32 tensor, got {tuple(active.shape)}")
+    if stride is None:
+        stride = torch.empty(B, dtype=torch.int32, device=state.device)
+    else:
+        _chk_eval(stride, torch.int32, "stride", (B,), state.device)
+    if err is not None:
+        _chk_eval(err, torch.float64, "err", (B, P), state.device)
+    _lib.call("edm_picard_control", _p(part), B, CHW, N, P, _p(state), _p(stride), _p(err), _p(active), _stream())
+    return stride
+
+
+def picard_slide(Xnew, D, stride, state, t_table, *, N, X=None, T=None):
+    """Slide every sample's window by its stride: (X, T), X another buffer than Xnew.  X[j] = Xnew[j + stride] while that
+    is a computed position; a position entering the window at table index i <= N - 1 is extrapolated along the ODE's
+    solution for a frozen denoised image, fma(Xnew[L] - Dh, t_i / t_{s + L}, Dh) with Dh = D[L - 1]; indices past N - 1 copy
+    Xnew[L].  T is rewritten from the state, which picard_control has advanced already."""
+    P, B, CHW = _picard_window(Xnew, "Xnew")
+    _picard_dims("picard_slide", N, P)
+    _picard_rows_of(D, "D", P, B, CHW, Xnew.device)
+    _chk_eval(stride, torch.int32, "stride", (B,), Xnew.device)
+    _picard_state(state, B, Xnew.device)
+    _chk_eval(t_table, f32, "t_table", None, Xnew.device)
+    if t_table.dim() != 1 or t_table.numel() < N:
+        raise ValueError(f"t_table: expected a 1-d table of at least {N} entries, got {tuple(t_table.shape)}")
+    if X is None:
+        X = torch.empty_like(Xnew)
+    else:
+        _chk_eval(X, f32, "X", Xnew.shape, Xnew.device)
+        if X.data_ptr() == Xnew.data_ptr():
+            raise ValueError("picard_slide: X must not alias Xnew (ping-pong, never in place)")
+    if T is None:
+        T = torch.empty((P + 1, B), dtype=f32, device=Xnew.device)
+    else:
+        _chk_eval(T, f32, "T", (P + 1, B), Xnew.device)
+    _lib.call("edm_picard_slide", _p(Xnew), _p(D), _p(stride), _p(state), _p(t_table), 0, B, N, P, CHW, _p(X), _p(T),
+              _stream())
+    return X, T
+
+
 def _nhwc32(t, name):
     _chk(t, f32, name)
     if t.dim() != 4:

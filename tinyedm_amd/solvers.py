@@ -1,6 +1,7 @@
 """ODE / SDE samplers with the loop optionally captured in a hipGraph: the 2nd-order Heun ones, deterministic as in the
 reference (solvers.py:4-59) and stochastic as Algorithm 2 of Karras et al. 2022, and the DPM-Solver++ multistep one
-(Lu et al. 2022) that spends one network evaluation per step."""
+(Lu et al. 2022) that spends one network evaluation per step; the adaptive Heun / Euler pair; and the table solve iterated
+in parallel over a window of steps (ParaDiGMS, Shih et al. 2023)."""
 import math
 import weakref
 from dataclasses import dataclass
@@ -52,7 +53,7 @@ class _Captured(NamedTuple):
     token: object           # launch-table slots and plan pins of the capture (ops.release_capture)
     w_dev: object           # the guidance weight the graph reads, or None for an unguided solve
     guide: object           # the guide network (kept alive: the key holds its id); None for none or 'unconditional'
-    state: object           # the mode's device state: _ChurnState, _MultistepState, _NllState or None
+    state: object           # the mode's device state: _ChurnState, _MultistepState, _NllState, _PicardState or None
     cond: object            # static _Conditioning, or None
     rest: object            # static _Restoration, or None
 
@@ -719,6 +720,13 @@ class DeterministicSolver:
     def _solve_graphed(self, model, x0, class_labels, mode: _Mode, guided=(), cond=None, rest=None):
         """replay (after capturing, the first time) what ``mode`` describes on x0: the solve, the inversion or the
         likelihood"""
+        ent = self._graph_entry(model, x0, class_labels, mode, guided, cond, rest)
+        ent.graph.replay()
+        return tuple(o.clone() for o in ent.out) if isinstance(ent.out, tuple) else ent.out.clone()
+
+    def _graph_entry(self, model, x0, class_labels, mode: _Mode, guided=(), cond=None, rest=None) -> _Captured:
+        """the captured entry of what ``mode`` describes (captured now, the first time), its static tensors written for this
+        call: ready to replay"""
         # graphs are cached PER MODEL OBJECT (weakly: a new model allocated at a dead one's address must not replay the
         # dead one's graph, which id(model) as a key allowed)
         owner = getattr(model, "__self__", model)        # a bound method is a fresh object per access: key on its object
@@ -791,8 +799,7 @@ class DeterministicSolver:
         for static, value in inputs:
             if static is not None:
                 static.copy_(value)
-        ent.graph.replay()
-        return tuple(o.clone() for o in ent.out) if isinstance(ent.out, tuple) else ent.out.clone()
+        return ent
 
 
 class ChurnSchedule(NamedTuple):
@@ -1184,3 +1191,190 @@ class AdaptiveSolver(DeterministicSolver):
     def log_likelihood(self, *args, **kwargs):
         raise ValueError("AdaptiveSolver.log_likelihood: an adaptive likelihood is not implemented (the divergence would "
                          "have to be integrated per sample); use DeterministicSolver")
+
+
+class ParallelStats(NamedTuple):
+    """what the last parallel solve did (ParallelSolver.last_stats)"""
+    iterations: int                         # Picard iterations of the batch = max(per_sample_iterations)
+    evaluations: int                        # batched calls of the network: order * iterations, + 1 for the closing step
+    guide_evaluations: int                  # calls of the guide, counted apart
+    rows: int                               # network rows evaluated in all: order * iterations * window * B + B
+    sequential_evaluations: int             # order * (N - 1) + 1: what the table solver takes
+    per_sample_iterations: torch.Tensor     # int64 [B] on the host: iterations until the sample's window reached the end
+
+
+class _PicardState(NamedTuple):
+    """the device state of one parallel solve (a captured entry owns its own)"""
+    X: torch.Tensor         # fp32 [P + 1, B, ...]: the window, position-major
+    Xnew: torch.Tensor      # the other buffer: the scan writes it, the slide reads it
+    T: torch.Tensor         # fp32 [P + 1, B]: the times of the window positions
+    state: torch.Tensor     # int32 [ops.PICARD_ROWS, B]
+    stride: torch.Tensor    # int32 [B]
+    active: torch.Tensor    # int32 [1]: the running count the host reads after every iteration
+    part: torch.Tensor      # fp64 [B, P, chunks]
+    tol: torch.Tensor       # fp64 [2]: atol, rtol
+    t_dev: torch.Tensor     # the sigma table on the device
+
+
+class ParallelSolver(DeterministicSolver):
+    """The table solver's result computed in parallel over time (ParaDiGMS: Shih et al. 2023): Picard iteration of the
+    Heun step (``order=2``) or the Euler step (``order=1``) of DeterministicSolver's table t_0 .. t_N over a window of
+    ``window`` = P consecutive steps.  Every sample b holds the states at table indices s_b .. s_b + P as unknowns; one
+    iteration evaluates the network at the first P of them in ONE batch of P * B rows (twice for Heun), rebuilds the
+    window as x_{s+j+1} = x_s + sum_{k <= j} h_k slope_k(old iterate) (ops.picard_scan, a prefix sum in index order),
+    measures per position
+
+        E_j = sqrt(mean ((new - old) / (atol + rtol max(|old|, |new|)))^2)        (fp64, order-fixed)
+
+    and slides the window past the m leading positions with E_j <= 1 and one more: the position after a converged
+    prefix is one sequential step from a converged state (ops.picard_control, ops.picard_slide; the entering positions are
+    initialised along the ODE's solution for a frozen denoised image, which sets the speed of convergence, never its
+    limit).  Every sample advances by at least one step per iteration, so steps 0 .. N-2 take at most N - 1 iterations:
+    the sequential depth is order * iterations + 1 network calls against the table solver's order * (N - 1) + 1.  The
+    closing step t_{N-1} -> 0 is the table's Euler step at batch B.  The fixed point of the iteration is the table
+    solver's result, and ``rtol = atol = 0`` (converged = no element moved, bit for bit) returns it: the bits of
+    DeterministicSolver.solve for a network whose rows do not depend on their batch.
+
+    Each sample has its own window start: a result does not depend on its batch mates.  Plain guidance (``guide``,
+    ``guidance``) mixes D = Dg + w (Dm - Dg) before the update.  ``solve(graph=True)`` captures ONE iteration and replays
+    it, with the host's 4-byte read of the active count between replays; tolerances and the guidance weight are re-read
+    from device memory.  ``guidance_interval`` raises ValueError, and so do start_step, image, mask, degradation,
+    measurement, operator, dps_scale, invert and log_likelihood, on the host before any launch.
+    ``last_stats`` (ParallelStats) describes the last solve."""
+
+    def __init__(self, num_steps: int = 18, sigma_min: float = 0.002, sigma_max: float = 80.0, rho: float = 7.0,
+                 dtype: str | None = None, *, window: int = 16, order: int = 2, rtol: float = 1e-3, atol: float = 1e-4,
+                 guide=None, guidance: float = 1.0, guidance_interval: tuple[float, float] | None = None, seed: int = 0):
+        self.window, self.order, self.rtol, self.atol = window, order, rtol, atol
+        self.last_stats = None
+        if isinstance(num_steps, bool) or not isinstance(num_steps, int) or num_steps < 2:
+            raise ValueError(f"ParallelSolver: needs num_steps >= 2 (steps 0 .. N-2 are iterated, the last one closes), got "
+                             f"{num_steps!r}")
+        super().__init__(num_steps, sigma_min, sigma_max, rho, dtype, guide=guide, guidance=guidance,
+                         guidance_interval=guidance_interval, seed=seed)
+
+    def guided_evaluations(self) -> tuple[bool, ...]:
+        """(whether the evaluations are guided,): all of them or none.  Host only; raises ValueError on an invalid
+        guidance, window, order or tolerance setting."""
+        if self.guidance_interval is not None:
+            raise ValueError("ParallelSolver: guidance_interval is not implemented (the rows of one evaluation are at "
+                             "different sigmas, so the interval would hold per row)")
+        flags = super().guided_evaluations()
+        self._check_parallel()
+        return (any(flags),)
+
+    def _check_parallel(self) -> None:
+        P = self.window
+        if isinstance(P, bool) or not isinstance(P, int) or not 1 <= P <= ops.PICARD_MAX_WINDOW:
+            raise ValueError(f"ParallelSolver: window must be an integer in 1 .. {ops.PICARD_MAX_WINDOW}, got {P!r}")
+        if isinstance(self.order, bool) or self.order not in (1, 2):
+            raise ValueError(f"ParallelSolver: order must be 1 (Euler) or 2 (Heun), got {self.order!r}")
+        for name in ("rtol", "atol"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+                raise ValueError(f"ParallelSolver: {name} must be a finite number >= 0, got {v!r}")
+        lo, hi = self.t_steps[self.num_steps - 1].item(), self.t_steps[0].item()
+        if not (math.isfinite(lo) and math.isfinite(hi) and 0 < lo < hi):
+            raise ValueError(f"ParallelSolver: needs 0 < sigma_min < sigma_max, got {self.sigma_min}, {self.sigma_max}")
+
+    @staticmethod
+    def _refuse(who: str, **given) -> None:
+        for name, on in given.items():
+            if on:
+                raise ValueError(f"ParallelSolver.{who}: {name} is not implemented for the parallel solver (it iterates the "
+                                 "plain table solve over a window of steps); use DeterministicSolver")
+
+    def _picard_state(self, x0) -> _PicardState:
+        """the device state of a solve from x0 (fp32 unit noise), the window at the head of the table"""
+        N, P, dev = self.num_steps, int(self.window), x0.device
+        B, CHW = x0.shape[0], x0.numel() // x0.shape[0]
+        t_dev = self.t_steps.to(dev)
+        X, T, state = ops.picard_begin(x0, t_dev, N, P)
+        return _PicardState(X, torch.empty_like(X), T, state, torch.zeros(B, dtype=torch.int32, device=dev),
+                            torch.zeros(1, dtype=torch.int32, device=dev),
+                            torch.empty((B, P, ops.picard_chunks(CHW)), dtype=torch.float64, device=dev),
+                            ops.picard_tol(self.atol, self.rtol, dev), t_dev)
+
+    def _iterate(self, model, labels, st: _PicardState, guided: bool, w_dev):
+        """one Picard iteration on the state's buffers (what a captured entry replays); labels: repeated window times"""
+        N, order = self.num_steps, int(self.order)
+        P, B = st.X.shape[0] - 1, st.X.shape[1]
+        rows = st.X[:P].view(P * B, *st.X.shape[2:])        # positions 0 .. P-1: one contiguous network batch
+        t, t1 = st.T[:P].view(-1), st.T[1:].view(-1)
+
+        def evaluate(xs, sigma):
+            D = model(xs, sigma, labels).float().contiguous()
+            if not guided:
+                return D
+            Dg = self._guide_eval(model, xs, sigma, labels)
+            return ops.dpm_multistep(xs, D, 0.0, 1.0, 0.0, 0.0, Dg=Dg, w_dev=w_dev)     # (the mix, bit for bit)
+        D = evaluate(rows, t)
+        dx, X1 = ops.adapt_euler(rows, D, t, t1)
+        D1 = evaluate(X1, t1) if order == 2 else None
+        ops.picard_scan(st.X, dx, X1, D1, st.T, st.state, N=N, tol=st.tol, Xnew=st.Xnew, part=st.part)
+        ops.picard_control(st.part, rows[0].numel(), st.state, N, P, st.active, stride=st.stride)
+        ops.picard_slide(st.Xnew, D, st.stride, st.state, st.t_dev, N=N, X=st.X, T=st.T)
+        return st.X
+
+    @torch.no_grad()
+    def solve(self, model, x0, class_labels=None, graph: bool = False, *, start_step: int = 0, image=None, mask=None,
+              degradation=None, measurement=None, operator=None, dps_scale=None):
+        self._refuse("solve", **{"start_step": start_step != 0, "image": image is not None, "mask": mask is not None,
+                                 "degradation": degradation is not None, "measurement": measurement is not None,
+                                 "operator": operator is not None, "dps_scale": dps_scale is not None})
+        guided, = self.guided_evaluations()
+        _check_float("solve", "x0", x0)
+        if x0.dim() < 2 or x0.numel() == 0:
+            raise ValueError(f"solve: x0 must be a non-empty [B, ...] tensor, got {tuple(x0.shape)}")
+        if not x0.is_cuda or (class_labels is not None and not class_labels.is_cuda):
+            raise ValueError("tinyedm_amd.ParallelSolver: x0 and class_labels must be GPU tensors (there is no CPU path)")
+        if guided:
+            self._check_guide(model, x0.device, class_labels)
+        N, P, order, B = self.num_steps, int(self.window), int(self.order), x0.shape[0]
+        in_dtype, x0 = x0.dtype, x0.float().contiguous()
+        labels = None if class_labels is None else class_labels.repeat(P, *([1] * (class_labels.dim() - 1)))
+        if not graph:
+            w_dev = torch.full((1,), float(self.guidance), device=x0.device) if guided else None
+            st = self._picard_state(x0)
+
+            def iterate():
+                self._iterate(model, labels, st, guided, w_dev)
+        else:
+            # one iteration is the captured unit.  The key: the window, the order and the table (kernel arguments of the
+            # capture); the tolerances and the guidance weight are device state a replay re-reads
+            mode = _Mode(("picard", P, order, tuple(self.t_steps.tolist())), lambda: self._picard_state(x0),
+                         lambda e: self._iterate(model, e.labels, e.state, guided, e.w_dev), lambda state: None)
+            ent = self._graph_entry(model, x0, labels, mode, (guided,))
+            st, w_dev, iterate = ent.state, ent.w_dev, ent.graph.replay
+            # the warm-up and earlier solves have moved the entry's window: back to the head of the table, from ent.x
+            ops.picard_begin(ent.x, st.t_dev, N, P, X=st.X, T=st.T, state=st.state)
+            st.active.zero_()
+            ops.picard_tol(self.atol, self.rtol, x0.device, out=st.tol)
+        iterations, seen, left = 0, 0, B
+        while left:
+            # position 1 of a window is one sequential step from a converged state: every active sample advances
+            assert iterations < N - 1, f"ParallelSolver.solve: {left} samples still active after N - 1 = {N - 1} iterations"
+            iterate()
+            iterations += 1
+            total = int(st.active.item())           # the one host read of an iteration: 4 bytes
+            seen, left = total, total - seen
+        # the table's closing Euler step t_{N-1} -> 0: one evaluation at batch B
+        ts = self.t_steps.tolist()
+        x, sigma = st.X[0], st.t_dev[N - 1:N]
+        D = model(x, sigma, class_labels).float().contiguous()
+        if guided:
+            D = ops.dpm_multistep(x, D, 0.0, 1.0, 0.0, 0.0, Dg=self._guide_eval(model, x, sigma, class_labels), w_dev=w_dev)
+        out = ops.heun_euler(x, D, ts[N - 1], 0.0)[1]
+        evaluations = order * iterations + 1
+        self.last_stats = ParallelStats(iterations, evaluations, evaluations if guided else 0,
+                                        order * iterations * P * B + B, order * (N - 1) + 1, st.state[2].cpu().long())
+        ops.check_health(x0.device, "ParallelSolver.solve")
+        return out.to(in_dtype)
+
+    def invert(self, *args, **kwargs):
+        raise ValueError("ParallelSolver.invert: inversion is not implemented for the parallel solver; use "
+                         "DeterministicSolver on the same sigma table")
+
+    def log_likelihood(self, *args, **kwargs):
+        raise ValueError("ParallelSolver.log_likelihood: likelihood evaluation is not implemented for the parallel solver; "
+                         "use DeterministicSolver")
