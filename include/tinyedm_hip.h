@@ -987,6 +987,44 @@ int edm_ideal_accumulate(const float* P, long ld, const void* refs, const float*
 int edm_ideal_finish(const float* acc, const float* state, long Q, int K, float mean, float stdv, float* D, float* lse,
                      float* ent, float* top_w, int* top_idx, unsigned* health, edm_stream_t stream);
 
+/* ---------------------------------------------------------------- moments and polynomial-kernel sums in fp64 (csrc/moments.hip) */
+/* The two reductions behind the Frechet distance of two sample sets (Heusel et al. 2017, "GANs Trained by a Two Time-Scale
+ * Update Rule Converge to a Local Nash Equilibrium"; the distance itself: Dowson & Landau 1982, "The Frechet distance between
+ * multivariate normal distributions") and the kernel inception distance (Binkowski et al. 2018, "Demystifying MMD GANs");
+ * the reference has no call site for either.  Both run on v_mfma_f64_16x16x4_f64 over rows that are converted to fp64 as
+ * they are loaded: no fp64 copy of a set is made.  dtype: 0 = uint8, 1 = float32.  uint8 moments and dot products are exact
+ * integers in fp64 (every sum stays below 2^53), so they do not depend on tiling or split count; float32 products are exact
+ * and the sums round in an order fixed by the arguments, so two calls give the same bits.  No atomics; every partial is
+ * written by an ordinary store.  Sets are row-contiguous at any byte alignment: aligned vector loads when the base is
+ * 16-byte aligned and a row is a whole number of them (moments: D % 4 == 0; sums: D % 16 == 0 for uint8, D % 4 == 0 for
+ * float32), element loads otherwise, same results.  Index lists are trusted:
+ * the caller checks that every entry names a row of its set.  Status -1 and nothing launched on a bad argument.
+ * edm_moments_splits: the number of shares of the N axis the library would give an N x D set (host logic only).
+ * edm_moments_partial: x [rows][D]; index long [N] (may be null: rows 0 .. N - 1; may repeat rows, any order) gathers the N
+ *   rows that take part; shift double [D] (may be null) is subtracted from every row in fp64 before the products (the second
+ *   pass of a two-pass covariance; null keeps uint8 results exact integers).  Share s of `splits` (the caller's choice in
+ *   [1, 1024]) takes rows N s / splits .. N (s + 1) / splits and writes psum [splits][D] and, of pgram [splits][D][D], the
+ *   64 x 64 tiles on and above the tile diagonal (entries with i / 64 > j / 64 are not written).  pgram null: the column
+ *   sums only.  Limits: 1 <= N < 2^40, 1 <= D <= 32768.
+ * edm_moments_finish: sum [D] and gram [D][D] (both null together with pgram) = the partials added in split order, the upper
+ *   triangle mirrored into the lower.
+ * edm_poly_sums_partial: for each of S subsets, rows idx_a[s][0 .. ma) of a and idx_b[s][0 .. mb) of b (long [S][ma] and
+ *   [S][mb]; a null list: rows 0 .. m - 1 for every subset): partial[s][ti][tj] = the sum over the 64 x 64 tile (ti, tj) of
+ *   the ma x mb pairs of (gamma a_i . b_j + coef0)^degree, the power by repeated multiplication, degree in [1, 4].
+ *   exclude_equal_index skips the pairs whose two row numbers are equal (by number, not by value: a duplicate row still
+ *   counts).  partial double [S][ceil(ma / 64)][ceil(mb / 64)].  Limits: 1 <= S <= 65535, 1 <= ma, mb <= 65535 * 64,
+ *   1 <= D <= 2^24.
+ * edm_poly_sums_finish: sums [S] = the `tiles` partials of each subset, added in a fixed order. */
+int edm_moments_splits(long N, int D);
+int edm_moments_partial(const void* x, int dtype, const long* index, long N, int D, const double* shift, int splits,
+                        double* psum, double* pgram, edm_stream_t stream);
+int edm_moments_finish(const double* psum, const double* pgram, int splits, int D, double* sum, double* gram,
+                       edm_stream_t stream);
+int edm_poly_sums_partial(const void* a, int dtype_a, const long* idx_a, const void* b, int dtype_b, const long* idx_b, int S,
+                          long ma, long mb, int D, double gamma, double coef0, int degree, int exclude_equal_index,
+                          double* partial, edm_stream_t stream);
+int edm_poly_sums_finish(const double* partial, int S, long tiles, double* sums, edm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -215,6 +215,12 @@ SIGNATURES = {
     "edm_ideal_softmax": [P, L, L, L, L, P, P, P, P],
     "edm_ideal_accumulate": [P, L, P, P, L, L, I, I, P, P],
     "edm_ideal_finish": [P, P, L, I, F, F, P, P, P, P, P, P, P],
+    # moments.hip
+    "edm_moments_splits": [L, I],
+    "edm_moments_partial": [P, I, P, L, I, P, I, P, P, P],
+    "edm_moments_finish": [P, P, I, I, P, P, P],
+    "edm_poly_sums_partial": [P, I, P, P, I, P, I, L, L, I, D, D, I, I, P, P],
+    "edm_poly_sums_finish": [P, I, L, P, P],
 }
 # include/tinyedm_hip_diag.h: tools-only entry points, bound on demand by call()
 DIAG_SIGNATURES = {
@@ -232,7 +238,7 @@ _NO_STATUS = {"edm_lowrank_wgrad_workspace", "edm_lowrank_supported", "edm_lowra
               "edm_wgrad3_apply_table_bytes",
               "edm_conv_wgrad_1x1_group_table_bytes", "edm_wgrad_finish_multi_table_bytes", "edm_attention_qkv_supported",
               "edm_attention_long_supported", "edm_conv_in_dgrad_pack_cols",
-              "edm_u8_knn_splits"}
+              "edm_u8_knn_splits", "edm_moments_splits"}
 
 _lib = None
 

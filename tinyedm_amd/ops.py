@@ -3697,3 +3697,112 @@ def ideal_denoise(x, sigma, refs, rnorms, mean=0.5, std=0.5, *, ref_labels=None,
             _lib.call("edm_ideal_accumulate", _p(S), ld, _p(r2[a:a + n]), _p(state), Q, n, K, int(a == 0), _p(D), st)
     _lib.call("edm_ideal_finish", _p(D), _p(state), Q, K, mean, std, _p(D), _p(lse), _p(ent), _p(top_w), _p(top_idx), hw, st)
     return D, lse, ent, top_w, top_idx
+
+
+# ------------------------------------------------------------------ fp64 moments and polynomial-kernel sums (csrc/moments.hip)
+MOMENTS_MAX_D = 32768
+MOMENTS_MAX_SPLITS = 1024
+POLY_MAX_M = 65535 * 64          # one grid row / column per 64 rows of a subset
+POLY_MAX_S = 65535
+POLY_MAX_D = 2 ** 24
+
+
+def _f64_rows(t, name):
+    """a set for the fp64 reductions: uint8 or float32 [n, ...] on the device, contiguous -> (the [n, D] view, dtype code)"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: expected a tensor, got {type(t).__name__}")
+    if t.dtype not in (torch.uint8, f32):
+        raise TypeError(f"{name}: expected uint8 pixels or float32 features, got {t.dtype} (convert features with .float())")
+    if t.dim() < 2 or t.numel() == 0:
+        raise ValueError(f"{name}: expected a non-empty [n, ...] tensor (D >= 1), got {tuple(t.shape)}")
+    _chk(t, t.dtype, name)
+    return t.view(t.shape[0], -1), 0 if t.dtype == torch.uint8 else 1
+
+
+def _row_index(index, rows, name, dev, dims):
+    """an int64 index tensor of `dims` dimensions on `dev`, every entry a row number in [0, rows)"""
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.int64 or index.dim() != dims or index.numel() == 0:
+        raise ValueError(f"{name}: expected a non-empty int64 tensor of {dims} dimension(s), got "
+                         f"{(index.dtype, tuple(index.shape)) if isinstance(index, torch.Tensor) else type(index).__name__}")
+    _chk_eval(index, torch.int64, name, None, dev)
+    lo, hi = int(index.min()), int(index.max())
+    if lo < 0 or hi >= rows:
+        raise ValueError(f"{name}: entries must lie in [0, {rows}), got {lo} .. {hi}")
+    return index
+
+
+def moments_splits(N, D) -> int:
+    """the number of shares of the N axis the library picks for the moments of an N x D set"""
+    return int(_lib.call("edm_moments_splits", int(N), int(D)))
+
+
+def moments(x, index=None, shift=None, splits=None, *, sums_only=False):
+    """(sum fp64 [D], gram fp64 [D, D]) of the rows of x (uint8 or float32 [n, ...], taken as [n, D]): sum = sum_i y_i and
+    gram = sum_i y_i y_i^T with y_i = x[index[i]] - shift in fp64.  index: int64 [N] on the device, any order, repeats
+    allowed (None: every row once).  shift: fp64 [D] on the device (None: 0).  uint8 rows without a shift give exact
+    integers, whatever `splits` (the number of shares of the N axis; None: the library's plan); float32 rows give the same
+    bits for the same arguments.  sums_only: the column sums alone, (sum, None)."""
+    x2, code = _f64_rows(x, "x")
+    D = x2.shape[1]
+    if D > MOMENTS_MAX_D:
+        raise ValueError(f"moments: rows must hold 1 to {MOMENTS_MAX_D} elements, got {D}")
+    if splits is not None and (isinstance(splits, bool) or not isinstance(splits, int) or not 1 <= splits <= MOMENTS_MAX_SPLITS):
+        raise ValueError(f"moments: splits must be None or an integer in [1, {MOMENTS_MAX_SPLITS}], got {splits!r}")
+    dev = x.device
+    if index is not None:
+        _row_index(index, x2.shape[0], "index", dev, 1)
+    if shift is not None:
+        _chk_eval(shift, torch.float64, "shift", (D,), dev)
+    N = x2.shape[0] if index is None else index.shape[0]
+    S = moments_splits(N, D) if splits is None else splits
+    psum = torch.empty(S, D, dtype=torch.float64, device=dev)
+    pgram = None if sums_only else torch.empty(S, D, D, dtype=torch.float64, device=dev)
+    out_sum = torch.empty(D, dtype=torch.float64, device=dev)
+    gram = None if sums_only else torch.empty(D, D, dtype=torch.float64, device=dev)
+    with _prof("moments", 0.0 if sums_only else 2.0 * N * D * D, float(N) * D * x.element_size()):
+        _lib.call("edm_moments_partial", _p(x2), code, _p(index), N, D, _p(shift), S, _p(psum), _p(pgram), _stream())
+        _lib.call("edm_moments_finish", _p(psum), _p(pgram), S, D, _p(out_sum), _p(gram), _stream())
+    return out_sum, gram
+
+
+def poly_kernel_sums(a, idx_a, b, idx_b, gamma, coef0, degree, exclude_equal_index=False):
+    """sums fp64 [S]: for each subset s the sum over i < ma, j < mb of (gamma a[idx_a[s, i]] . b[idx_b[s, j]] + coef0)^degree
+    in fp64.  a, b: uint8 or float32 [n, ...] with the same number of elements per row (taken as [n, D]); idx_a int64
+    [S, ma], idx_b int64 [S, mb] on the device (None: every row of the set in order, as one subset).  degree: 1 to 4.
+    exclude_equal_index skips the pairs with idx_a[s, i] == idx_b[s, j] (the diagonal of a set against itself; by index, so
+    a duplicate row still counts).  Same arguments, same bits."""
+    if isinstance(degree, bool) or not isinstance(degree, int) or not 1 <= degree <= 4:
+        raise ValueError(f"poly_kernel_sums: degree must be an integer in [1, 4], got {degree!r}")
+    gamma, coef0 = float(gamma), float(coef0)
+    if not (math.isfinite(gamma) and math.isfinite(coef0)):
+        raise ValueError(f"poly_kernel_sums: gamma and coef0 must be finite, got {gamma}, {coef0}")
+    a2, code_a = _f64_rows(a, "a")
+    b2, code_b = _f64_rows(b, "b")
+    D = a2.shape[1]
+    if b2.shape[1] != D:
+        raise ValueError(f"poly_kernel_sums: rows of a hold {D} elements, rows of b {b2.shape[1]}")
+    if D > POLY_MAX_D:
+        raise ValueError(f"poly_kernel_sums: rows must hold 1 to {POLY_MAX_D} elements, got {D}")
+    dev = a.device
+    if b.device != dev:
+        raise ValueError(f"poly_kernel_sums: a on {dev}, b on {b.device}")
+    if idx_a is not None:
+        _row_index(idx_a, a2.shape[0], "idx_a", dev, 2)
+    if idx_b is not None:
+        _row_index(idx_b, b2.shape[0], "idx_b", dev, 2)
+    S = 1 if idx_a is None else idx_a.shape[0]
+    if (1 if idx_b is None else idx_b.shape[0]) != S:
+        raise ValueError(f"poly_kernel_sums: idx_a and idx_b must list the same number of subsets (None counts as one)")
+    ma = a2.shape[0] if idx_a is None else idx_a.shape[1]
+    mb = b2.shape[0] if idx_b is None else idx_b.shape[1]
+    if not 1 <= S <= POLY_MAX_S or ma > POLY_MAX_M or mb > POLY_MAX_M:
+        raise ValueError(f"poly_kernel_sums: expected 1 to {POLY_MAX_S} subsets of at most {POLY_MAX_M} rows, got {S} of "
+                         f"{ma} x {mb}")
+    tiles = ((ma + 63) // 64) * ((mb + 63) // 64)
+    partial = torch.empty(S, tiles, dtype=torch.float64, device=dev)
+    sums = torch.empty(S, dtype=torch.float64, device=dev)
+    with _prof("poly_kernel_sums", 2.0 * S * ma * mb * D, float(S) * (ma + mb) * D * a.element_size()):
+        _lib.call("edm_poly_sums_partial", _p(a2), code_a, _p(idx_a), _p(b2), code_b, _p(idx_b), S, ma, mb, D, gamma, coef0,
+                  degree, int(bool(exclude_equal_index)), _p(partial), _stream())
+        _lib.call("edm_poly_sums_finish", _p(partial), S, tiles, _p(sums), _stream())
+    return sums
