@@ -677,6 +677,10 @@ int edm_dps_update(const float* x, const float* g, const float* nrm, float scale
  *   alone, [B, CHW];  L_b += (t1 - t0) / 2 * (CHW - q_b) / t1 with q_b from D1 under (step, 1) and h1.
  * edm_nll_prior: L_b += log N(x_b; 0, t^2 I) = -CHW/2 log(2 pi t^2) - sum_j (x_bj / t)^2 / 2, x [B, CHW]. */
 #define EDM_NLL_MAX_CHUNKS 64
+/* How many entries of a sample's row of `part` the order-fixed reductions fill (likelihood, noise-level evaluation, the
+ * adaptive and the parallel solver): min(ceil(ceil(CHW / 4) / 256), EDM_NLL_MAX_CHUNKS), 0 for CHW <= 0.  Host logic only:
+ * the rule the kernels index with, asked of the library instead of restated by the caller. */
+int edm_sample_chunks(long CHW);
 int edm_nll_probe(const float* x, float h, const void* rec, int step, int ev, int K, int B, long CHW, float* E,
                   unsigned* health, edm_stream_t stream);
 int edm_heun_euler_div(const float* E, const float* D, float t0, float t1, float h0, float h1, const void* rec, int step,

@@ -258,6 +258,17 @@ def test_ops_have_no_cpu_path():
     assert [ops.adapt_chunks(n) for n in (1, 1024, 1025, 3072, 4099, 10 ** 6)] == [1, 1, 2, 3, 5, 64]
 
 
+def test_the_library_states_the_chunk_rule():
+    """edm_sample_chunks (host logic): the rule the kernels index `part` with, against its closed form; ops sizes the
+    workspaces of the adaptive and the parallel solver with the library's value instead of a copy of the formula"""
+    from tinyedm_amd import _lib
+    for CHW in (1, 4, 5, 1024, 1025, 1028, 3072, 65536, 65540, 2 ** 31):
+        want = min(((CHW + 3) // 4 + 255) // 256, ops.NLL_MAX_CHUNKS)
+        assert _lib.call("edm_sample_chunks", CHW) == want, CHW
+        assert ops.adapt_chunks(CHW) == want and ops.picard_chunks(CHW) == want, CHW
+    assert ops.NLL_MAX_CHUNKS == 64 and ops.adapt_chunks(2 ** 31) == 64
+
+
 GEN = dict(ckpt_path="missing.ckpt", load_ema=False, num_samples=4, image_size=32, num_classes=10, batch_size=4)
 
 

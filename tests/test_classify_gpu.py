@@ -1,5 +1,5 @@
 """The diffusion classifier on the GPU (tinyedm_amd/classify.py, ops.eval_diffuse_classes / ops.eval_sqerr_classes in
-optim.hip):
+sample_eval.hip):
 
  * the two class-sweep kernels bit for bit against the pair they extend, on the dwordx4 path, the scalar path with a
    partial last quad, a misaligned tensor and C = 1; the squared error against numpy fp64; health bit and refusals;

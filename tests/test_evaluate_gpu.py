@@ -1,4 +1,4 @@
-"""Loss by noise level on the GPU (tinyedm_amd/evaluate.py, ops.eval_diffuse / ops.eval_sqerr in optim.hip):
+"""Loss by noise level on the GPU (tinyedm_amd/evaluate.py, ops.eval_diffuse / ops.eval_sqerr in sample_eval.hip):
 
  * the noise against the numpy restatement of tests/evaluate_ref.py on the dwordx4 path, the scalar path with a partial
    last quad and the scalar path of a misaligned tensor; clean + sigma*n on non-zero images; the noise of an (id, level,

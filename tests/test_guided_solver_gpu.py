@@ -1,6 +1,6 @@
 """Guided Heun sampling on the GPU (DeterministicSolver(guide=..., guidance=..., guidance_interval=...)):
 
- * the guided update kernels (optim.hip) against an fp64 restatement, on the dwordx4 path, its scalar tail and the
+ * the guided update kernels (solver_steps.hip) against an fp64 restatement, on the dwordx4 path, its scalar tail and the
    scalar path of a misaligned operand; w = 0 is bit-identical to the unguided update fed D_guide; a NaN raises the
    health bit;
  * guided trajectories of tiny nets against the CPU oracle composing D_guide + w*(D_main - D_guide) per sigma: CFG with

@@ -1,6 +1,6 @@
 """DPM-Solver++ multistep sampling on the GPU (MultistepSolver, ops.dpm_multistep):
 
- * the update kernel (optim.hip) against an fp64 restatement, for each order, guided and unguided, on the dwordx4 path,
+ * the update kernel (solver_steps.hip) against an fp64 restatement, for each order, guided and unguided, on the dwordx4 path,
    its scalar tail and the scalar path of a misaligned operand; w = 0 is bit-identical to the unguided kernel fed
    D_guide; the final row (0, 1, 0, 0) returns the mixed D itself; a NaN raises the health bit; bad operands raise;
  * convergence on two analytic denoisers (a Gaussian with its exact solution, a 4-component Gaussian mixture against an

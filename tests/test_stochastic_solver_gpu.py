@@ -1,6 +1,6 @@
 """Stochastic Heun sampling on the GPU (StochasticSolver, Algorithm 2 of Karras et al. 2022):
 
- * the churn kernel (ops.heun_churn, optim.hip) against a numpy restatement of Philox4x32-10 + Box-Muller in uint64 /
+ * the churn kernel (ops.heun_churn, solver_steps.hip) against a numpy restatement of Philox4x32-10 + Box-Muller in uint64 /
    fp64, on the dwordx4 path, the scalar path (CHW % 4 != 0) and the scalar path of a misaligned tensor; x + c*n on a
    non-zero x; the noise of a sample does not depend on the batch size or the memory path; different step, solve index
    or seed give uncorrelated N(0, 1) noise; a NaN raises the health bit;

@@ -128,6 +128,7 @@ SIGNATURES = {
     "edm_adam_ema_ranges": [P, P, P, P, P, L, P, I, P, I, F, F, F, F, I, F, F, P, I, P, P],
     "edm_phema_accumulate": [P, P, P, I, L, P],
     "edm_phema_finish": [P, P, L, P],
+    # solver_steps.hip
     "edm_heun_euler": [P, P, F, F, P, P, L, P, P],
     "edm_heun_correct": [P, P, P, P, F, F, P, L, P, P],
     "edm_heun_euler_guided": [P, P, P, P, F, F, P, P, L, P, P],
@@ -136,6 +137,9 @@ SIGNATURES = {
     "edm_dpm_multistep": [P, P, P, P, P, P, F, F, F, F, P, P, L, P, P],
     "edm_state_init": [P, P, F, P, L, P, P],
     "edm_inpaint_blend": [P, P, P, F, P, I, I, I, L, I, P, P, P],
+    "edm_scale_f32": [P, F, P, L, P],
+    # sample_eval.hip
+    "edm_sample_chunks": [L],
     "edm_nll_probe": [P, F, P, I, I, I, I, L, P, P, P],
     "edm_heun_euler_div": [P, P, F, F, F, F, P, I, I, I, L, P, P, P, P, P, P],
     "edm_heun_correct_div": [P, P, P, P, F, F, F, F, P, I, I, I, I, L, P, P, P, P, P],
@@ -144,7 +148,6 @@ SIGNATURES = {
     "edm_eval_sqerr": [P, P, I, L, P, P, P, P],
     "edm_eval_diffuse_classes": [P, P, P, P, I, P, I, I, L, P, P, P, P],
     "edm_eval_sqerr_classes": [P, P, I, I, L, P, P, P, P],
-    "edm_scale_f32": [P, F, P, L, P],
     # grad_guard.hip
     "edm_grad_guard": [P, L, P, I, P, I, I, F, P, F, F, I, I, P, P, P, P, P],
     "edm_adam_ema_guarded": [P, P, P, P, P, L, F, F, F, F, I, F, F, P, I, P, P, P],
@@ -238,7 +241,7 @@ _NO_STATUS = {"edm_lowrank_wgrad_workspace", "edm_lowrank_supported", "edm_lowra
               "edm_wgrad3_apply_table_bytes",
               "edm_conv_wgrad_1x1_group_table_bytes", "edm_wgrad_finish_multi_table_bytes", "edm_attention_qkv_supported",
               "edm_attention_long_supported", "edm_conv_in_dgrad_pack_cols",
-              "edm_u8_knn_splits", "edm_moments_splits"}
+              "edm_u8_knn_splits", "edm_moments_splits", "edm_sample_chunks"}
 
 _lib = None
 

@@ -25,6 +25,7 @@ def _stale(src, obj):
         return True
     t = os.path.getmtime(obj)
     deps = [os.path.join(CSRC, src)] + [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")]
+    deps.append(os.path.join(os.path.dirname(HERE), "include", "tinyedm_hip.h"))      # csrc/quads.h includes it
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -1,61 +1,26 @@
 // Adaptive integration of the probability-flow ODE: the embedded Heun(2) / Euler(1) pair with local extrapolation and a
 // step controller that lives on the device.  Every sample carries its own time and step size, so the Heun updates of
-// optim.hip (t0, t1 by value for the whole batch) are restated here with the times read per sample; the expressions are
-// written as those kernels' code is contracted (k_heun_euler_div / k_heun_correct_div do the same), so a batch whose
-// samples all sit at one pair (t0, t1) gets the bits of edm_heun_euler / edm_heun_correct.
+// solver_steps.hip (t0, t1 by value for the whole batch) appear here with the times read per sample; both evaluate the
+// step functions of quads.h (as k_heun_euler_div / k_heun_correct_div do), so a batch whose samples all sit at one pair
+// (t0, t1) gets the bits of edm_heun_euler / edm_heun_correct.
 //
 // Per-sample state: EDM_ADAPT_ROWS rows of B 32-bit words, row r at state + r * B (include/tinyedm_hip.h):
 //   T, T1, H, ERR fp32; STATUS (0 active, 1 done, 2 failed), ACCEPTED, REJECTED, AFTER_REJECT uint32.
 // A sample that is not active has t1 == t: the update kernels then copy x through (dx = 0, y = x) whatever D holds, and
 // its error partials are +0.
 //
-// The error norm is order-fixed, as edm_eval_sqerr's: workgroup (chunk, b) sums its quads of sample b in fp64
-// (thread-serial, the xor butterfly of whole waves, four wave totals in index order) into part[b][chunk]; the controller
-// adds a sample's chunks in index order.  The chunking depends on CHW alone.  No atomics on floating point.
+// The error norm is order-fixed, as edm_eval_sqerr's (block_partial and chunk_sum of quads.h): the controller adds a
+// sample's chunks in index order.  The chunking depends on CHW alone.  No atomics on floating point.
 #include "common.h"
+#include "quads.h"
 
 #include <cmath>
-#include <initializer_list>
 
 namespace {
 
-constexpr int ADAPT_MAX_CHUNKS = 64;        // = EDM_NLL_MAX_CHUNKS (include/tinyedm_hip.h)
 enum { ROW_T = 0, ROW_T1, ROW_H, ROW_ERR, ROW_STATUS, ROW_ACCEPTED, ROW_REJECTED, ROW_AFTER_REJECT, ADAPT_ROWS };
 enum : uint32_t { ST_ACTIVE = 0, ST_DONE = 1, ST_FAILED = 2 };
 
-template <bool VEC>
-__device__ __forceinline__ void load4(const float* __restrict__ p, int m, float (&v)[4]) {
-  if (VEC) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = k < m ? p[k] : 0.f;
-  }
-}
-template <bool VEC>
-__device__ __forceinline__ void store4(float* __restrict__ p, int m, const float (&v)[4]) {
-  if (VEC) {
-    *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (k < m) p[k] = v[k];
-  }
-}
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-// EVERY thread of the 256-thread workgroup calls this, after its loop and outside any divergent branch
-__device__ __forceinline__ void block_partial(double v, double* __restrict__ slot) {
-  __shared__ double red[4];
-  v = wave_sum_f64(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) *slot = ((red[0] + red[1]) + red[2]) + red[3];
-}
 // the snap rule: the trial time of a step of h from t towards t_end.  When t + h passes t_end, or comes within 1 % of
 // |h| of it, the step ends on t_end exactly (a sliver of a last step is never taken)
 __device__ __forceinline__ float snap_t1(float t, float h, float t_end) {
@@ -90,7 +55,7 @@ __global__ __launch_bounds__(256) void k_adapt_euler(const float* __restrict__ x
   bool bad = false;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const long b = i / nq, q = i - b * nq, e = b * CHW + 4 * q;
-    const int m = VEC ? 4 : (int)(CHW - 4 * q < 4 ? CHW - 4 * q : 4);
+    const int m = quad_len<VEC>(CHW, q);
     const float t0 = t[b], tn = t1[b];
     float xv[4], d[4], o[4];
     load4<VEC>(x + e, m, xv);
@@ -102,15 +67,14 @@ __global__ __launch_bounds__(256) void k_adapt_euler(const float* __restrict__ x
       load4<VEC>(Dn + e, m, dv);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        d[k] = (xv[k] - dv[k]) / t0;
-        o[k] = fmaf(tn - t0, d[k], xv[k]);      // (k_heun_euler's x + (t1 - t0) * d as the compiler contracts it)
-        bad |= !(fabsf(o[k]) <= 3.0e38f);
+        o[k] = heun_euler_stage(xv[k], dv[k], t0, tn, d[k]);
+        bad |= nonfinite(o[k]);
       }
     }
     store4<VEC>(dx + e, m, d);
     store4<VEC>(x1 + e, m, o);
   }
-  if (health && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(health, 2u);
+  EDM_RAISE_HEALTH(health, bad, 2u);
 }
 
 // grid (chunks, B).  k_heun_correct with the times of sample b: y = x + (t1 - t0) * (0.5 dx + 0.5 (x1 - D1) / t1), and
@@ -129,7 +93,7 @@ __global__ __launch_bounds__(256) void k_adapt_correct(const float* __restrict__
   double acc = 0.0;
   for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
     const long e = b * CHW + 4 * q;
-    const int m = VEC ? 4 : (int)(CHW - 4 * q < 4 ? CHW - 4 * q : 4);
+    const int m = quad_len<VEC>(CHW, q);
     float xv[4], o[4];
     load4<VEC>(x + e, m, xv);
     if (active) {
@@ -139,9 +103,8 @@ __global__ __launch_bounds__(256) void k_adapt_correct(const float* __restrict__
       load4<VEC>(D1 + e, m, d1);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const float dp = (x1v[k] - d1[k]) / tn;
-        o[k] = fmaf(tn - t0, 0.5f * dxv[k] + 0.5f * dp, xv[k]);      // (k_heun_correct's sum, contracted as there)
-        bad |= !(fabsf(o[k]) <= 3.0e38f);
+        o[k] = heun_update(xv[k], heun_slope(dxv[k], x1v[k], d1[k], tn), t0, tn);
+        bad |= nonfinite(o[k]);
         const double sc = fma(rtol, fmax(fabs((double)xv[k]), fabs((double)o[k])), atol);
         const double r = ((double)o[k] - (double)x1v[k]) / sc;
         if (k < m) acc = fma(r, r, acc);
@@ -152,8 +115,8 @@ __global__ __launch_bounds__(256) void k_adapt_correct(const float* __restrict__
     }
     store4<VEC>(y + e, m, o);
   }
-  block_partial(acc, part + b * ADAPT_MAX_CHUNKS + blockIdx.x);
-  if (health && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(health, 2u);
+  block_partial(acc, part + b * EDM_NLL_MAX_CHUNKS + blockIdx.x);
+  EDM_RAISE_HEALTH(health, bad, 2u);
 }
 
 // One thread per sample, fp64.  E = sqrt(sum of the sample's partials in index order / CHW); accept iff E <= 1 (a NaN E
@@ -173,8 +136,7 @@ __global__ __launch_bounds__(64) void k_adapt_control(const double* __restrict__
     uint32_t status = state[ROW_STATUS * B + b];
     unsigned char acc = 0;
     if (status == ST_ACTIVE) {
-      double s = 0.0;
-      for (int c = 0; c < chunks; ++c) s += part[(long)b * ADAPT_MAX_CHUNKS + c];
+      const double s = chunk_sum(part + (long)b * EDM_NLL_MAX_CHUNKS, chunks);
       const double E = sqrt(s / (double)CHW);
       float t = sf[ROW_T * B + b];
       const float t1 = sf[ROW_T1 * B + b];
@@ -223,26 +185,11 @@ __global__ __launch_bounds__(256) void k_adapt_commit(float* __restrict__ x, con
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
     const long b = i / nq, q = i - b * nq, e = b * CHW + 4 * q;
     if (!accept[b]) continue;
-    const int m = VEC ? 4 : (int)(CHW - 4 * q < 4 ? CHW - 4 * q : 4);
+    const int m = quad_len<VEC>(CHW, q);
     float v[4];
     load4<VEC>(y + e, m, v);
     store4<VEC>(x + e, m, v);
   }
-}
-
-inline int grid_for(long work, int block) {
-  long g = (work + block - 1) / block;
-  if (g > 256 * 16) g = 256 * 16;
-  return g < 1 ? 1 : (int)g;
-}
-inline int adapt_chunks(long CHW) {
-  const long c = ((CHW + 3) / 4 + 255) / 256;
-  return (int)(c < ADAPT_MAX_CHUNKS ? c : ADAPT_MAX_CHUNKS);
-}
-bool aligned16(std::initializer_list<const void*> ps) {
-  for (const void* p : ps)
-    if (reinterpret_cast<uintptr_t>(p) & 15) return false;
-  return true;
 }
 
 }  // namespace
@@ -268,7 +215,7 @@ extern "C" int edm_adapt_euler(const float* x, const float* D, const float* t, c
   EDM_CHECK_LAUNCH("adapt_euler");
   return EDM_OK;
 }
-// part: device workspace of B * EDM_NLL_MAX_CHUNKS doubles; the first adapt_chunks(CHW) of every row are written
+// part: device workspace of B * EDM_NLL_MAX_CHUNKS doubles; the first sample_chunks(CHW) of every row are written
 extern "C" int edm_adapt_correct(const float* x, const float* dx, const float* x1, const float* D1, const float* t,
                                  const float* t1, int B, long CHW, double atol, double rtol, float* y, double* part,
                                  unsigned* health, hipStream_t st) {
@@ -276,7 +223,7 @@ extern "C" int edm_adapt_correct(const float* x, const float* dx, const float* x
               "adapt_correct: bad args (B <= 65535)");
   EDM_REQUIRE(std::isfinite(atol) && std::isfinite(rtol) && atol >= 0.0 && rtol >= 0.0 && atol + rtol > 0.0,
               "adapt_correct: atol and rtol must be finite, >= 0 and not both 0");
-  const dim3 grid(adapt_chunks(CHW), B), block(256);
+  const dim3 grid(sample_chunks(CHW), B), block(256);
   if (CHW % 4 == 0 && aligned16({x, dx, x1, D1, y}))
     hipLaunchKernelGGL(k_adapt_correct<true>, grid, block, 0, st, x, dx, x1, D1, t, t1, CHW, atol, rtol, y, part, health);
   else
@@ -292,7 +239,7 @@ extern "C" int edm_adapt_control(const double* part, int B, long CHW, float t_en
   EDM_REQUIRE(safety > 0.0 && safety <= 1.0 && fac_min > 0.0 && fac_min < 1.0 && fac_max >= 1.0 && std::isfinite(fac_max) &&
                   h_floor >= 0.0 && h_floor < 1.0,
               "adapt_control: needs 0 < safety <= 1, 0 < fac_min < 1 <= fac_max < inf, 0 <= h_floor < 1");
-  hipLaunchKernelGGL(k_adapt_control, dim3((B + 63) / 64), dim3(64), 0, st, part, adapt_chunks(CHW), B, CHW, t_end, safety,
+  hipLaunchKernelGGL(k_adapt_control, dim3((B + 63) / 64), dim3(64), 0, st, part, sample_chunks(CHW), B, CHW, t_end, safety,
                      fac_min, fac_max, h_floor, (uint32_t*)state, accept, active, health);
   EDM_CHECK_LAUNCH("adapt_control");
   return EDM_OK;

@@ -80,6 +80,13 @@ inline void edm_max_lds_once(const void* fn, int bytes, std::atomic<unsigned lon
     edm_max_lds_once(reinterpret_cast<const void*>(kern), (bytes), done_);         \
   } while (0)
 
+// workgroups of `block` threads for a grid-stride loop over `work` items: at least 1, at most `cap`
+inline int grid_for(long work, int block, int cap = 256 * 16) {
+  long g = (work + block - 1) / block;
+  if (g > cap) g = cap;
+  return g < 1 ? 1 : (int)g;
+}
+
 #define SILU_DIV 0.596f
 #define NORM_EPS 1e-4f
 
@@ -147,6 +154,16 @@ __device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint3
   return Philox4{c0, c1, c2, c3};
 }
 __device__ __forceinline__ float u32_to_unit(uint32_t u) { return (float)(u >> 8) * (1.0f / 16777216.0f); }  // [0,1)
+// two normal draws from two Philox words
+__device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float& n0, float& n1) {
+  const float u1 = ((float)(a >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0,1)
+  const float u2 = ((float)(b >> 8) + 0.5f) * (1.0f / 16777216.0f);
+  const float r = sqrtf(-2.0f * __logf(u1));
+  float s, c;
+  __sincosf(6.28318530717958648f * u2, &s, &c);
+  n0 = r * c;
+  n1 = r * s;
+}
 
 // Dropout keep mask of the 8 elements of 16-byte chunk i8 (bit j = element j kept), shared by the forward and backward
 // kernels and edm_dropout_mask: ONE Philox4x32-10 call per chunk, 16 random bits per element compared with

@@ -51,7 +51,7 @@ __global__ __launch_bounds__(256) void k_u8_gather_normalize(const unsigned char
 //       so the draw is unbiased (a word is rejected with probability < n / 2^32).  sx and sy look for their j
 //       independently.  After AUG_TRIES rejected words (probability < 2^-256 for n < 2^16) the last one is used as it is.
 // The draws of a disabled op are made and ignored, so enabling one op never moves another's parameters.
-constexpr uint32_t AUG_TAG = 0x41554731u;  // "AUG1": differs from 0x0da7 above and from the tags of optim.hip / linear.hip
+constexpr uint32_t AUG_TAG = 0x41554731u;  // "AUG1": differs from 0x0da7 above and from the tags of optim.hip / solver_steps.hip / sample_eval.hip / linear.hip
 constexpr int AUG_TRIES = 16;
 
 struct AugDraw {

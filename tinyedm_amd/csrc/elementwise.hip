@@ -18,12 +18,6 @@ extern "C" const char* edm_last_error() { return g_err; }
 extern "C" int edm_version() { return 1; }
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
-static inline int grid_for(long work, int block, int cap = 256 * 16) {
-  long g = (work + block - 1) / block;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
 
 // ------------------------------------------------------------------ pixel_norm + mp_silu
 // networks.py:9-14 (pixel_norm over C), :83-84 (mp_silu), used at :249-252.

@@ -7,6 +7,7 @@
 // Every sum is fp64 and runs in a fixed order (quads of a lane, butterfly of a wave = one 1024-element block, blocks of a
 // tensor, tensors of the arena): no floating-point atomics, bit-identical from run to run, whatever the grid or chunk length.
 #include "common.h"
+#include "quads.h"
 #include <math.h>
 #include <cmath>
 
@@ -25,13 +26,8 @@ struct GuardTensor {
   int first_chunk, n_chunks, first_block, n_blocks;
 };
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 __device__ __forceinline__ bool guard_bad(float g, float gs) {     // NaN, or beyond 3e38 before or after the scale
-  return !(fabsf(g) <= 3.0e38f) || !(fabsf(g * gs) <= 3.0e38f);
+  return nonfinite(g) || nonfinite(g * gs);
 }
 
 // launch 1: workgroup c takes chunk c, its four waves the blocks of the chunk in turn.  part[b] = sum (g * grad_scale)^2 of
@@ -190,7 +186,7 @@ __global__ __launch_bounds__(256) void k_adam_ema_guarded(float* __restrict__ th
   auto scaled = [&](float g) {
     if (!clip) return g;
     const float s = g * raw_scale;
-    bad |= !(fabsf(s) <= 3.0e38f);                    // (a clipped infinity is finite: the health bit still reports it)
+    bad |= nonfinite(s);                              // (a clipped infinity is finite: the health bit still reports it)
     return s > cv ? cv : (s < -cv ? -cv : s);         // NaN passes through
   };
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
@@ -241,13 +237,7 @@ __global__ __launch_bounds__(256) void k_adam_ema_guarded(float* __restrict__ th
       }
     }
   }
-  if (health && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(health, 1u);
-}
-
-inline int guard_grid_for(long work, int block) {
-  long g = (work + block - 1) / block;
-  if (g > 256 * 16) g = 256 * 16;
-  return g < 1 ? 1 : (int)g;
+  EDM_RAISE_HEALTH(health, bad, 1u);
 }
 
 int launch_guarded(float* theta, float* grad, float* m, float* v, float* ema, float* const* profiles, int K,
@@ -271,7 +261,7 @@ int launch_guarded(float* theta, float* grad, float* m, float* v, float* ema, fl
   a.ema_beta = ema_beta;
   a.grad_scale = grad_scale;
   const long n4 = (n + 3) / 4;
-  const dim3 grid(guard_grid_for(n4, 256)), block(256);
+  const dim3 grid(grid_for(n4, 256)), block(256);
   const StepParams* d = (const StepParams*)dyn;
   const GuardRecord* r = (const GuardRecord*)record;
 #define EDM_GUARDED_LAUNCH(KK_) \

@@ -10,47 +10,21 @@
 // Per-sample state: EDM_PICARD_ROWS rows of B 32-bit words (include/tinyedm_hip.h): START, STATUS (0 active, 1 done),
 // ITERATIONS.
 //
-// Bit rules, as adaptive.hip's: the step expressions are written as k_adapt_euler / k_adapt_correct are contracted, so at
-// the fixed point a step has the bits of edm_heun_euler / edm_heun_correct; the error norm is order-fixed (thread-serial
+// Bit rules, as adaptive.hip's: the step expressions are the functions of quads.h that k_adapt_euler / k_adapt_correct call,
+// so at the fixed point a step has the bits of edm_heun_euler / edm_heun_correct; the error norm is order-fixed (thread-serial
 // per position, the xor butterfly of whole waves, four wave totals in index order, chunks in index order) with a chunking
 // that depends on CHW alone; no atomics on floating point; nothing is read on the host.
 #include "common.h"
+#include "quads.h"
 
 #include <cmath>
-#include <initializer_list>
 
 namespace {
 
 constexpr int PICARD_MAX_WINDOW = 64;       // = EDM_PICARD_MAX_WINDOW: sizes the LDS of the scan
-constexpr int PICARD_MAX_CHUNKS = 64;       // = EDM_NLL_MAX_CHUNKS
 enum { ROW_START = 0, ROW_STATUS, ROW_ITERATIONS, PICARD_ROWS };
 enum : uint32_t { ST_ACTIVE = 0, ST_DONE = 1 };
 
-template <bool VEC>
-__device__ __forceinline__ void load4(const float* __restrict__ p, int m, float (&v)[4]) {
-  if (VEC) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-    v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = k < m ? p[k] : 0.f;
-  }
-}
-template <bool VEC>
-__device__ __forceinline__ void store4(float* __restrict__ p, int m, const float (&v)[4]) {
-  if (VEC) {
-    *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (k < m) p[k] = v[k];
-  }
-}
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 // the window start as the kernels use it: inside the table whatever the word holds
 __device__ __forceinline__ int table_start(uint32_t word, int N) {
   const int s = (int)word;
@@ -82,7 +56,7 @@ __global__ __launch_bounds__(256) void k_picard_scan(const float* __restrict__ X
   for (long base = (long)blockIdx.x * 256; base < nq; base += (long)gridDim.x * 256) {      // (block-uniform trip count)
     const long q = base + threadIdx.x, e = (long)b * CHW + 4 * q;
     const bool valid = q < nq;
-    const int m = VEC ? 4 : (int)(CHW - 4 * q < 4 ? CHW - 4 * q : 4);
+    const int m = quad_len<VEC>(CHW, q);
     float cur[4] = {0.f, 0.f, 0.f, 0.f};
     if (valid) {
       load4<VEC>(X + e, m, cur);
@@ -102,19 +76,15 @@ __global__ __launch_bounds__(256) void k_picard_scan(const float* __restrict__ X
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          float slope = dxv[k];
-          if (HEUN) {
-            const float dp = (x1v[k] - d1[k]) / t1;
-            slope = 0.5f * dxv[k] + 0.5f * dp;          // (k_heun_correct's sum, contracted as there)
-          }
-          nw[k] = fmaf(t1 - t0, slope, cur[k]);
+          const float slope = HEUN ? heun_slope(dxv[k], x1v[k], d1[k], t1) : dxv[k];
+          nw[k] = heun_update(cur[k], slope, t0, t1);
           const double od = (double)old[k], nd = (double)nw[k];
           const double sc = fma(rtol, fmax(fabs(od), fabs(nd)), atol);
           const double d = nd - od;                     // (exact: the difference of two fp32 values)
           double r = d / sc;
           if (sc == 0.0) r = d == 0.0 ? 0.0 : (double)INFINITY;
           if (k < m) {
-            bad |= !(fabsf(nw[k]) <= 3.0e38f);
+            bad |= nonfinite(nw[k]);
             acc = fma(r, r, acc);
           }
           cur[k] = nw[k];
@@ -133,7 +103,7 @@ __global__ __launch_bounds__(256) void k_picard_scan(const float* __restrict__ X
     const int j = threadIdx.x;
     part[((long)b * P + j) * gridDim.x + blockIdx.x] = j < L ? ((red[0][j] + red[1][j]) + red[2][j]) + red[3][j] : 0.0;
   }
-  if (health && __any(bad) && lane == 0) atomicOr(health, 2u);
+  EDM_RAISE_HEALTH(health, bad, 2u);
 }
 
 // One thread per sample, fp64.  E_j = sqrt(sum of part[b][j - 1][.] in index order / CHW) for the live positions
@@ -153,8 +123,7 @@ __global__ __launch_bounds__(64) void k_picard_control(const double* __restrict_
       int m = 0;
       bool leading = true;
       for (int j = 0; j < L; ++j) {
-        double sum = 0.0;
-        for (int c = 0; c < chunks; ++c) sum += part[((long)b * P + j) * chunks + c];
+        const double sum = chunk_sum(part + ((long)b * P + j) * chunks, chunks);
         const double E = sqrt(sum / (double)CHW);
         if (err) err[(long)b * P + j] = E;
         if (leading && E <= 1.0) ++m; else leading = false;
@@ -203,7 +172,7 @@ __global__ __launch_bounds__(256) void k_picard_slide(const float* __restrict__ 
   const float t_base = tt[s_old + L];
   for (long q = (long)blockIdx.x * 256 + threadIdx.x; q < nq; q += (long)gridDim.x * 256) {
     const long e = (long)b * CHW + 4 * q;
-    const int m = VEC ? 4 : (int)(CHW - 4 * q < 4 ? CHW - 4 * q : 4);
+    const int m = quad_len<VEC>(CHW, q);
     float xl[4], dh[4] = {0.f, 0.f, 0.f, 0.f}, v[4];
     load4<VEC>(Xnew + (long)L * row + e, m, xl);
     if (!begin && enters && L > 0) load4<VEC>(D + (long)(L - 1) * row + e, m, dh);
@@ -228,16 +197,6 @@ __global__ __launch_bounds__(256) void k_picard_slide(const float* __restrict__ 
   }
 }
 
-inline int picard_chunks(long CHW) {
-  const long c = ((CHW + 3) / 4 + 255) / 256;
-  return (int)(c < PICARD_MAX_CHUNKS ? c : PICARD_MAX_CHUNKS);
-}
-bool aligned16(std::initializer_list<const void*> ps) {
-  for (const void* p : ps)
-    if (reinterpret_cast<uintptr_t>(p) & 15) return false;
-  return true;
-}
-
 }  // namespace
 
 // X: [P + 1][B][CHW]; dx, X1, D1: [P][B][CHW] (D1 NULL: the Euler iteration); T: [P + 1][B]; tol: DEVICE {atol, rtol};
@@ -249,7 +208,7 @@ extern "C" int edm_picard_scan(const float* X, const float* dx, const float* X1,
               "picard_scan: bad args (X1 goes with D1; Xnew must not alias X)");
   EDM_REQUIRE(B > 0 && B <= 65535 && N >= 2 && P >= 1 && P <= PICARD_MAX_WINDOW && CHW > 0,
               "picard_scan: needs 0 < B <= 65535, N >= 2, 1 <= P <= 64");
-  const dim3 grid(picard_chunks(CHW), B), block(256);
+  const dim3 grid(sample_chunks(CHW), B), block(256);
   const uint32_t* s = (const uint32_t*)state;
   const bool vec = CHW % 4 == 0 && aligned16({X, dx, X1, D1, Xnew});
   if (D1) {
@@ -272,7 +231,7 @@ extern "C" int edm_picard_control(const double* part, int B, long CHW, int N, in
                                   int* active, hipStream_t st) {
   EDM_REQUIRE(part && state && stride && active && B > 0 && CHW > 0 && N >= 2 && P >= 1 && P <= PICARD_MAX_WINDOW,
               "picard_control: bad args (N >= 2, 1 <= P <= 64)");
-  hipLaunchKernelGGL(k_picard_control, dim3((B + 63) / 64), dim3(64), 0, st, part, picard_chunks(CHW), B, CHW, N, P,
+  hipLaunchKernelGGL(k_picard_control, dim3((B + 63) / 64), dim3(64), 0, st, part, sample_chunks(CHW), B, CHW, N, P,
                      (uint32_t*)state, stride, err, active);
   EDM_CHECK_LAUNCH("picard_control");
   return EDM_OK;
@@ -285,7 +244,7 @@ extern "C" int edm_picard_slide(const float* Xnew, const float* D, const int* st
               "picard_slide: bad args (X must not alias Xnew)");
   EDM_REQUIRE(B > 0 && B <= 65535 && N >= 2 && P >= 1 && P <= PICARD_MAX_WINDOW && CHW > 0,
               "picard_slide: needs 0 < B <= 65535, N >= 2, 1 <= P <= 64");
-  const dim3 grid(picard_chunks(CHW), B), block(256);
+  const dim3 grid(sample_chunks(CHW), B), block(256);
   if (CHW % 4 == 0 && aligned16({Xnew, D, X}))
     hipLaunchKernelGGL(k_picard_slide<true>, grid, block, 0, st, Xnew, D, stride, (uint32_t*)state, t_table, begin, B, N, P, CHW, X, T);
   else

@@ -4,22 +4,11 @@
 // A averages every S x S pixel block (S in {1, 2, 4, 8}) and, with `gray`, also the C <= 8 channels; A+ replicates a
 // value to its block.  Tensors are the solver state's: contiguous fp32 NCHW.
 #include "common.h"
-#include <initializer_list>
+#include "quads.h"
 
 namespace {
 
-inline int grid_for(long work, int block) {
-  long g = (work + block - 1) / block;
-  if (g > 256 * 16) g = 256 * 16;
-  return g < 1 ? 1 : (int)g;
-}
-bool aligned16(std::initializer_list<const void*> ps) {
-  for (const void* p : ps)
-    if (reinterpret_cast<uintptr_t>(p) & 15) return false;
-  return true;
-}
-
-// SW consecutive values of a row of D = Dg + w*(Dm - Dg) (Dg non-null; heun_euler_guided's expression) or of D = Dm
+// SW consecutive values of a row of D = Dg + w*(Dm - Dg) (Dg non-null; guidance_mix of quads.h) or of D = Dm
 template <int SW, bool VEC>
 __device__ __forceinline__ void load_row(const float* __restrict__ Dm, const float* __restrict__ Dg, float w, long e,
                                          float (&v)[SW]) {
@@ -30,11 +19,11 @@ __device__ __forceinline__ void load_row(const float* __restrict__ Dm, const flo
       f32x4 g{};
       if (Dg) g = *reinterpret_cast<const f32x4*>(Dg + e + 4 * q);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) v[4 * q + j] = Dg ? fmaf(w, m[j] - g[j], g[j]) : m[j];
+      for (int j = 0; j < 4; ++j) v[4 * q + j] = Dg ? guidance_mix(w, m[j], g[j]) : m[j];
     }
   } else {
 #pragma unroll
-    for (int j = 0; j < SW; ++j) v[j] = Dg ? fmaf(w, Dm[e + j] - Dg[e + j], Dg[e + j]) : Dm[e + j];
+    for (int j = 0; j < SW; ++j) v[j] = Dg ? guidance_mix(w, Dm[e + j], Dg[e + j]) : Dm[e + j];
   }
 }
 
@@ -103,7 +92,7 @@ k_restore(const float* __restrict__ Dm, const float* __restrict__ Dg, const floa
 #pragma unroll
           for (int j = 0; j < SW; ++j) {
             v[j] = v[j] + corr[j / S];
-            bad |= !(fabsf(v[j]) <= 3.0e38f);
+            bad |= nonfinite(v[j]);
           }
           if constexpr (VEC) {
 #pragma unroll
@@ -117,7 +106,7 @@ k_restore(const float* __restrict__ Dm, const float* __restrict__ Dg, const floa
       }
     }
   }
-  if (PROJECT && health && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(health, 2u);
+  if (PROJECT) EDM_RAISE_HEALTH(health, bad, 2u);
 }
 
 bool shape_ok(int B, int C, int H, int W, int scale, int gray) {
@@ -255,10 +244,10 @@ k_dps_update(const float* __restrict__ x, const float* __restrict__ g, const flo
     const float nb = nrm[i / n];
     float v = x[i];
     if (nb != 0.f && scale != 0.f) v = fmaf(scale / nb, g[i], v);
-    bad |= !(fabsf(v) <= 3.0e38f);
+    bad |= nonfinite(v);
     out[i] = v;
   }
-  if (health && __any(bad) && (threadIdx.x & 63) == 0) atomicOr(health, 2u);
+  EDM_RAISE_HEALTH(health, bad, 2u);
 }
 
 }  // namespace

@@ -1795,7 +1795,7 @@ def aug_embed_wgrad(gemb_sigma, aug):
     return gw
 
 
-# ------------------------------------------------------------------ step-level kernels
+# ------------------------------------------------------------------ the training step (csrc/optim.hip)
 def diffuse(clean, P_mean, P_std, seed, step, dyn=None):
     _chk(clean, f32, "clean")
     B = clean.shape[0]
@@ -2110,6 +2110,7 @@ def phema_finish(acc):
     return out
 
 
+# ------------------------------------------------------------------ the updates of the samplers (csrc/solver_steps.hip)
 def heun_euler(x, D, t0, t1):
     _chk(x, f32, "x")
     _chk(D, f32, "D", x.shape)
@@ -2291,6 +2292,14 @@ def inpaint_blend(x, image, mask, t, rec, step):
     return out
 
 
+def scale_f32(x, s):
+    _chk(x, f32, "x")
+    y = torch.empty_like(x)
+    _lib.call("edm_scale_f32", _p(x), float(s), _p(y), x.numel(), _stream())
+    return y
+
+
+# ------------------------------------------------------------------ zero-shot restoration (csrc/restore.hip)
 RESTORE_SCALES = (1, 2, 4, 8)   # block sizes of the restoration operator (csrc/restore.hip)
 RESTORE_MAX_GRAY_CHANNELS = 8
 
@@ -2480,6 +2489,7 @@ def conv_in_dgrad(gy, wpack, gD, sigma, sigma_data):
     return gx
 
 
+# ------------------------------------------------------------------ likelihood and noise-level evaluation (csrc/sample_eval.hip)
 NLL_MAX_PROBES = 32             # a probe is one bit of a Philox word
 NLL_MAX_STEPS = 1 << 16         # step < 2**16 keeps the probe tags apart from the churn's and the blend's
 NLL_MAX_CHUNKS = 64             # EDM_NLL_MAX_CHUNKS: per-sample partial sums of the order-fixed reduction
@@ -2721,14 +2731,7 @@ def eval_sqerr_classes(D, clean, num_classes, out=None):
     return out
 
 
-def scale_f32(x, s):
-    _chk(x, f32, "x")
-    y = torch.empty_like(x)
-    _lib.call("edm_scale_f32", _p(x), float(s), _p(y), x.numel(), _stream())
-    return y
-
-
-# ------------------------------------------------------------------ reference-precision evaluation (csrc/eval_f32.hip)
+# ------------------------------------------------------------------ adaptive ODE solver (csrc/adaptive.hip)
 ADAPT_ROWS = 8                  # EDM_ADAPT_ROWS: 32-bit words of per-sample state of the adaptive solver
 ADAPT_ACTIVE, ADAPT_DONE, ADAPT_FAILED = 0, 1, 2
 
@@ -2815,8 +2818,9 @@ def adapt_correct(x, dx, x1, D1, t, t1, atol, rtol, part=None):
 
 
 def adapt_chunks(CHW: int) -> int:
-    """how many entries of a row of `part` a sample of CHW elements fills (a function of CHW alone)"""
-    return min(((CHW + 3) // 4 + 255) // 256, NLL_MAX_CHUNKS)
+    """how many entries of a row of `part` a sample of CHW elements fills (a function of CHW alone): the rule the kernels
+    index with, asked of the library (edm_sample_chunks; host logic, no launch)"""
+    return int(_lib.call("edm_sample_chunks", int(CHW)))
 
 
 def adapt_control(part, CHW, state, t_end, active, *, safety=0.9, fac_min=0.2, fac_max=5.0, h_floor=1e-6, accept=None):
@@ -3045,6 +3049,7 @@ def picard_slide(Xnew, D, stride, state, t_table, *, N, X=None, T=None):
     return X, T
 
 
+# ------------------------------------------------------------------ reference-precision evaluation (csrc/eval_f32.hip)
 def _nhwc32(t, name):
     _chk(t, f32, name)
     if t.dim() != 4:

@@ -1017,6 +1017,55 @@ class MultistepSolver(DeterministicSolver):
                                  m_out=hist[i % L] if L and i < self.num_steps - 1 else None)
 
 
+class _IteratedSolver(DeterministicSolver):
+    """What AdaptiveSolver and ParallelSolver share on the host: both integrate the plain table's span with plain guidance
+    and refuse the rest.  _REFUSAL is the subclass's one sentence, "<the ... solver> (<what it does instead>)"."""
+    _REFUSAL: str
+
+    def _refuse(self, who: str, **given) -> None:
+        for name, on in given.items():
+            if on:
+                raise ValueError(f"{type(self).__name__}.{who}: {name} is not implemented for {self._REFUSAL}; use "
+                                 "DeterministicSolver")
+
+    def _check_tolerances(self) -> None:
+        for name in ("rtol", "atol"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
+                raise ValueError(f"{type(self).__name__}: {name} must be a finite number >= 0, got {v!r}")
+
+    def _check_span(self) -> None:
+        lo, hi = self.t_steps[self.num_steps - 1].item(), self.t_steps[0].item()
+        if not (math.isfinite(lo) and math.isfinite(hi) and 0 < lo < hi):
+            raise ValueError(f"{type(self).__name__}: needs 0 < sigma_min < sigma_max, got {self.sigma_min}, "
+                             f"{self.sigma_max}")
+
+    @staticmethod
+    def _check_batch(who: str, name: str, t) -> None:
+        _check_float(who, name, t)
+        if t.dim() < 2 or t.numel() == 0:
+            raise ValueError(f"{who}: {name} must be a non-empty [B, ...] tensor, got {tuple(t.shape)}")
+
+    def _mixed_evaluation(self, model, class_labels, guided: bool, w_dev, calls=None):
+        """evaluate(x, sigma) -> D of the model, with plain guidance D = Dg + w (Dm - Dg) mixed on the device; calls
+        (optional [network, guide] list) counts the batch calls"""
+        def evaluate(xs, sigma):
+            if calls is not None:
+                calls[0] += 1
+                calls[1] += int(guided)
+            D = model(xs, sigma, class_labels).float().contiguous()
+            if not guided:
+                return D
+            Dg = self._guide_eval(model, xs, sigma, class_labels)
+            return ops.dpm_multistep(xs, D, 0.0, 1.0, 0.0, 0.0, Dg=Dg, w_dev=w_dev)     # (the mix, bit for bit)
+        return evaluate
+
+    @staticmethod
+    def _closing_step(evaluate, x, sigma, t: float):
+        """the table's closing Euler step t -> 0 (sigma: t on the device): one batch evaluation"""
+        return ops.heun_euler(x, evaluate(x, sigma), t, 0.0)[1]
+
+
 class AdaptiveStats(NamedTuple):
     """what the last adaptive solve did (AdaptiveSolver.last_stats)"""
     accepted: torch.Tensor      # int64 [B] on the host: accepted steps per sample
@@ -1026,7 +1075,7 @@ class AdaptiveStats(NamedTuple):
     guide_evaluations: int      # calls of the guide, counted apart
 
 
-class AdaptiveSolver(DeterministicSolver):
+class AdaptiveSolver(_IteratedSolver):
     """The probability-flow ODE integrated to a tolerance instead of on a table: the embedded Heun(2) / Euler(1) pair
     with local extrapolation, every sample at its own time and step size, the step controller on the device
     (csrc/adaptive.hip).  A trial step from t to t1 takes the Euler result x1 and the Heun result y, measures
@@ -1048,6 +1097,8 @@ class AdaptiveSolver(DeterministicSolver):
     degradation, operator / dps_scale, end_step and log_likelihood, on the host before any launch.  RuntimeError when
     ``max_iterations`` is reached with samples still active or a sample's step fell under ``h_floor`` |t|.
     ``last_stats`` (AdaptiveStats) describes the last solve or inversion."""
+
+    _REFUSAL = "the adaptive solver (it integrates sigma_max <-> sigma_min eagerly, every sample at its own sigma)"
 
     def __init__(self, num_steps: int = 18, sigma_min: float = 0.002, sigma_max: float = 80.0, rho: float = 7.0,
                  dtype: str | None = None, *, guide=None, guidance: float = 1.0,
@@ -1073,19 +1124,14 @@ class AdaptiveSolver(DeterministicSolver):
         return (any(flags),)
 
     def _check_adaptive(self) -> None:
-        for name in ("rtol", "atol"):
-            v = getattr(self, name)
-            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
-                raise ValueError(f"AdaptiveSolver: {name} must be a finite number >= 0, got {v!r}")
+        self._check_tolerances()
         if not self.rtol + self.atol > 0:
             raise ValueError("AdaptiveSolver: rtol and atol must not both be 0")
         m = self.max_iterations
         if isinstance(m, bool) or not isinstance(m, int) or m < 1:
             raise ValueError(f"AdaptiveSolver: max_iterations must be an integer >= 1, got {m!r}")
         ops.check_controller(self.safety, self.fac_min, self.fac_max, self.h_floor)
-        lo, hi = self.t_steps[self.num_steps - 1].item(), self.t_steps[0].item()
-        if not (math.isfinite(lo) and math.isfinite(hi) and 0 < lo < hi):
-            raise ValueError(f"AdaptiveSolver: needs 0 < sigma_min < sigma_max, got {self.sigma_min}, {self.sigma_max}")
+        self._check_span()
 
     def span(self, upwards: bool = False) -> tuple[float, float, float]:
         """(t_start, t_end, h0) of ``solve`` (or of ``invert``, upwards) as the fp32 table values"""
@@ -1093,28 +1139,13 @@ class AdaptiveSolver(DeterministicSolver):
         N = self.num_steps
         return (ts[N - 1], ts[0], ts[N - 2] - ts[N - 1]) if upwards else (ts[0], ts[N - 1], ts[1] - ts[0])
 
-    @staticmethod
-    def _refuse(who: str, **given) -> None:
-        for name, on in given.items():
-            if on:
-                raise ValueError(f"AdaptiveSolver.{who}: {name} is not implemented for the adaptive solver (it integrates "
-                                 "sigma_max <-> sigma_min eagerly, every sample at its own sigma); use DeterministicSolver")
-
     def _integrate(self, model, x, class_labels, span, guided, w_dev, who):
         """x (fp32, owned: advanced in place) from t_start to t_end; returns x and the counting evaluation of (x, sigma),
         guidance mix included; last_stats is written"""
         t_start, t_end, h0 = span
         B, CHW, dev = x.shape[0], x.numel() // x.shape[0], x.device
         calls = [0, 0]
-
-        def evaluate(xs, sigma):
-            calls[0] += 1
-            D = model(xs, sigma, class_labels).float().contiguous()
-            if not guided:
-                return D
-            calls[1] += 1
-            Dg = self._guide_eval(model, xs, sigma, class_labels)
-            return ops.dpm_multistep(xs, D, 0.0, 1.0, 0.0, 0.0, Dg=Dg, w_dev=w_dev)     # (the mix, bit for bit)
+        evaluate = self._mixed_evaluation(model, class_labels, guided, w_dev, calls)
         state = ops.adapt_begin(B, t_start, t_end, h0, dev)
         rows = ops.adapt_rows(state)
         active = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -1154,9 +1185,7 @@ class AdaptiveSolver(DeterministicSolver):
                                  "measurement": measurement is not None, "operator": operator is not None,
                                  "dps_scale": dps_scale is not None})
         guided, = self.guided_evaluations()
-        _check_float("solve", "x0", x0)
-        if x0.dim() < 2 or x0.numel() == 0:
-            raise ValueError(f"solve: x0 must be a non-empty [B, ...] tensor, got {tuple(x0.shape)}")
+        self._check_batch("solve", "x0", x0)
         _check_gpu("AdaptiveSolver", "x0", x0)
         if guided:
             self._check_guide(model, x0.device, class_labels)
@@ -1164,9 +1193,7 @@ class AdaptiveSolver(DeterministicSolver):
         w_dev = torch.full((1,), float(self.guidance), device=x0.device) if guided else None
         x = ops.scale_f32(x0.float().contiguous(), span[0])
         x, evaluate = self._integrate(model, x, class_labels, span, guided, w_dev, "solve")
-        # the table's closing Euler step sigma_min -> 0: one batch evaluation
-        D = evaluate(x, torch.full((1,), span[1], device=x.device))
-        out = ops.heun_euler(x, D, span[1], 0.0)[1]
+        out = self._closing_step(evaluate, x, torch.full((1,), span[1], device=x.device), span[1])
         self.last_stats = self.last_stats._replace(evaluations=self.last_stats.evaluations + 1,
                                                    guide_evaluations=self.last_stats.guide_evaluations + int(guided))
         ops.check_health(x.device, "AdaptiveSolver.solve")
@@ -1178,9 +1205,7 @@ class AdaptiveSolver(DeterministicSolver):
         returns the unit-scale latent x / sigma_max.  Only D_main is evaluated (``guide`` and ``guidance`` are ignored)."""
         self._refuse("invert", **{"graph=True": graph, "end_step": end_step != 0})
         self._check_adaptive()
-        _check_float("invert", "image", image)
-        if image.dim() < 2 or image.numel() == 0:
-            raise ValueError(f"invert: image must be a non-empty [B, ...] tensor, got {tuple(image.shape)}")
+        self._check_batch("invert", "image", image)
         _check_gpu("AdaptiveSolver", "image", image)
         span = self.span(upwards=True)
         x = image.float().contiguous().clone()
@@ -1216,7 +1241,7 @@ class _PicardState(NamedTuple):
     t_dev: torch.Tensor     # the sigma table on the device
 
 
-class ParallelSolver(DeterministicSolver):
+class ParallelSolver(_IteratedSolver):
     """The table solver's result computed in parallel over time (ParaDiGMS: Shih et al. 2023): Picard iteration of the
     Heun step (``order=2``) or the Euler step (``order=1``) of DeterministicSolver's table t_0 .. t_N over a window of
     ``window`` = P consecutive steps.  Every sample b holds the states at table indices s_b .. s_b + P as unknowns; one
@@ -1241,6 +1266,8 @@ class ParallelSolver(DeterministicSolver):
     from device memory.  ``guidance_interval`` raises ValueError, and so do start_step, image, mask, degradation,
     measurement, operator, dps_scale, invert and log_likelihood, on the host before any launch.
     ``last_stats`` (ParallelStats) describes the last solve."""
+
+    _REFUSAL = "the parallel solver (it iterates the plain table solve over a window of steps)"
 
     def __init__(self, num_steps: int = 18, sigma_min: float = 0.002, sigma_max: float = 80.0, rho: float = 7.0,
                  dtype: str | None = None, *, window: int = 16, order: int = 2, rtol: float = 1e-3, atol: float = 1e-4,
@@ -1269,20 +1296,8 @@ class ParallelSolver(DeterministicSolver):
             raise ValueError(f"ParallelSolver: window must be an integer in 1 .. {ops.PICARD_MAX_WINDOW}, got {P!r}")
         if isinstance(self.order, bool) or self.order not in (1, 2):
             raise ValueError(f"ParallelSolver: order must be 1 (Euler) or 2 (Heun), got {self.order!r}")
-        for name in ("rtol", "atol"):
-            v = getattr(self, name)
-            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v) or v < 0:
-                raise ValueError(f"ParallelSolver: {name} must be a finite number >= 0, got {v!r}")
-        lo, hi = self.t_steps[self.num_steps - 1].item(), self.t_steps[0].item()
-        if not (math.isfinite(lo) and math.isfinite(hi) and 0 < lo < hi):
-            raise ValueError(f"ParallelSolver: needs 0 < sigma_min < sigma_max, got {self.sigma_min}, {self.sigma_max}")
-
-    @staticmethod
-    def _refuse(who: str, **given) -> None:
-        for name, on in given.items():
-            if on:
-                raise ValueError(f"ParallelSolver.{who}: {name} is not implemented for the parallel solver (it iterates the "
-                                 "plain table solve over a window of steps); use DeterministicSolver")
+        self._check_tolerances()
+        self._check_span()
 
     def _picard_state(self, x0) -> _PicardState:
         """the device state of a solve from x0 (fp32 unit noise), the window at the head of the table"""
@@ -1301,13 +1316,7 @@ class ParallelSolver(DeterministicSolver):
         P, B = st.X.shape[0] - 1, st.X.shape[1]
         rows = st.X[:P].view(P * B, *st.X.shape[2:])        # positions 0 .. P-1: one contiguous network batch
         t, t1 = st.T[:P].view(-1), st.T[1:].view(-1)
-
-        def evaluate(xs, sigma):
-            D = model(xs, sigma, labels).float().contiguous()
-            if not guided:
-                return D
-            Dg = self._guide_eval(model, xs, sigma, labels)
-            return ops.dpm_multistep(xs, D, 0.0, 1.0, 0.0, 0.0, Dg=Dg, w_dev=w_dev)     # (the mix, bit for bit)
+        evaluate = self._mixed_evaluation(model, labels, guided, w_dev)
         D = evaluate(rows, t)
         dx, X1 = ops.adapt_euler(rows, D, t, t1)
         D1 = evaluate(X1, t1) if order == 2 else None
@@ -1323,9 +1332,7 @@ class ParallelSolver(DeterministicSolver):
                                  "degradation": degradation is not None, "measurement": measurement is not None,
                                  "operator": operator is not None, "dps_scale": dps_scale is not None})
         guided, = self.guided_evaluations()
-        _check_float("solve", "x0", x0)
-        if x0.dim() < 2 or x0.numel() == 0:
-            raise ValueError(f"solve: x0 must be a non-empty [B, ...] tensor, got {tuple(x0.shape)}")
+        self._check_batch("solve", "x0", x0)
         if not x0.is_cuda or (class_labels is not None and not class_labels.is_cuda):
             raise ValueError("tinyedm_amd.ParallelSolver: x0 and class_labels must be GPU tensors (there is no CPU path)")
         if guided:
@@ -1359,12 +1366,8 @@ class ParallelSolver(DeterministicSolver):
             total = int(st.active.item())           # the one host read of an iteration: 4 bytes
             seen, left = total, total - seen
         # the table's closing Euler step t_{N-1} -> 0: one evaluation at batch B
-        ts = self.t_steps.tolist()
-        x, sigma = st.X[0], st.t_dev[N - 1:N]
-        D = model(x, sigma, class_labels).float().contiguous()
-        if guided:
-            D = ops.dpm_multistep(x, D, 0.0, 1.0, 0.0, 0.0, Dg=self._guide_eval(model, x, sigma, class_labels), w_dev=w_dev)
-        out = ops.heun_euler(x, D, ts[N - 1], 0.0)[1]
+        out = self._closing_step(self._mixed_evaluation(model, class_labels, guided, w_dev), st.X[0], st.t_dev[N - 1:N],
+                                 self.t_steps[N - 1].item())
         evaluations = order * iterations + 1
         self.last_stats = ParallelStats(iterations, evaluations, evaluations if guided else 0,
                                         order * iterations * P * B + B, order * (N - 1) + 1, st.state[2].cpu().long())
