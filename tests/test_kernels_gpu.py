@@ -721,7 +721,8 @@ def test_step_level_kernels(ops):
     noisy_ref, sigma_ref = O.diffuse(clean, eps, noise, -1.2, 1.2)
     noisy, sigma = ops.diffuse_given(clean.to(DEV), eps.to(DEV), noise.to(DEV), -1.2, 1.2)
     assert torch.allclose(noisy.cpu(), noisy_ref, rtol=1e-5, atol=1e-5) and torch.allclose(sigma.cpu(), sigma_ref, rtol=1e-5)
-    # Philox diffuser: distribution of ln(sigma) and of the unit noise (RNG parity is distributional)
+    # Philox diffuser: distribution of ln(sigma) and of the unit noise (the streams themselves, the dropout mask and the
+    # Adam + EMA forms element by element against exact restatements: tests/test_step_exact_gpu.py)
     big = torch.zeros(4096, 3, 8, 8, device=DEV)
     nz, sg = ops.diffuse(big, -1.2, 1.2, 42, 3)
     ls = sg.log()

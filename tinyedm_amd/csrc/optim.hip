@@ -37,14 +37,16 @@ __global__ void k_diffuse(const float* __restrict__ clean, float* __restrict__ n
   }
 }
 
-// same with the two normal draws supplied (deterministic tests / external RNG)
+// same with the two normal draws supplied (deterministic tests / external RNG).  Not on the training path, and what other
+// code is compared against: sigma is exp(P_mean + P_std*eps) evaluated in double and rounded once (half an ulp).  In
+// fp32 the rounding of the argument alone is up to 2 u of sigma at |argument| in [2, 4) and the device expf adds 2-3 u more.
 __global__ void k_diffuse_given(const float* __restrict__ clean, const float* __restrict__ eps,
                                 const float* __restrict__ noise, float* __restrict__ noisy, float* __restrict__ sigma,
                                 float P_mean, float P_std, int B, long CHW) {
   const long total = (long)B * CHW;
   for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
     const int b = (int)(e / CHW);
-    const float s = expf(P_mean + P_std * eps[b]);
+    const float s = (float)exp((double)P_mean + (double)P_std * (double)eps[b]);
     noisy[e] = clean[e] + s * noise[e];
     if (e % CHW == 0) sigma[b] = s;
   }
