@@ -648,7 +648,14 @@ def _qkv_perm(C, heads):
     # head dims of the other reference configs (streamed-operand kernels, attention_generic.hip):
     # MNIST 512/4 @7x7, ImageNet-64 576/4 @16x16 and 768/4 @8x8, plus ragged token counts
     (2, 7, 7, 2, 128), (1, 16, 16, 2, 144), (2, 8, 8, 2, 192), (1, 14, 14, 1, 144), (2, 5, 5, 1, 32), (1, 12, 12, 1, 192),
-    (1, 16, 16, 1, 128)])
+    (1, 16, 16, 1, 128),
+    # head dim 64, the dispatch on nt = ceil(N / 32): NT = 4 (65..128 tokens) masked, NT = 4 with every tile full (N = 128), a
+    # last tile that holds one token at NT = 4 / 2 / 8 (N = 65, 33, 225), NT = 1 full (N = 32), a single token
+    (1, 10, 10, 2, 64), (2, 8, 16, 1, 64), (1, 5, 13, 1, 64), (1, 3, 11, 1, 64), (1, 15, 15, 1, 64), (1, 4, 8, 1, 64),
+    (1, 1, 1, 1, 64),
+    # the other head dims at NT = 4, masked (N = 100) and full (N = 128); head dim 32 above 64 tokens; a single token
+    (1, 10, 10, 1, 32), (1, 8, 16, 1, 32), (1, 10, 10, 1, 128), (1, 8, 16, 1, 128), (1, 10, 10, 1, 144), (1, 8, 16, 1, 144),
+    (1, 10, 10, 1, 192), (1, 8, 16, 1, 192), (1, 16, 16, 2, 32), (1, 1, 1, 1, 128)])
 def test_attention_fwd_bwd(ops, B, H, W, heads, hd):
     g = torch.Generator().manual_seed(B + H + heads + hd)
     C = hd * heads

@@ -642,7 +642,8 @@ __global__ void k_nhwc_to_nchw_f32(const float* __restrict__ x, float* __restric
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ split-bf16 operands
-// An fp32 value as a PAIR of bf16: hi = bf16(x) (round to nearest even), lo = bf16(x - hi): x = hi + lo up to 2^-18 |x|.
+// An fp32 value as a PAIR of bf16: hi = bf16(x) (round to nearest even), lo = bf16(x - hi): x = hi + lo up to 2^-17 |x|
+// (x - hi is exact and below 2^-8 |x|; its own rounding to 8 significant bits loses at most 2^-9 of it).
 // Activations: [rows][C] floats -> [rows][2 C] bf16 = [hi | lo] (the same bytes).  Weights: w_hat [O][I * taps] (master
 // order) -> [taps][O][3 Ip] = [w_hi | w_lo | w_hi].  edm_split_conv (conv_dispatch.hip) multiplies them in three bf16 passes.
 namespace {
