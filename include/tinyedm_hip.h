@@ -1029,6 +1029,37 @@ int edm_poly_sums_partial(const void* a, int dtype_a, const long* idx_a, const v
                           double* partial, edm_stream_t stream);
 int edm_poly_sums_finish(const double* partial, int S, long tiles, double* sums, edm_stream_t stream);
 
+/* ---------------------------------------------------------------- feature-space nearest neighbours (csrc/neighbors_f32.hip) */
+/* The float32 form of the exact search above, for the feature spaces in which precision and recall (Kynkaanniemi et al.
+ * 2019) and density and coverage (Naeem et al. 2020) were defined; the reference has no call site for it.  Distances are
+ * fp64 on v_mfma_f64_16x16x4_f64 (the tile engine of the moments above): d2 = fmax((|q|^2 + |r|^2) - 2 q.r, 0), float32
+ * products exact, only the sums round.  The bits of d2(q, r) depend on the two rows and D only -- not on tile position,
+ * splits, chunking, the load path (16-byte loads when a base is 16-byte aligned and D % 4 == 0, element loads otherwise) or
+ * on which kernel computes them -- and identical rows give +0.0 exactly.  The order is the pair (bit pattern of d2 as
+ * uint64, reference index), ties to the lower index.  No atomics; every output element is written by an ordinary store.
+ * Input must be finite (the caller's check).  Limits, status -1 otherwise: 1 <= k <= 32, k <= R (k <= R - 1 with
+ * exclude_self) unless partial, 1 <= D <= 32768, Q <= 65535 * 64, ref_base + R <= 2^31 - 64, 1 <= splits <= 1024.
+ * edm_f32_knn_splits: the number of shares of the R axis the library would give a Q x R search (host logic only).
+ * edm_f32_norms: norms fp64 [n_rows] = |x|^2 with the bits of the distance tile's x.x (the tile run on the rows against
+ *   themselves, the diagonal kept); the qnorms / rnorms of the two calls below.
+ * edm_f32_knn_partial: writes keys_d2 uint64 [splits][Q][k] (bit patterns of d2) and keys_idx int32 [splits][Q][k]
+ *   (ref_base + reference row), each list ascending, unused slots (all-ones, -1).  Arguments as in edm_u8_knn_partial.
+ * edm_fknn_merge: n_lists lists per query (splits of one call or of every chunk, end to end) -> dist fp64 [Q][k],
+ *   idx int32 [Q][k], ascending by (d2, idx).
+ * edm_f32_ball_count_partial: counts int32 [splits][Q], counts[s][q] = the number of references r in share s with
+ *   d2(q, r) <= radii[r] (closed compare in fp64; radii fp64 [R], finite and >= 0); an empty share writes 0 and the caller
+ *   adds the shares as integers.  Arguments as in edm_u8_ball_count_partial. */
+int edm_f32_knn_splits(long Q, long R);
+int edm_f32_norms(const void* x, long n_rows, int D, double* norms, edm_stream_t stream);
+int edm_f32_knn_partial(const void* queries, const void* refs, long Q, long R, int D, int k, int exclude_self, long ref_base,
+                        int partial, int splits, const double* qnorms, const double* rnorms, unsigned long long* keys_d2,
+                        int* keys_idx, edm_stream_t stream);
+int edm_fknn_merge(const unsigned long long* keys_d2, const int* keys_idx, int n_lists, long Q, int k, double* dist, int* idx,
+                   edm_stream_t stream);
+int edm_f32_ball_count_partial(const void* queries, const void* refs, long Q, long R, int D, const double* radii,
+                               int exclude_self, long ref_base, int splits, const double* qnorms, const double* rnorms,
+                               int* counts, edm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

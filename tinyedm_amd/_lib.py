@@ -224,6 +224,12 @@ SIGNATURES = {
     "edm_moments_finish": [P, P, I, I, P, P, P],
     "edm_poly_sums_partial": [P, I, P, P, I, P, I, L, L, I, D, D, I, I, P, P],
     "edm_poly_sums_finish": [P, I, L, P, P],
+    # neighbors_f32.hip
+    "edm_f32_knn_splits": [L, L],
+    "edm_f32_norms": [P, L, I, P, P],
+    "edm_f32_knn_partial": [P, P, L, L, I, I, I, L, I, I, P, P, P, P, P],
+    "edm_fknn_merge": [P, P, I, L, I, P, P, P],
+    "edm_f32_ball_count_partial": [P, P, L, L, I, P, I, L, I, P, P, P, P],
 }
 # include/tinyedm_hip_diag.h: tools-only entry points, bound on demand by call()
 DIAG_SIGNATURES = {
@@ -241,7 +247,7 @@ _NO_STATUS = {"edm_lowrank_wgrad_workspace", "edm_lowrank_supported", "edm_lowra
               "edm_wgrad3_apply_table_bytes",
               "edm_conv_wgrad_1x1_group_table_bytes", "edm_wgrad_finish_multi_table_bytes", "edm_attention_qkv_supported",
               "edm_attention_long_supported", "edm_conv_in_dgrad_pack_cols",
-              "edm_u8_knn_splits", "edm_moments_splits", "edm_sample_chunks"}
+              "edm_u8_knn_splits", "edm_moments_splits", "edm_sample_chunks", "edm_f32_knn_splits"}
 
 _lib = None
 

@@ -3609,6 +3609,138 @@ def u8_ball_count(queries, refs, radii, exclude_self=False, splits=None, *, ref_
     return counts.sum(0, dtype=torch.int64)
 
 
+# ------------------------------------------------------------------ feature-space nearest neighbours (csrc/neighbors_f32.hip)
+FKNN_MAX_Q = 65535 * 64      # one grid row per 64 queries
+FKNN_MAX_R = 2 ** 31 - 64    # row numbers of the last 64-reference tile stay 32-bit ints
+
+
+def _fknn_rows(t, name):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: expected a tensor, got {type(t).__name__}")
+    if t.dtype != f32:
+        raise TypeError(f"{name}: expected float32 features, got {t.dtype} (convert with .float(); uint8 pixels go to the "
+                        "u8 form)")
+    if t.dim() < 2 or t.numel() == 0:
+        raise ValueError(f"{name}: expected a non-empty [N, ...] tensor, got {tuple(t.shape)}")
+    _chk(t, f32, name)
+    return t.view(t.shape[0], -1)
+
+
+def fknn_check(Q, R, D, k, exclude_self=False):
+    """the limits of a feature search of Q queries against R references of D elements, as the library states them"""
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"f32_knn: k must be an integer in [1, {KNN_MAX_K}], got {k!r}")
+    if not 1 <= D <= KNN_MAX_D:
+        raise ValueError(f"f32_knn: rows must hold 1 to {KNN_MAX_D} elements, got {D}")
+    if not 1 <= Q <= FKNN_MAX_Q:
+        raise ValueError(f"f32_knn: expected 1 to {FKNN_MAX_Q} queries, got {Q}")
+    if not 1 <= R <= FKNN_MAX_R:
+        raise ValueError(f"f32_knn: expected 1 to 2^31 - 64 references, got {R}")
+    if k > R - (1 if exclude_self else 0):
+        raise ValueError(f"f32_knn: k = {k} needs at least that many references"
+                         f"{' besides the query itself' if exclude_self else ''}, got R = {R}")
+
+
+def f32_knn_splits(Q, R) -> int:
+    """the split count of the R axis the library picks for a Q x R feature search"""
+    return int(_lib.call("edm_f32_knn_splits", int(Q), int(R)))
+
+
+def _fknn_plan(who, queries, refs, k, exclude_self, splits, ref_chunk):
+    """the shared validation of f32_knn and f32_ball_count -> (q2, r2, chunk bounds, shares per chunk)"""
+    if isinstance(queries, torch.Tensor) and isinstance(refs, torch.Tensor) and refs.device != queries.device:
+        raise ValueError(f"{who}: queries on {queries.device}, refs on {refs.device}")
+    q2, r2 = _fknn_rows(queries, "queries"), _fknn_rows(refs, "refs")
+    if queries.shape[1:] != refs.shape[1:]:
+        raise ValueError(f"{who}: queries {tuple(queries.shape[1:])} and refs {tuple(refs.shape[1:])} differ in shape")
+    (Q, D), R = q2.shape, r2.shape[0]
+    fknn_check(Q, R, D, k, exclude_self)
+    if ref_chunk is not None and (isinstance(ref_chunk, bool) or not isinstance(ref_chunk, int) or ref_chunk < 1):
+        raise ValueError(f"{who}: ref_chunk must be None or an integer >= 1, got {ref_chunk!r}")
+    chunk = R if ref_chunk is None else min(ref_chunk, R)
+    bounds = [(a, min(a + chunk, R)) for a in range(0, R, chunk)]
+    if splits is None:
+        shares = [f32_knn_splits(Q, b - a) for a, b in bounds]
+    elif isinstance(splits, bool) or not isinstance(splits, int) or not 1 <= splits <= KNN_MAX_SPLITS:
+        raise ValueError(f"{who}: splits must be an integer in [1, {KNN_MAX_SPLITS}], got {splits!r}")
+    else:
+        shares = [splits] * len(bounds)
+    return q2, r2, bounds, shares
+
+
+def f32_norms(x):
+    """fp64 [N]: |x|^2 of the rows of a float32 [N, ...] tensor with the bits of the distance tile's x . x (edm_f32_norms), so
+    that identical rows are at distance +0.0 exactly"""
+    x2 = _fknn_rows(x, "x")
+    if not 1 <= x2.shape[1] <= KNN_MAX_D or x2.shape[0] > FKNN_MAX_R:
+        raise ValueError(f"f32_norms: expected at most 2^31 - 64 rows of 1 to {KNN_MAX_D} elements, got {tuple(x2.shape)}")
+    out = torch.empty(x2.shape[0], dtype=torch.float64, device=x.device)
+    _lib.call("edm_f32_norms", _p(x2), x2.shape[0], x2.shape[1], _p(out), _stream())
+    return out
+
+
+def _fknn_norms(q2, r2):
+    """the norms of both sets (one launch when the references are the queries)"""
+    qn = f32_norms(q2)
+    same = q2.data_ptr() == r2.data_ptr() and q2.shape == r2.shape
+    return qn, (qn if same else f32_norms(r2))
+
+
+def f32_knn(queries, refs, k, exclude_self=False, splits=None, *, ref_chunk=None):
+    """The k nearest rows of refs (float32 [R, ...]) for every row of queries (float32 [Q, ...], same trailing shape; inputs
+    of any rank >= 2 are taken as [N, D]) by squared Euclidean distance in fp64, d2 = max(|q|^2 + |r|^2 - 2 q.r, 0), ties to
+    the lower index -> (dist fp64 [Q, k], idx int64 [Q, k]), ascending by (dist, idx).  exclude_self, splits and ref_chunk as
+    in u8_knn; the bits of a distance depend on the two rows only, so the result depends on neither splits nor ref_chunk.
+    The input must be finite (the callers that take a set in check it once; nothing is scanned per call)."""
+    q2, r2, bounds, shares = _fknn_plan("f32_knn", queries, refs, k, exclude_self, splits, ref_chunk)
+    (Q, D), dev = q2.shape, queries.device
+    qn, rn = _fknn_norms(q2, r2)
+    n = sum(shares)
+    keys_d2 = torch.empty(n, Q, k, dtype=torch.uint64, device=dev)
+    keys_idx = torch.empty(n, Q, k, dtype=torch.int32, device=dev)
+    at = 0
+    for (a, b), s in zip(bounds, shares):
+        _lib.call("edm_f32_knn_partial", _p(q2), _p(r2[a:b]), Q, b - a, D, k, int(bool(exclude_self)), a,
+                  int(len(bounds) > 1), s, _p(qn), _p(rn[a:b]), _p(keys_d2[at:at + s]), _p(keys_idx[at:at + s]), _stream())
+        at += s
+    dist = torch.empty(Q, k, dtype=torch.float64, device=dev)
+    idx = torch.empty(Q, k, dtype=torch.int32, device=dev)
+    _lib.call("edm_fknn_merge", _p(keys_d2), _p(keys_idx), at, Q, k, _p(dist), _p(idx), _stream())
+    return dist, idx.to(torch.int64)
+
+
+def ball_radii_f64(radii, R):
+    """radii: an fp64 tensor [R], finite and >= 0 -> contiguous (f32_ball_count's check)"""
+    if not isinstance(radii, torch.Tensor) or radii.dtype != torch.float64:
+        raise ValueError(f"f32_ball_count: radii must be a float64 tensor, got "
+                         f"{radii.dtype if isinstance(radii, torch.Tensor) else type(radii).__name__}")
+    if tuple(radii.shape) != (R,):
+        raise ValueError(f"f32_ball_count: radii must have shape ({R},), one per reference, got {tuple(radii.shape)}")
+    if not bool((torch.isfinite(radii) & (radii >= 0)).all()):
+        raise ValueError("f32_ball_count: radii must be finite and >= 0")
+    return radii.contiguous()
+
+
+def f32_ball_count(queries, refs, radii, exclude_self=False, splits=None, *, ref_chunk=None):
+    """For every row of queries (float32 [Q, ...]) the number of rows r of refs (float32 [R, ...], same trailing shape) whose
+    closed ball holds it: d2(q, r) <= radii[r], d2 as in f32_knn (the same bits: a radius taken from f32_knn is compared
+    with the very number it was) -> int64 [Q].  radii: fp64 [R], finite and >= 0.  exclude_self, splits and ref_chunk as in
+    u8_ball_count: every share of every chunk writes its own int32 counts and one integer sum folds them."""
+    q2, r2, bounds, shares = _fknn_plan("f32_ball_count", queries, refs, 1, False, splits, ref_chunk)
+    (Q, D), R, dev = q2.shape, r2.shape[0], queries.device
+    if not isinstance(radii, torch.Tensor) or radii.device != refs.device:
+        raise ValueError(f"f32_ball_count: radii must be a tensor on {refs.device}")
+    rad = ball_radii_f64(radii, R)
+    qn, rn = _fknn_norms(q2, r2)
+    counts = torch.empty(sum(shares), Q, dtype=torch.int32, device=dev)
+    at = 0
+    for (a, b), s in zip(bounds, shares):
+        _lib.call("edm_f32_ball_count_partial", _p(q2), _p(r2[a:b]), Q, b - a, D, _p(rad[a:b]), int(bool(exclude_self)), a, s,
+                  _p(qn), _p(rn[a:b]), _p(counts[at:at + s]), _stream())
+        at += s
+    return counts.sum(0, dtype=torch.int64)
+
+
 # ------------------------------------------------------------------ ideal denoiser of a training set (csrc/ideal.hip)
 IDEAL_MAX_K = 32768              # elements per image (edm_u8_norms' limit: |u - 128|^2 summed in an int)
 IDEAL_MAX_Q = 65535 * 64         # one grid row per 64 queries

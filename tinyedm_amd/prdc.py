@@ -23,6 +23,14 @@ that fresh data gets (`--holdout`: at finite sample sizes real against real is b
     python -m tinyedm.prdc --image_dir samples --dataset cifar10 --data_dir datasets/cifar --k 3 5 10 --holdout \\
         --report prdc.json
 
+The feature-space form, the one the two papers define: float32 [n, D] features extracted elsewhere (the arrays
+`tinyedm.frechet --features` takes; no extractor ships here) in place of the images.  The same definitions then run on fp64
+squared Euclidean distances (csrc/neighbors_f32.hip: ops.f32_knn, ops.f32_ball_count; the k-th neighbour radius of the search
+is bit for bit the number the ball count compares against), and only the ratios' inputs are floats:
+
+    python -m tinyedm.prdc --features samples.npy --ref_features train.npy --holdout_features test.npy \\
+        --labels_json drawn.json --ref_labels train_labels.json --k 3 5 10 --report prdc.json
+
 check_k, radii_from_knn, metrics_from_counts, per_class and check_args are plain numpy on the host and need no GPU.
 """
 from __future__ import annotations
@@ -33,7 +41,7 @@ import os
 
 import numpy as np
 
-from .neighbors import MAX_K, _read_dataset, load_images_u8
+from .neighbors import FEATURE_SPACE, MAX_K, _read_dataset, as_set, feature_form, load_images_u8, read_feature_sets
 
 RATIOS = ("precision", "recall", "density", "coverage")
 
@@ -71,9 +79,18 @@ def radii_from_knn(dist, ks) -> dict:
 def metrics_from_counts(hits_x, hits_y, near_y, r_x, k: int) -> dict:
     """hits_x [N] (per sample, the real balls that hold it), hits_y [M] (per real, the sample balls that hold it), near_y [M]
     (per real, d2 to its nearest sample), r_x [M] (the reals' radii at this k) -> the four ratios, their integer numerators
-    and the set sizes"""
+    and the set sizes.  Float near_y and r_x (the feature form: fp64 distances as the search returned them) are compared as
+    fp64, both lists then being floats; integer ones as int64."""
     hx, hy = np.asarray(hits_x, dtype=np.int64).reshape(-1), np.asarray(hits_y, dtype=np.int64).reshape(-1)
-    ny, rx = np.asarray(near_y, dtype=np.int64).reshape(-1), np.asarray(r_x, dtype=np.int64).reshape(-1)
+    ny, rx = np.asarray(near_y), np.asarray(r_x)
+    if ny.dtype.kind == "f" or rx.dtype.kind == "f":
+        if ny.dtype.kind != "f" or rx.dtype.kind != "f":
+            raise ValueError("metrics_from_counts: near_y and r_x must both be float (feature) or both integer (pixel) distances")
+        ny, rx = ny.astype(np.float64).reshape(-1), rx.astype(np.float64).reshape(-1)
+        if not (np.isfinite(ny).all() and np.isfinite(rx).all()):
+            raise ValueError("metrics_from_counts: non-finite distances")
+    else:
+        ny, rx = ny.astype(np.int64).reshape(-1), rx.astype(np.int64).reshape(-1)
     (k,) = check_k(k)
     N, M = int(hx.size), int(hy.size)
     if N < 1 or M < 1 or ny.size != M or rx.size != M:
@@ -116,26 +133,31 @@ def per_class(score, real, fake, real_labels, fake_labels, ks) -> dict:
 
 # ---------------------------------------------------------------------------------------------------- the device path
 def _to_device(x, device):
+    """uint8 [n, ...] images or finite float32 [n, D] features, on the device"""
+    return as_set(x, "prdc").to(device).contiguous()
+
+
+def _search_ops(t):
+    """(knn, ball_count) for a set's kind: the exact integer kernels for uint8 images, the fp64 ones for float32 features"""
     import torch
-    t = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
-    if t.dtype != torch.uint8 or t.dim() < 2:
-        raise ValueError(f"prdc: images must be uint8 [n, ...], got {t.dtype} {tuple(t.shape)}")
-    return t.to(device).contiguous()
+    from . import ops
+    return (ops.f32_knn, ops.f32_ball_count) if t.dtype == torch.float32 else (ops.u8_knn, ops.u8_ball_count)
 
 
 def _score_sets(real, fake, ks, ref_chunk, real_dist=None, per_sample=False) -> dict:
-    """real, fake: uint8 on one device; real_dist: the reals' self-search at >= max(ks), if the caller holds it"""
-    from . import ops
+    """real, fake: both uint8 or both float32, on one device; real_dist: the reals' self-search at >= max(ks), if the caller
+    holds it.  Radii and distances stay what the search returned (int64 or fp64) up to the compares."""
+    knn, ball_count = _search_ops(real)
     kmax = max(ks)
     if real_dist is None:
-        real_dist = ops.u8_knn(real, real, kmax, exclude_self=True, ref_chunk=ref_chunk)[0]
+        real_dist = knn(real, real, kmax, exclude_self=True, ref_chunk=ref_chunk)[0]
     r_x = radii_from_knn(real_dist, ks)
-    r_y = radii_from_knn(ops.u8_knn(fake, fake, kmax, exclude_self=True, ref_chunk=ref_chunk)[0], ks)
-    near_y = ops.u8_knn(real, fake, 1, ref_chunk=ref_chunk)[0][:, 0].cpu().numpy()
+    r_y = radii_from_knn(knn(fake, fake, kmax, exclude_self=True, ref_chunk=ref_chunk)[0], ks)
+    near_y = knn(real, fake, 1, ref_chunk=ref_chunk)[0][:, 0].cpu().numpy()
     out = {}
     for k in ks:
-        hits_x = ops.u8_ball_count(fake, real, r_x[k], ref_chunk=ref_chunk).cpu().numpy()
-        hits_y = ops.u8_ball_count(real, fake, r_y[k], ref_chunk=ref_chunk).cpu().numpy()
+        hits_x = ball_count(fake, real, r_x[k], ref_chunk=ref_chunk).cpu().numpy()
+        hits_y = ball_count(real, fake, r_y[k], ref_chunk=ref_chunk).cpu().numpy()
         out[k] = metrics_from_counts(hits_x, hits_y, near_y, r_x[k].cpu().numpy(), k)
         if per_sample:
             out[k]["per_sample"] = {"hits_x": hits_x.tolist(), "real_reached": (hits_y > 0).tolist()}
@@ -144,12 +166,12 @@ def _score_sets(real, fake, ks, ref_chunk, real_dist=None, per_sample=False) -> 
 
 class ManifoldMetrics:
     """Precision, recall, density and coverage of sample sets against one resident set of reals.  real_u8: uint8 [M, ...]
-    (numpy or torch; moved to `device`); k: an integer or a sequence.  The reals' radii for every k come from one self-search
+    images (exact integer pixel distances) or float32 [M, D] features (fp64 Euclidean distances, the space the metrics were
+    defined in), numpy or torch, moved to `device`; the samples must be of the same kind.  k: an integer or a sequence.  The reals' radii for every k come from one self-search
     at max(k), run here once."""
 
     def __init__(self, real_u8, k=5, ref_chunk=None, device=None):
         import torch
-        from . import ops
         if ref_chunk is not None and (isinstance(ref_chunk, bool) or not isinstance(ref_chunk, int) or ref_chunk < 1):
             raise ValueError(f"ManifoldMetrics: ref_chunk must be None or an integer >= 1, got {ref_chunk!r}")
         self.ks = check_k(k, num_real=len(real_u8))
@@ -158,7 +180,7 @@ class ManifoldMetrics:
             device = real_u8.device if on_gpu else torch.device("cuda", torch.cuda.current_device())
         self.real = _to_device(real_u8, device)
         self.ref_chunk = ref_chunk
-        self.real_dist = ops.u8_knn(self.real, self.real, max(self.ks), exclude_self=True, ref_chunk=ref_chunk)[0]
+        self.real_dist = _search_ops(self.real)[0](self.real, self.real, max(self.ks), exclude_self=True, ref_chunk=ref_chunk)[0]
         self.r_x = radii_from_knn(self.real_dist, self.ks)
 
     def score(self, fake_u8, real_labels=None, fake_labels=None, per_sample=False) -> dict:
@@ -170,6 +192,9 @@ class ManifoldMetrics:
             raise ValueError("ManifoldMetrics.score: give both real_labels and fake_labels, or neither")
         check_k(self.ks, self.real.shape[0], len(fake_u8))
         fake = _to_device(fake_u8, self.real.device)
+        if fake.dtype != self.real.dtype:
+            raise ValueError(f"ManifoldMetrics.score: the samples are {fake.dtype}, the reals {self.real.dtype}: both sets must "
+                             "be uint8 images or both float32 features")
         if fake.shape[1:] != self.real.shape[1:]:
             raise ValueError(f"ManifoldMetrics.score: samples {tuple(fake.shape[1:])} and reals {tuple(self.real.shape[1:])} "
                              "differ in shape")
@@ -211,14 +236,52 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--labels_json", type=str, default=None,
                    help="a JSON list of the samples' class indices in index order (generate --labels_to): adds the per-class "
                         "table; the reals' labels come from --dataset")
+    p.add_argument("--features", type=str, default=None, metavar="A.npy", help="samples as a float32 [n, D] array")
+    p.add_argument("--ref_features", type=str, default=None, metavar="B.npy", help="reals as a float32 [n, D] array")
+    p.add_argument("--holdout_features", type=str, default=None, metavar="C.npy",
+                   help="held-out rows as a float32 [n, D] array, scored against the same reals")
+    p.add_argument("--ref_labels", type=str, default=None,
+                   help="with --ref_features and --labels_json: a JSON list of the reals' class indices in row order")
     p.add_argument("--ref_chunk", type=int, default=None, help="search the references this many rows at a time")
     p.add_argument("--per_sample", action="store_true", help="add the per-sample and per-real membership to the report")
     p.add_argument("--report", type=str, required=True, metavar="OUT.json")
     return p
 
 
+def _check_common(args) -> tuple:
+    ks = check_k(args.k)
+    if args.num_real is not None:
+        if isinstance(args.num_real, bool) or not isinstance(args.num_real, int) or args.num_real < 2:
+            raise ValueError(f"prdc: --num_real must be an integer >= 2, got {args.num_real!r}")
+        check_k(ks, num_real=args.num_real)
+    if args.ref_chunk is not None and (isinstance(args.ref_chunk, bool) or not isinstance(args.ref_chunk, int)
+                                       or args.ref_chunk < 1):
+        raise ValueError(f"prdc: --ref_chunk must be an integer >= 1, got {args.ref_chunk!r}")
+    return ks
+
+
+def _check_feature_args(args) -> None:
+    """the feature form of check_args; leaves the arrays it had to read in args.feature_sets"""
+    if args.features is None or args.ref_features is None:
+        raise ValueError("prdc: the feature form needs both --features and --ref_features")
+    if (args.labels_json is None) != (args.ref_labels is None):
+        raise ValueError("prdc: with features the per-class table needs both --labels_json (samples) and --ref_labels (reals)")
+    ks = _check_common(args)
+    args.feature_sets = read_feature_sets(args, "prdc", min_rows=2)
+    real = args.feature_sets["ref_features"]
+    if args.num_real is not None and args.num_real > real.shape[0]:
+        raise ValueError(f"prdc: --num_real {args.num_real} exceeds the {real.shape[0]} reals")
+    real = real[:args.num_real]
+    check_sets(ks, real, {f: x for f, x in args.feature_sets.items() if f != "ref_features"})
+
+
 def check_args(args) -> None:
-    """every choice that needs nothing loaded, checked before an image or the GPU is touched"""
+    """every choice that needs nothing loaded, checked before an image or the GPU is touched (the feature form also reads
+    its arrays: their dtype, shape and finiteness are part of the check)"""
+    if feature_form(args, "prdc"):
+        return _check_feature_args(args)
+    if getattr(args, "ref_labels", None) is not None:
+        raise ValueError("prdc: --ref_labels goes with --ref_features; the labels of --dataset are its own")
     if args.image_dir is None:
         raise ValueError("prdc: give the samples with --image_dir")
     if (args.dataset is None) == (args.ref_image_dir is None):
@@ -227,20 +290,13 @@ def check_args(args) -> None:
         raise ValueError("prdc: --dataset needs --data_dir")
     if args.dataset is None and args.data_dir is not None:
         raise ValueError("prdc: --data_dir goes with --dataset")
-    ks = check_k(args.k)
-    if args.num_real is not None:
-        if isinstance(args.num_real, bool) or not isinstance(args.num_real, int) or args.num_real < 2:
-            raise ValueError(f"prdc: --num_real must be an integer >= 2, got {args.num_real!r}")
-        check_k(ks, num_real=args.num_real)
+    _check_common(args)
     if args.holdout and args.dataset is None:
         raise ValueError("prdc: --holdout takes the test split of --dataset; use --holdout_image_dir with --ref_image_dir")
     if args.holdout and args.holdout_image_dir is not None:
         raise ValueError("prdc: give one held-out set: --holdout or --holdout_image_dir")
     if args.labels_json is not None and args.dataset is None:
         raise ValueError("prdc: --labels_json needs a labelled set of reals (--dataset): a directory of images has no labels")
-    if args.ref_chunk is not None and (isinstance(args.ref_chunk, bool) or not isinstance(args.ref_chunk, int)
-                                       or args.ref_chunk < 1):
-        raise ValueError(f"prdc: --ref_chunk must be an integer >= 1, got {args.ref_chunk!r}")
 
 
 def check_sets(ks, real, sets) -> None:
@@ -254,12 +310,12 @@ def check_sets(ks, real, sets) -> None:
             raise ValueError(f"{e} (reals and {name})") from None
 
 
-def _read_sample_labels(path, n):
+def _read_sample_labels(path, n, flag="--labels_json"):
     with open(path) as f:
         labels = json.load(f)
     if not isinstance(labels, list) or len(labels) < n or not all(
             isinstance(v, int) and not isinstance(v, bool) and v >= 0 for v in labels):
-        raise ValueError(f"prdc: --labels_json must hold a list of at least {n} class indices")
+        raise ValueError(f"prdc: {flag} must hold a list of at least {n} class indices")
     return np.asarray(labels[:n], dtype=np.int64)
 
 
@@ -298,19 +354,29 @@ def main(argv=None):
     try:
         check_args(args)
         ks = check_k(args.k)
-        real = _read_dataset(args.dataset, args.data_dir, True) if args.dataset is not None else load_images_u8(args.ref_image_dir)
-        real_labels = _read_dataset_labels(args.dataset, args.data_dir) if args.labels_json is not None else None
+        feats = getattr(args, "feature_sets", None)
+        if feats is not None:
+            real = feats["ref_features"]
+            real_labels = None if args.ref_labels is None else _read_sample_labels(args.ref_labels, real.shape[0], "--ref_labels")
+        else:
+            real = _read_dataset(args.dataset, args.data_dir, True) if args.dataset is not None else load_images_u8(args.ref_image_dir)
+            real_labels = _read_dataset_labels(args.dataset, args.data_dir) if args.labels_json is not None else None
         if args.num_real is not None:
             if args.num_real > real.shape[0]:
                 raise ValueError(f"prdc: --num_real {args.num_real} exceeds the {real.shape[0]} reals")
             real = real[:args.num_real]
             real_labels = None if real_labels is None else real_labels[:args.num_real]
         shape = real.shape[1:]
-        sets = {"samples": load_images_u8(args.image_dir, shape[1:], shape[0])}
-        if args.holdout:
-            sets["holdout"] = _read_dataset(args.dataset, args.data_dir, False)
-        elif args.holdout_image_dir is not None:
-            sets["holdout"] = load_images_u8(args.holdout_image_dir, shape[1:], shape[0])
+        if feats is not None:
+            sets = {"samples": feats["features"]}
+            if "holdout_features" in feats:
+                sets["holdout"] = feats["holdout_features"]
+        else:
+            sets = {"samples": load_images_u8(args.image_dir, shape[1:], shape[0])}
+            if args.holdout:
+                sets["holdout"] = _read_dataset(args.dataset, args.data_dir, False)
+            elif args.holdout_image_dir is not None:
+                sets["holdout"] = load_images_u8(args.holdout_image_dir, shape[1:], shape[0])
         check_sets(ks, real, sets)
         fake_labels = None if args.labels_json is None else _read_sample_labels(args.labels_json, sets["samples"].shape[0])
     except ValueError as e:
@@ -318,10 +384,14 @@ def main(argv=None):
     import torch
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
     mm = ManifoldMetrics(real, k=ks, ref_chunk=args.ref_chunk)
-    report = {"k": list(ks), "num_real": int(real.shape[0]), "image_shape": [int(v) for v in shape],
-              "space": "pixels (exact integer distances): read the samples against the holdout entry, not against 1",
-              "num_samples": int(sets["samples"].shape[0]),
-              "samples": _json_keys(mm.score(sets["samples"], real_labels, fake_labels, per_sample=args.per_sample))}
+    report = {"k": list(ks), "num_real": int(real.shape[0])}
+    if feats is not None:
+        report.update({"feature_dim": int(shape[0]), "space": FEATURE_SPACE})
+    else:
+        report.update({"image_shape": [int(v) for v in shape],
+                       "space": "pixels (exact integer distances): read the samples against the holdout entry, not against 1"})
+    report.update({"num_samples": int(sets["samples"].shape[0]),
+                   "samples": _json_keys(mm.score(sets["samples"], real_labels, fake_labels, per_sample=args.per_sample))})
     if "holdout" in sets:
         report["num_holdout"] = int(sets["holdout"].shape[0])
         report["holdout"] = _json_keys(mm.score(sets["holdout"]))
