@@ -1060,6 +1060,18 @@ int edm_f32_ball_count_partial(const void* queries, const void* refs, long Q, lo
                                int exclude_self, long ref_base, int splits, const double* qnorms, const double* rnorms,
                                int* counts, edm_stream_t stream);
 
+/* ---------------------------------------------------------------- denoiser activations as features (csrc/features.hip) */
+/* Global average pool of an fp32 NHWC activation into a slice of a feature row (Xiang et al. 2023, "Denoising Diffusion
+ * Autoencoders are Unified Self-supervised Learners": pooled activations of an intermediate block; the reference has no
+ * call site for it).  x fp32 [B][HW][C] contiguous; row b of out starts at out + b * out_stride (floats) and only its columns
+ * [out_offset, out_offset + C) are written: out[b][out_offset + c] = (float)((sum_p (double)x[b][p][c]) / (double)HW).
+ * The sum is fp64 in an order that depends on HW alone (pixel p in slot p % 32, slots in ascending order), so a row's
+ * bits depend on neither B, its place in the batch, C nor the load path (16-byte loads when C % 4 == 0 and x is 16-byte
+ * aligned, element loads otherwise).  No atomics.  Any C >= 1 up to 65535 * 32, any HW >= 1, any B >= 1 (beyond 65 535
+ * too); the destination needs 4-byte alignment only; out_stride >= out_offset + C.  Status -1 otherwise. */
+int edm_f32_pool_features(const float* x, float* out, int B, int HW, int C, long out_stride, int out_offset,
+                          edm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

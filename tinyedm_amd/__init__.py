@@ -6,6 +6,7 @@ __version__ = "0.1.0"
 from . import _runtime_env  # noqa: F401  (first: sets HIP runtime flags before anything can initialise the GPU)
 from .edm import EDM, Diffuser
 from .ema import EMA, EMAOptimizer, FusedAdam, sigma_rel_to_gamma
+from .features import FeatureExtractor
 from .frechet import DistributionDistance, FeatureStats, frechet_distance, kid, kid_from_sums, subset_indices
 from .ideal import IdealDenoiser
 from .metric import WeightedMeanSquaredError
@@ -17,7 +18,7 @@ from .trainer import LightningModule, Trainer
 from .vjp import input_vjp
 from . import config, networks, ops
 
-__all__ = ["EDM", "Diffuser", "DeterministicSolver", "StochasticSolver", "MultistepSolver", "AdaptiveSolver", "ParallelSolver", "ParallelStats", "LinearDegradation", "GaussianBlur", "input_vjp", "IdealDenoiser", "ManifoldMetrics", "DistributionDistance", "FeatureStats", "frechet_distance", "kid", "kid_from_sums",
+__all__ = ["EDM", "Diffuser", "DeterministicSolver", "StochasticSolver", "MultistepSolver", "AdaptiveSolver", "ParallelSolver", "ParallelStats", "LinearDegradation", "GaussianBlur", "input_vjp", "IdealDenoiser", "FeatureExtractor", "ManifoldMetrics", "DistributionDistance", "FeatureStats", "frechet_distance", "kid", "kid_from_sums",
            "subset_indices", "WeightedMeanSquaredError", "Denoiser", "Linear", "Conv2d",
            "Embedding", "DenoiserWrapper", "EMA", "EMAOptimizer", "FusedAdam", "Trainer", "LightningModule",
            "sigma_rel_to_gamma", "manual_seed", "config", "networks", "ops"]

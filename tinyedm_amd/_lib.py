@@ -230,6 +230,8 @@ SIGNATURES = {
     "edm_f32_knn_partial": [P, P, L, L, I, I, I, L, I, I, P, P, P, P, P],
     "edm_fknn_merge": [P, P, I, L, I, P, P, P],
     "edm_f32_ball_count_partial": [P, P, L, L, I, P, I, L, I, P, P, P, P],
+    # features.hip
+    "edm_f32_pool_features": [P, P, I, I, I, L, I, P],
 }
 # include/tinyedm_hip_diag.h: tools-only entry points, bound on demand by call()
 DIAG_SIGNATURES = {

@@ -209,6 +209,14 @@ class EDM(LightningModule):
             _, embedding = self.embedding(sigma, class_label, augment_labels)
         return self.denoiser(noisy_image, sigma, embedding)
 
+    def forward_taps(self, noisy_image: Tensor, sigma: Tensor, class_label: Tensor | None = None,
+                     taps=("mid",)) -> dict[str, Tensor]:
+        """Block outputs of the denoiser as fp32 NHWC tensors (Denoiser.forward_taps; features.py).  The embedding is
+        formed as in forward, without augment labels."""
+        class_label = class_label if self.conditional else None
+        _, embedding = self.embedding(sigma, class_label)
+        return self.denoiser.forward_taps(noisy_image, sigma, embedding, taps)
+
     def predict_step(self, batch: Any, batch_idx: int, dataloader_idx: int | None = None):
         x0, class_label, *cond = batch       # cond: (image[, mask]) of an image-conditioned batch (RandomNoiseDataModule)
         class_label = class_label if self.conditional else None

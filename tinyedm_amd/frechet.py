@@ -12,8 +12,8 @@ are the two distances between distributions that the literature reports:
 
 The features are either the pixels themselves (uint8 images, feature u / 255: a crude space, as for prdc, but one in which
 the moments are exact integers and the result is unique) or float32 vectors extracted elsewhere (Inception, DINO, ...:
-no extractor ships here).  The two reductions over a set -- the moments sum x, sum x x^T and the kernel sums -- run in fp64
-on the device (csrc/moments.hip through ops.moments and ops.poly_kernel_sums); everything after them is numpy fp64 on the
+no such extractor ships here; tinyedm.features takes them from the project's own denoiser).  The two reductions over a
+set -- the moments sum x, sum x x^T and the kernel sums -- run in fp64 on the device (csrc/moments.hip through ops.moments and ops.poly_kernel_sums); everything after them is numpy fp64 on the
 host and needs no GPU: FeatureStats, frechet_distance, subset_indices, kid_from_sums, check_args.
 
 FD is biased upwards at a finite number of samples; read the samples' number against the one fresh data gets (`--holdout`).

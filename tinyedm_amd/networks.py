@@ -1756,6 +1756,36 @@ def build_decoder_blocks(block_types, out_channels, skip_channels, **kwargs):
     return blocks
 
 
+def tap_positions(taps, n_enc: int, n_dec: int) -> dict:
+    """Tap names of Denoiser.forward_taps -> {name: position in the block sequence (encoder blocks, then decoder blocks)},
+    in the order given.  "enc<i>" is the output of encoder_blocks[i] (after its attention, if it has one), "dec<i>" that of
+    decoder_blocks[i], "mid" the last encoder block.  Host logic only."""
+    valid = f'"enc0" .. "enc{n_enc - 1}", "dec0" .. "dec{n_dec - 1}" or "mid" (= "enc{n_enc - 1}")'
+    if isinstance(taps, str):
+        taps = (taps,)
+    try:
+        names = list(taps)
+    except TypeError:
+        raise ValueError(f"taps: expected a list of tap names, each {valid}, got {taps!r}") from None
+    if not names:
+        raise ValueError(f"taps: no tap named; each is {valid}")
+    out = {}
+    for name in names:
+        pos = None
+        if name == "mid":
+            pos = n_enc - 1
+        elif isinstance(name, str) and name[:3] in ("enc", "dec") and name[3:].isascii() and name[3:].isdigit():
+            i, n = int(name[3:]), n_enc if name[:3] == "enc" else n_dec
+            if i < n and name[3:] == str(i):
+                pos = i if name[:3] == "enc" else n_enc + i
+        if pos is None or pos < 0:
+            raise ValueError(f"taps: unknown tap {name!r}; each is {valid}")
+        if pos in out.values():
+            raise ValueError(f"taps: {name!r} names a block twice in {names}; each is {valid}")
+        out[name] = pos
+    return out
+
+
 # --------------------------------------------------------------------------------------
 # Denoiser (networks.py:490-605)
 # --------------------------------------------------------------------------------------
@@ -2194,7 +2224,13 @@ class Denoiser(nn.Module):
         self.eval_dtype = dtype
         return self
 
-    def _forward_f32(self, noisy: Tensor, sig: Tensor, emb: Tensor) -> Tensor:
+    def _forward_f32(self, noisy: Tensor, sig: Tensor, emb: Tensor, taps: dict | None = None):
+        """taps (forward_taps): {position in the block sequence: tap name} -> {name: that block's output, fp32 NHWC}; the
+        walk ends behind the deepest tapped block.  With taps every block hands on a plain fp32 tensor (want=None), which
+        its consumer takes through the generic path: the split back end's fused hand-overs (want_of) run other kernels
+        than the generic path and agree with it to rounding only, and a tap's bits must not depend on which other blocks
+        are tapped.  None: the whole network -> D."""
+        tapped, last = {}, max(taps) if taps else -1
         blocks = self._res_blocks()
         lin_all = ops.linear_fwd(emb, self._wcat(blocks))
         lins, off = {}, 0
@@ -2206,7 +2242,7 @@ class Denoiser(nn.Module):
         x = ops.f32_conv(ops.f32_precond_in(noisy, sig, self.sigma_data, cp), self.conv_in.packs()[2], 9)
         skips = [x]
         dec = list(zip(self.decoder_blocks, self.skip_connections))
-        split = bool(_SPLIT_EVAL[0]) and F32_FUSE_OUT
+        split = bool(_SPLIT_EVAL[0]) and F32_FUSE_OUT and not taps
 
         def want_of(block, nxt, n_skip, hw, skip_c):
             """what `block`'s last conv writes for its consumer `nxt` (round 6: the eval-shaped forward of the split back
@@ -2233,6 +2269,10 @@ class Denoiser(nn.Module):
             want = want_of(block, dec[0][0], dec[0][1], (h, w), 0) if (i + 1 == len(enc) and dec and not dec[0][1]) else None
             x = block.forward_f32(x, lins[block], want)
             skips.append(x[0] if isinstance(x, tuple) else x)
+            if taps and i in taps:
+                tapped[taps[i]] = x
+                if i == last:
+                    return tapped
         for i, (block, has_skip) in enumerate(dec):
             skip = skips.pop() if has_skip else None
             if isinstance(block.resample, UpSample):
@@ -2240,6 +2280,10 @@ class Denoiser(nn.Module):
             nxt, n_skip = dec[i + 1] if i + 1 < len(dec) else (None, False)
             want = want_of(block, nxt, n_skip, (h, w), skips[-1].shape[-1] if (n_skip and skips) else 0)
             x = block.forward_f32(x, lins[block], skip, want)
+            if taps and len(enc) + i in taps:
+                tapped[taps[len(enc) + i]] = x
+                if len(enc) + i == last:
+                    return tapped
         return ops.f32_conv_out(x, self.conv_out.packs()[2], self.gain_out.detach(), noisy, sig, self.sigma_data)
 
     def forward(self, noisy_image: Tensor, sigma: Tensor, embedding: Tensor):
@@ -2248,6 +2292,35 @@ class Denoiser(nn.Module):
             return self._forward(noisy_image, sigma, embedding)
         finally:
             _IN_DENOISER[0] = prev
+
+    def forward_taps(self, noisy_image: Tensor, sigma: Tensor, embedding: Tensor, taps) -> dict:
+        """Block outputs as features (features.py): {name: fp32 NHWC (B,H,W,C)} for the tap names in `taps` (tap_positions:
+        "enc<i>", "dec<i>", "mid").  Reference-precision evaluation only (eval mode, eval_dtype "f32" or "f32x3"), under
+        no_grad.  The network runs up to the deepest tap: no later block and no conv_out is launched (the embed Linears of
+        all blocks are one GEMM and run whole)."""
+        where = tap_positions(taps, len(self.encoder_blocks), len(self.decoder_blocks))
+        if self.eval_dtype == "bf16":
+            raise ValueError("Denoiser.forward_taps: features are taken at reference precision: set_eval_dtype('f32x3') or "
+                             "'f32' (the bf16 forward is training-shaped and has no taps)")
+        if self.training:
+            raise ValueError("Denoiser.forward_taps: the denoiser must be in eval mode (the fp32 path is evaluation-only)")
+        if not noisy_image.is_cuda:
+            raise RuntimeError("tinyedm_amd.Denoiser: inputs must be GPU tensors (there is no CPU path)")
+        prev, _IN_DENOISER[0] = _IN_DENOISER[0], True
+        try:
+            with torch.no_grad():
+                self._prep_all()
+                noisy = noisy_image.float().contiguous()
+                _SPLIT_EVAL[0] = self.eval_dtype == "f32x3"
+                try:
+                    out = self._forward_f32(noisy, sigma.detach().float().flatten().contiguous(),
+                                            _emb32(embedding.detach(), noisy.shape[0]),
+                                            {pos: name for name, pos in where.items()})
+                finally:
+                    _SPLIT_EVAL[0] = False
+        finally:
+            _IN_DENOISER[0] = prev
+        return {name: out[name] for name in where}       # (in the order asked for)
 
     def _forward(self, noisy_image: Tensor, sigma: Tensor, embedding: Tensor):
         if not noisy_image.is_cuda:

@@ -3943,3 +3943,30 @@ def poly_kernel_sums(a, idx_a, b, idx_b, gamma, coef0, degree, exclude_equal_ind
                   degree, int(bool(exclude_equal_index)), _p(partial), _stream())
         _lib.call("edm_poly_sums_finish", _p(partial), S, tiles, _p(sums), _stream())
     return sums
+
+
+# ------------------------------------------------------------------ denoiser activations as features (csrc/features.hip)
+def f32_pool_features(x, out=None, offset=0):
+    """The spatial mean of an fp32 NHWC activation (B,H,W,C) as feature columns: out[b, offset + c] = the mean over H*W of
+    x[b, :, :, c], summed in fp64 in an order that depends on H*W alone and rounded to fp32 once -- row b has the same bits
+    whatever the batch.  out=None allocates and returns (B, C); otherwise out is a contiguous fp32 (B, Dtot) tensor with
+    offset + C <= Dtot, only those C columns are written, and out is returned.  Any C >= 1, any B."""
+    try:
+        B, H, W, C = _nhwc32(x, "x")
+    except (TypeError, RuntimeError) as e:
+        raise ValueError(str(e)) from None
+    if x.numel() == 0:
+        raise ValueError(f"x: expected a non-empty (B,H,W,C) tensor, got {tuple(x.shape)}")
+    if isinstance(offset, bool) or not isinstance(offset, int) or offset < 0:
+        raise ValueError(f"f32_pool_features: offset must be an integer >= 0, got {offset!r}")
+    if out is None:
+        if offset:
+            raise ValueError("f32_pool_features: an offset needs the out tensor it points into")
+        out = torch.empty(B, C, device=x.device, dtype=f32)
+    else:
+        _chk_eval(out, f32, "out", None, x.device)
+        if out.dim() != 2 or out.shape[0] != B or offset + C > out.shape[1]:
+            raise ValueError(f"out: expected ({B}, Dtot) with Dtot >= offset + C = {offset + C}, got {tuple(out.shape)}")
+    with _prof("f32_pool_features", 0.0, 4.0 * (x.numel() + B * C)):
+        _lib.call("edm_f32_pool_features", _p(x), _p(out), B, H * W, C, out.shape[1], offset, _stream())
+    return out

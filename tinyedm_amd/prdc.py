@@ -24,8 +24,8 @@ that fresh data gets (`--holdout`: at finite sample sizes real against real is b
         --report prdc.json
 
 The feature-space form, the one the two papers define: float32 [n, D] features extracted elsewhere (the arrays
-`tinyedm.frechet --features` takes; no extractor ships here) in place of the images.  The same definitions then run on fp64
-squared Euclidean distances (csrc/neighbors_f32.hip: ops.f32_knn, ops.f32_ball_count; the k-th neighbour radius of the search
+`tinyedm.frechet --features` takes; tinyedm.features writes them from the project's own denoiser) in place of the images.
+The same definitions then run on fp64 squared Euclidean distances (csrc/neighbors_f32.hip: ops.f32_knn, ops.f32_ball_count; the k-th neighbour radius of the search
 is bit for bit the number the ball count compares against), and only the ratios' inputs are floats:
 
     python -m tinyedm.prdc --features samples.npy --ref_features train.npy --holdout_features test.npy \\
