@@ -1072,6 +1072,26 @@ int edm_f32_ball_count_partial(const void* queries, const void* refs, long Q, lo
 int edm_f32_pool_features(const float* x, float* out, int B, int HW, int C, long out_stride, int out_offset,
                           edm_stream_t stream);
 
+/* ---------------------------------------------------------------- optimised sampling schedules (csrc/schedule.hip) */
+/* The local error of every single-step jump between two nodes of a recorded teacher trajectory: the pair costs of the
+ * dynamic-programming schedule search (Watson et al. 2021; Chen et al. 2024; the reference has no call site for it).
+ * X fp32 [G+1][B][K], node-major: the states at the grid nodes, node G the result; S fp32 [G][B][K]: the Euler slopes at
+ * nodes 0 .. G-1; tau: DEVICE fp64 [G+1], the grid (the fp32 table values widened), tau[G] = 0; d2: DEVICE fp64
+ * [B][G][G+1], every entry WRITTEN.  For i < j, with h = tau[j] - tau[i] and everything in fp64:
+ *   order 1, and order 2 when j == G (Heun's closing step is Euler-only):  e_k = x_ik + h s_ik - x_jk
+ *   order 2 when j < G (the trapezoid along the trajectory):              e_k = x_ik + (h/2)(s_ik + s_jk) - x_jk
+ *   d2[b][i][j] = sum_k e_k^2,
+ * evaluated as e = fma(c h, s_i + s_j', x_i - x_j), (c, s_j') = (1/2, s_j) or (1, 0).  Entries with j <= i are +0.0.
+ * The bits of d2[b][i][j] depend only on K, the two nodes' rows of sample b, tau[i], tau[j] and order: not on B, G, the
+ * pair's place in a tile, the other pairs or the load path (dwordx4 when K % 4 == 0 and X, S are 16-byte aligned, the same
+ * quads element by element otherwise).  No floating-point atomics: thread t of 256 adds the quads t, t + 256, ... of the K
+ * axis in ascending order, then the wave butterfly and the four wave totals in index order, a function of K alone.
+ * Any K >= 1, any B >= 1 with B * ceil(G/4) * ceil((G+1)/8) < 2^31, 1 <= G <= EDM_SCHEDULE_MAX_GRID, order 1 or 2; tau and
+ * d2 8-byte aligned.  Status -1 otherwise. */
+#define EDM_SCHEDULE_MAX_GRID 256
+int edm_pair_step_errors(const float* X, const float* S, const double* tau, int B, int G, long K, int order, double* d2,
+                         edm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,13 +12,14 @@ from .ideal import IdealDenoiser
 from .metric import WeightedMeanSquaredError
 from .networks import Conv2d, Denoiser, DenoiserWrapper, Embedding, Linear, manual_seed
 from .prdc import ManifoldMetrics
+from .schedule import Schedule, optimize_schedule
 from .solvers import (AdaptiveSolver, DeterministicSolver, GaussianBlur, LinearDegradation, MultistepSolver,
-                      ParallelSolver, ParallelStats, StochasticSolver)
+                      ParallelSolver, ParallelStats, StochasticSolver, Trajectory)
 from .trainer import LightningModule, Trainer
 from .vjp import input_vjp
 from . import config, networks, ops
 
-__all__ = ["EDM", "Diffuser", "DeterministicSolver", "StochasticSolver", "MultistepSolver", "AdaptiveSolver", "ParallelSolver", "ParallelStats", "LinearDegradation", "GaussianBlur", "input_vjp", "IdealDenoiser", "FeatureExtractor", "ManifoldMetrics", "DistributionDistance", "FeatureStats", "frechet_distance", "kid", "kid_from_sums",
+__all__ = ["EDM", "Diffuser", "DeterministicSolver", "StochasticSolver", "MultistepSolver", "AdaptiveSolver", "ParallelSolver", "ParallelStats", "Trajectory", "Schedule", "optimize_schedule", "LinearDegradation", "GaussianBlur", "input_vjp", "IdealDenoiser", "FeatureExtractor", "ManifoldMetrics", "DistributionDistance", "FeatureStats", "frechet_distance", "kid", "kid_from_sums",
            "subset_indices", "WeightedMeanSquaredError", "Denoiser", "Linear", "Conv2d",
            "Embedding", "DenoiserWrapper", "EMA", "EMAOptimizer", "FusedAdam", "Trainer", "LightningModule",
            "sigma_rel_to_gamma", "manual_seed", "config", "networks", "ops"]

@@ -232,6 +232,8 @@ SIGNATURES = {
     "edm_f32_ball_count_partial": [P, P, L, L, I, P, I, L, I, P, P, P, P],
     # features.hip
     "edm_f32_pool_features": [P, P, I, I, I, L, I, P],
+    # schedule.hip
+    "edm_pair_step_errors": [P, P, P, I, I, L, I, P, P],
 }
 # include/tinyedm_hip_diag.h: tools-only entry points, bound on demand by call()
 DIAG_SIGNATURES = {

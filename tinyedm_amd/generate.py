@@ -110,6 +110,9 @@ grid and `--restore_report` the RMS of A x - y (to be read against N) and the PS
 written `<index>.png` files, in index order, which is what `--labels_json` of `tinyedm.evaluate` and `tinyedm.classify`
 reads.  `python -m tinyedm.classify --image_dir samples --labels_json FILE.json ...` then measures how often the
 sampler produced the class it was asked for.  Without the flag nothing changes.
+`--sigma_table schedule.json` samples on the table that `python -m tinyedm.schedule` optimised for `--num_steps` (a file
+without that N is refused, naming the N it has) instead of the Karras table; it combines with `--solver heun`, `dpmpp`
+and `picard`, `--S_churn` and the guidance flags, and is an error with `--solver adaptive`, which has no table.
 Multi-GPU = replicas only: under `python -m torch.distributed.run --nproc-per-node N` every rank samples
 its own contiguous index range with its own noise seed and writes `<global index>.png`; there is no collective.
 """
@@ -339,10 +342,13 @@ def load_images(init_dir, mean, std, image_size, channels) -> torch.Tensor:
 def _validate(*, solver, S_churn, init_dir, start_step, num_steps, mask_box, invert_to, likelihood_to, network_dtype,
               num_probes, dequantize, image_size, dps_scale, blur_std, blur_radius, measurement_noise, restore_scale,
               restore_gray, save_degraded, restore_report, labels_to, guided, guidance_interval=None, rtol=None, atol=None,
-              max_iterations=None, solver_report=None, window=None, solver_order=2) -> tuple:
+              max_iterations=None, solver_report=None, window=None, solver_order=2, sigma_table=None) -> tuple:
     """every choice that needs nothing loaded, checked once and in one order for generate() and the command line; returns
     (posterior, restoring): whether the run samples with DPS, and whether it restores (DDNM or DPS)"""
     _check_solver(solver, S_churn)
+    if sigma_table is not None and solver == "adaptive":
+        raise ValueError("generate: --solver adaptive does not take --sigma_table (it integrates sigma_max <-> sigma_min, "
+                         "every sample at its own sigma); use --solver heun")
     _check_adaptive(solver, guidance_interval, init_dir, start_step, mask_box, invert_to, likelihood_to,
                     restore_scale, restore_gray, dps_scale, rtol, atol, max_iterations, solver_report)
     _check_picard(solver, guidance_interval, init_dir, start_step, mask_box, invert_to, likelihood_to, restore_scale,
@@ -497,7 +503,8 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
              solver_order=2, init_dir=None, start_step=0, mask_box=None, invert_to=None, likelihood_to=None,
              num_probes=1, dequantize=False, restore_scale=1, restore_gray=False, save_degraded=None,
              restore_report=None, labels_to=None, dps_scale=None, blur_std=None, blur_radius=2,
-             measurement_noise=0.0, rtol=None, atol=None, max_iterations=None, solver_report=None, window=None) -> None:
+             measurement_noise=0.0, rtol=None, atol=None, max_iterations=None, solver_report=None, window=None,
+             sigma_table=None) -> None:
     from . import _runtime_env
     from .callbacks import PreditionWriter
     from .datamodules import RandomNoiseDataModule
@@ -512,7 +519,11 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
         measurement_noise=measurement_noise, restore_scale=restore_scale, restore_gray=restore_gray,
         save_degraded=save_degraded, restore_report=restore_report, labels_to=labels_to,
         guided=guide is not None or guide_ckpt_path is not None, guidance_interval=guidance_interval, rtol=rtol, atol=atol,
-        max_iterations=max_iterations, solver_report=solver_report, window=window, solver_order=solver_order)
+        max_iterations=max_iterations, solver_report=solver_report, window=window, solver_order=solver_order,
+        sigma_table=sigma_table)
+    if sigma_table is not None:     # (before anything is loaded: a file without this N is refused, naming the N it has)
+        from .schedule import Schedule
+        sigma_table = Schedule.load(sigma_table, num_steps).sigmas
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -537,6 +548,8 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
             print(f"[rank {rank}] guidance 1.0: the guide network is unused", flush=True)
     rank_seed = seed + 1000003 * rank
     common = dict(num_steps=num_steps, guide=guide, guidance=guidance, guidance_interval=guidance_interval, seed=rank_seed)
+    if sigma_table is not None:
+        common["sigmas"] = sigma_table
     adaptive_stats = []
     if solver == "adaptive":
         tol = {k: v for k, v in (("rtol", rtol), ("atol", atol), ("max_iterations", max_iterations)) if v is not None}
@@ -727,6 +740,9 @@ def main(argv=None):
     parser.add_argument("--labels_to", type=str, default=None, metavar="FILE.json",
                         help="write the class indices the samples were drawn for, in index order (the format "
                              "--labels_json of tinyedm.classify reads); class-conditional checkpoints, not with --init_dir")
+    parser.add_argument("--sigma_table", type=str, default=None, metavar="schedule.json",
+                        help="sample on the table of this file for --num_steps (python -m tinyedm.schedule writes it) "
+                             "instead of the Karras table; --solver heun, dpmpp or picard")
     args = parser.parse_args(argv)
     _check_solver(args.solver, args.S_churn)        # a ValueError, not a usage error: raised before _validate meets it
     try:
@@ -771,7 +787,7 @@ def main(argv=None):
              restore_report=args.restore_report, labels_to=args.labels_to, dps_scale=args.dps_scale,
              blur_std=args.blur_std, blur_radius=args.blur_radius, measurement_noise=args.measurement_noise,
              rtol=args.rtol, atol=args.atol, max_iterations=args.max_iterations, solver_report=args.solver_report,
-             window=args.window)
+             window=args.window, sigma_table=args.sigma_table)
 
 
 if __name__ == "__main__":

@@ -3970,3 +3970,35 @@ def f32_pool_features(x, out=None, offset=0):
     with _prof("f32_pool_features", 0.0, 4.0 * (x.numel() + B * C)):
         _lib.call("edm_f32_pool_features", _p(x), _p(out), B, H * W, C, out.shape[1], offset, _stream())
     return out
+
+
+# ------------------------------------------------------------------ optimised sampling schedules (csrc/schedule.hip)
+SCHEDULE_MAX_GRID = 256         # EDM_SCHEDULE_MAX_GRID: nodes of the teacher grid edm_pair_step_errors takes
+
+
+def pair_step_errors(X, S, tau, order=2):
+    """The squared local error of every single-step jump i -> j between the nodes of a recorded trajectory
+    (DeterministicSolver.trace): X fp32 [G + 1, B, ...] the states, S fp32 [G, B, ...] the Euler slopes, tau fp64 [G + 1]
+    on the device (the table widened, tau[G] = 0).  Returns d2 fp64 [B, G, G + 1]; for i < j, in fp64,
+
+        d2[b, i, j] = sum_k (x_i + h s_i - x_j)^2                (order 1, and order 2 when j == G),   h = tau[j] - tau[i]
+        d2[b, i, j] = sum_k (x_i + h/2 (s_i + s_j) - x_j)^2      (order 2, j < G: the trapezoid along the trajectory)
+
+    and +0.0 where j <= i.  The bits of an entry depend on K, the two nodes' rows of the sample, tau[i], tau[j] and order
+    alone (include/tinyedm_hip.h).  1 <= G <= SCHEDULE_MAX_GRID."""
+    _chk_eval(X, f32, "X")
+    if X.dim() < 3 or X.numel() == 0 or X.shape[0] < 2:
+        raise ValueError(f"X: expected a non-empty fp32 [G + 1, B, ...] tensor with G >= 1, got {tuple(X.shape)}")
+    G, B = X.shape[0] - 1, X.shape[1]
+    if G > SCHEDULE_MAX_GRID:
+        raise ValueError(f"pair_step_errors: at most {SCHEDULE_MAX_GRID} grid nodes, got {G}")
+    _chk_eval(S, f32, "S", (G, *X.shape[1:]), X.device)
+    _chk_eval(tau, torch.float64, "tau", (G + 1,), X.device)
+    if isinstance(order, bool) or order not in (1, 2):
+        raise ValueError(f"pair_step_errors: order must be 1 (Euler) or 2 (trapezoid), got {order!r}")
+    K = X.numel() // ((G + 1) * B)
+    d2 = torch.empty((B, G, G + 1), dtype=torch.float64, device=X.device)
+    pairs = B * G * (G + 1) // 2
+    with _prof("pair_step_errors", 6.0 * pairs * K, 4.0 * (X.numel() + S.numel()) + 8.0 * d2.numel()):
+        _lib.call("edm_pair_step_errors", _p(X), _p(S), _p(tau), B, G, K, int(order), _p(d2), _stream())
+    return d2

@@ -34,6 +34,34 @@ def _check_gpu(cls: str, name: str, t) -> None:
         raise RuntimeError(f"tinyedm_amd.{cls}: {name} must be a GPU tensor (there is no CPU path)")
 
 
+def _sigma_table(who: str, sigmas) -> torch.Tensor:
+    """a caller's sigma table (a sequence, numpy array or 1-D tensor of the N non-zero levels) as the fp32 host tensor a
+    solver stores; ValueError unless it has >= 2 finite, positive entries that still decrease strictly as fp32 values"""
+    try:
+        if isinstance(sigmas, torch.Tensor):
+            t = sigmas.detach().cpu().to(torch.float64)
+        else:       # (through numpy: torch would round a list of Python floats to fp32 before the checks see it)
+            import numpy as np
+            t = torch.from_numpy(np.array(sigmas, dtype=np.float64))
+    except (TypeError, ValueError, RuntimeError):
+        raise ValueError(f"{who}: sigmas must be a sequence, numpy array or 1-D tensor of numbers") from None
+    if t.dim() != 1 or t.numel() < 2:
+        raise ValueError(f"{who}: sigmas must be one-dimensional with at least 2 entries, got shape {tuple(t.shape)}")
+    if not bool(torch.isfinite(t).all()) or not bool((t > 0).all()):
+        raise ValueError(f"{who}: sigmas must be finite and > 0 (the closing 0 is appended), got {t.tolist()}")
+    t = t.float()
+    if not bool(torch.isfinite(t).all()) or not bool((t > 0).all()) or not bool((t[1:] < t[:-1]).all()):
+        raise ValueError(f"{who}: sigmas must be strictly decreasing, finite and > 0 as float32 values, got {t.tolist()}")
+    return t
+
+
+class Trajectory(NamedTuple):
+    """what DeterministicSolver.trace records of one Heun solve of N steps"""
+    x: torch.Tensor         # fp32 [N + 1, B, *shape]: node i is the state at t_i, node N the result of the solve
+    slope: torch.Tensor     # fp32 [N, B, *shape]: the Euler slope dx at (x_i, t_i) (of the mixed D, with a guide)
+    sigmas: torch.Tensor    # fp32 [N + 1] on the host: the table, closing 0 included
+
+
 def _denoisers(net):
     """(module, its eval_dtype) of every Denoiser of a network -- the modules that own an evaluation precision and
     eval-mode weight packs; nothing for a plain callable"""
@@ -291,13 +319,22 @@ class DeterministicSolver:
     ``LinearDegradation`` or a ``GaussianBlur``; y may be noisy; ``dps_scale=0`` is the plain solve bit for bit.  With
     ``degradation=``, a guide, ``mask=``, ``graph=True`` or ``MultistepSolver`` it raises ValueError.
     ``invert`` runs the probability-flow ODE upwards, image -> latent; ``log_likelihood`` does the same and integrates
-    the change of variables along the way (keyword-only ``delta``: the relative half-width of its central difference)."""
+    the change of variables along the way (keyword-only ``delta``: the relative half-width of its central difference).
+    A caller's table (keyword-only ``sigmas``: a sequence, numpy array or 1-D tensor of the N non-zero levels, e.g. a
+    ``tinyedm.schedule.Schedule``'s) replaces the Karras expression: ``num_steps`` becomes its length, ``sigma_max`` and
+    ``sigma_min`` its ends, ``rho`` None; fewer than 2 entries, a value that is not finite or not positive, or values
+    that do not decrease strictly as float32 raise ValueError.  The table is constructor-only.  ``trace`` records the
+    states and Euler slopes of a solve (the teacher of the schedule search)."""
 
     MAX_GRAPHS = 4      # captured solves kept per model (shape / precision combinations; least recently used dropped)
 
     def __init__(self, num_steps: int = 18, sigma_min: float = 0.002, sigma_max: float = 80.0, rho: float = 7.0,
                  dtype: str | None = None, *, guide=None, guidance: float = 1.0,
-                 guidance_interval: tuple[float, float] | None = None, seed: int = 0, delta: float = NLL_DELTA):
+                 guidance_interval: tuple[float, float] | None = None, seed: int = 0, delta: float = NLL_DELTA,
+                 sigmas=None):
+        table = None if sigmas is None else _sigma_table(type(self).__name__, sigmas)
+        if table is not None:       # a caller's table: its length and its ends replace the Karras parameters
+            num_steps, sigma_max, sigma_min, rho = table.numel(), table[0].item(), table[-1].item(), None
         self.num_steps = num_steps
         self.delta = delta
         self.seed = seed
@@ -309,9 +346,12 @@ class DeterministicSolver:
             raise ValueError("tinyedm_amd.DeterministicSolver integrates in float32 (the reference's only working "
                              "setting: its .to(dtype) call crashes for string dtypes)")
         self.dtype = torch.float32
-        i = torch.arange(num_steps, dtype=torch.float32)
-        t = (sigma_max ** (1 / rho) + i / (num_steps - 1) * (sigma_min ** (1 / rho) - sigma_max ** (1 / rho))) ** rho
-        self.t_steps = torch.cat([t, torch.zeros(1)])
+        if table is None:
+            i = torch.arange(num_steps, dtype=torch.float32)
+            t = (sigma_max ** (1 / rho) + i / (num_steps - 1) * (sigma_min ** (1 / rho) - sigma_max ** (1 / rho))) ** rho
+        else:
+            t = table
+        self.t_steps = torch.cat([t, torch.zeros(1)])       # constructor-only: never rewritten (captured solves rely on it)
         self._graphs = weakref.WeakKeyDictionary()      # model -> {(shapes, device[, guide]): captured solve}
         self.guide = guide
         self.guidance = guidance
@@ -463,6 +503,10 @@ class DeterministicSolver:
 
     def _step(self, evaluate, x1, i, ts, t_dev, guided, w_dev, state):
         """step i of the loop, t_i -> t_{i+1}: Euler and, but for the last step, the Heun correction"""
+        return self._heun_step(evaluate, x1, i, ts, t_dev, guided, w_dev, state)[1]
+
+    def _heun_step(self, evaluate, x1, i, ts, t_dev, guided, w_dev, state):
+        """the Heun step i as (dx, x_{i+1}): dx is the Euler slope at the step's start, which trace() records"""
         x, t0, s0 = self._step_start(x1, i, ts, t_dev, state)
         t1 = ts[i + 1]
         D, Dg = evaluate(x, s0, guided[2 * i])
@@ -471,7 +515,55 @@ class DeterministicSolver:
             D1, Dg1 = evaluate(x1, t_dev[i + 1], guided[2 * i + 1])
             x1 = ops.heun_correct(x, dx, x1, D1, t0, t1) if Dg1 is None else \
                 ops.heun_correct_guided(x, dx, x1, D1, Dg1, w_dev, t0, t1)
-        return x1
+        return dx, x1
+
+    # ------------------------------------------------------------------ the teacher's recorder
+    def _check_trace(self) -> None:
+        """which solvers can record their solve (the Heun ones whose steps start at the table's own states)"""
+        if type(self)._step is not DeterministicSolver._step:
+            raise ValueError(f"{type(self).__name__}.trace: the recorder follows the Heun step of DeterministicSolver; "
+                             f"{type(self).__name__} takes another step")
+        if type(self)._step_start is not DeterministicSolver._step_start and self._graph_key_extra():
+            raise ValueError(f"{type(self).__name__}.trace: a churned solve is not an ODE and has no trajectory to record; "
+                             "set S_churn = 0 (or use DeterministicSolver)")
+
+    @torch.no_grad()
+    def trace(self, model, x0, class_labels=None, *, graph: bool = False, start_step: int = 0, image=None, mask=None,
+              degradation=None, measurement=None, operator=None, dps_scale=None) -> Trajectory:
+        """The plain eager Heun solve with what its loop computes kept: Trajectory(x, slope, sigmas), x fp32
+        [N + 1, B, ...] the states at t_0 .. t_N (x[0] = ops.scale_f32(x0, t_0) and x[N] = solve(model, x0, labels), bit
+        for bit), slope fp32 [N, B, ...] the Euler slope at (x_i, t_i) as ops.heun_euler / heun_euler_guided return it (of
+        the mixed D with a guide; guidance_interval is honoured).  The two buffers are allocated once and written row by
+        row.  Image conditioning, restoration, posterior sampling and graph=True raise ValueError."""
+        for name, on in (("graph=True", graph), ("start_step", start_step != 0), ("image", image is not None),
+                         ("mask", mask is not None), ("degradation", degradation is not None),
+                         ("measurement", measurement is not None), ("operator", operator is not None),
+                         ("dps_scale", dps_scale is not None)):
+            if on:
+                raise ValueError(f"{type(self).__name__}.trace: {name} is not implemented for the recorder (it runs the "
+                                 "plain eager solve); use solve")
+        self._check_trace()
+        guided = self.guided_evaluations()
+        _check_float("trace", "x0", x0)
+        if x0.dim() < 2 or x0.numel() == 0:
+            raise ValueError(f"trace: x0 must be a non-empty [B, ...] tensor, got {tuple(x0.shape)}")
+        _check_gpu(type(self).__name__, "x0", x0)
+        if any(guided):
+            self._check_guide(model, x0.device, class_labels)
+        x0 = x0.float().contiguous()
+        N, ts, t_dev = self.num_steps, self.t_steps.tolist(), self.t_steps.to(x0.device)
+        w_dev = torch.full((1,), float(self.guidance), device=x0.device) if any(guided) else None
+        X = torch.empty((N + 1, *x0.shape), dtype=torch.float32, device=x0.device)
+        slope = torch.empty((N, *x0.shape), dtype=torch.float32, device=x0.device)
+
+        def evaluate(x, sigma, flag):
+            return self._evaluate(model, x, sigma, class_labels, flag, w_dev, None)
+        X[0].copy_(ops.scale_f32(x0, ts[0]))
+        for i in range(N):
+            dx, x1 = self._heun_step(evaluate, X[i], i, ts, t_dev, guided, w_dev, None)
+            slope[i].copy_(dx)
+            X[i + 1].copy_(x1)
+        return Trajectory(X, slope, self.t_steps.clone())
 
     # ------------------------------------------------------------------ diffusion posterior sampling
     def _posterior(self, model, x0, guided, mask, graph, degradation, operator, measurement, dps_scale):
@@ -843,13 +935,13 @@ class StochasticSolver(DeterministicSolver):
     def __init__(self, num_steps: int = 18, sigma_min: float = 0.002, sigma_max: float = 80.0, rho: float = 7.0,
                  dtype: str | None = None, *, guide=None, guidance: float = 1.0,
                  guidance_interval: tuple[float, float] | None = None, S_churn: float = 0.0, S_min: float = 0.0,
-                 S_max: float = math.inf, S_noise: float = 1.0, seed: int = 0):
+                 S_max: float = math.inf, S_noise: float = 1.0, seed: int = 0, sigmas=None):
         self.S_churn = S_churn
         self.S_min = S_min
         self.S_max = S_max
         self.S_noise = S_noise
         super().__init__(num_steps, sigma_min, sigma_max, rho, dtype, guide=guide, guidance=guidance,
-                         guidance_interval=guidance_interval, seed=seed)    # (validates the churn settings too)
+                         guidance_interval=guidance_interval, seed=seed, sigmas=sigmas)  # (validates the churn settings too)
 
     def churn_schedule(self) -> ChurnSchedule:
         """gamma_i, t_hat_i and c_i of every step, computed in fp64 from the fp32 sigma table and rounded to fp32
@@ -940,11 +1032,13 @@ class MultistepSolver(DeterministicSolver):
 
     def __init__(self, num_steps: int = 18, sigma_min: float = 0.002, sigma_max: float = 80.0, rho: float = 7.0,
                  dtype: str | None = None, *, order: int = 2, guide=None, guidance: float = 1.0,
-                 guidance_interval: tuple[float, float] | None = None, seed: int = 0):
+                 guidance_interval: tuple[float, float] | None = None, seed: int = 0, sigmas=None):
+        if sigmas is not None:
+            num_steps = _sigma_table("MultistepSolver", sigmas).numel()
         _check_multistep(num_steps, order)
         self.order = order
         super().__init__(num_steps, sigma_min, sigma_max, rho, dtype, guide=guide, guidance=guidance,
-                         guidance_interval=guidance_interval, seed=seed)
+                         guidance_interval=guidance_interval, seed=seed, sigmas=sigmas)
 
     def _steps(self, start_step: int = 0) -> tuple:
         """(k_i, a_i, c0_i, c1_i, c2_i) per step: the effective order and the fp32 coefficients as host floats.  A
@@ -1028,6 +1122,10 @@ class _IteratedSolver(DeterministicSolver):
                 raise ValueError(f"{type(self).__name__}.{who}: {name} is not implemented for {self._REFUSAL}; use "
                                  "DeterministicSolver")
 
+    def trace(self, *args, **kwargs):
+        raise ValueError(f"{type(self).__name__}.trace: the recorder is not implemented for {self._REFUSAL}; use "
+                         "DeterministicSolver")
+
     def _check_tolerances(self) -> None:
         for name in ("rtol", "atol"):
             v = getattr(self, name)
@@ -1104,7 +1202,8 @@ class AdaptiveSolver(_IteratedSolver):
                  dtype: str | None = None, *, guide=None, guidance: float = 1.0,
                  guidance_interval: tuple[float, float] | None = None, seed: int = 0, rtol: float = 1e-3,
                  atol: float = 1e-4, max_iterations: int = 1024, safety: float = 0.9, fac_min: float = 0.2,
-                 fac_max: float = 5.0, h_floor: float = 1e-6):
+                 fac_max: float = 5.0, h_floor: float = 1e-6, sigmas=None):
+        self._refuse("__init__", sigmas=sigmas is not None)     # (it has no table: it integrates between the table's ends)
         self.rtol, self.atol, self.max_iterations = rtol, atol, max_iterations
         self.safety, self.fac_min, self.fac_max, self.h_floor = safety, fac_min, fac_max, h_floor
         self.last_stats = None
@@ -1271,14 +1370,17 @@ class ParallelSolver(_IteratedSolver):
 
     def __init__(self, num_steps: int = 18, sigma_min: float = 0.002, sigma_max: float = 80.0, rho: float = 7.0,
                  dtype: str | None = None, *, window: int = 16, order: int = 2, rtol: float = 1e-3, atol: float = 1e-4,
-                 guide=None, guidance: float = 1.0, guidance_interval: tuple[float, float] | None = None, seed: int = 0):
+                 guide=None, guidance: float = 1.0, guidance_interval: tuple[float, float] | None = None, seed: int = 0,
+                 sigmas=None):
         self.window, self.order, self.rtol, self.atol = window, order, rtol, atol
         self.last_stats = None
+        if sigmas is not None:
+            num_steps = _sigma_table("ParallelSolver", sigmas).numel()
         if isinstance(num_steps, bool) or not isinstance(num_steps, int) or num_steps < 2:
             raise ValueError(f"ParallelSolver: needs num_steps >= 2 (steps 0 .. N-2 are iterated, the last one closes), got "
                              f"{num_steps!r}")
         super().__init__(num_steps, sigma_min, sigma_max, rho, dtype, guide=guide, guidance=guidance,
-                         guidance_interval=guidance_interval, seed=seed)
+                         guidance_interval=guidance_interval, seed=seed, sigmas=sigmas)
 
     def guided_evaluations(self) -> tuple[bool, ...]:
         """(whether the evaluations are guided,): all of them or none.  Host only; raises ValueError on an invalid
