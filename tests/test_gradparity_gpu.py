@@ -122,6 +122,11 @@ def _grad_parity(tag, ecfg, dcfg, shape, P_mean, P_std, seed_params, seed_data, 
                 per[k] = abs(gr.item() - go.item()) / max(abs(go.item()), scal_rms)
             else:
                 per[k] = rel(gr, go)
+            if k.endswith(".qkv_conv.weight"):
+                # the q, k and v rows on their own (row = head*3d + dd*3 + which, tests/test_kernels_gpu.py::_qkv_perm)
+                for wi, nm in enumerate("qkv"):
+                    rows = lambda t: t.detach().reshape(dcfg.num_heads, -1, 3, *t.shape[1:])[:, :, wi]
+                    per[f"{k}[{nm} rows]"] = rel(rows(gr), rows(go))
         worst = max(per, key=per.get)
         out[leg] = {"worst_tensor": worst, "worst": per[worst], "limit": lim, "median": float(np.median(list(per.values()))),
                     "n_tensors": len(per), "per_tensor": {k: round(v, 6) for k, v in sorted(per.items())}}
