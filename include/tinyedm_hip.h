@@ -1092,6 +1092,38 @@ int edm_f32_pool_features(const float* x, float* out, int B, int HW, int C, long
 int edm_pair_step_errors(const float* X, const float* S, const double* tau, int B, int G, long K, int order, double* d2,
                          edm_stream_t stream);
 
+/* ---------------------------------------------------------------- feature clustering (csrc/kmeans.hip) */
+/* The update half of a Lloyd iteration (k-means on features: Hu et al. 2023, "Self-guided diffusion models"; the reference
+ * has no call site for it): per cluster, the column sums of its member rows in fp64, each float32 widened as it is loaded,
+ * through an inverted index.  The assignment half is edm_f32_knn_partial with k = 1.
+ * The order.  Cluster k's rows are listed in ascending row number; the row at position p of that list is in chunk
+ * p / EDM_CLUSTER_BLOCK.  partial(chunk) = (((+0.0 + row_0) + row_1) + ...) over the chunk's rows in ascending position;
+ * sums[k] = (((+0.0 + partial_0) + partial_1) + ...) over the cluster's chunks in ascending chunk number.  d2sums follows
+ * the same sequence on d2[row].  The bits of an output element are a function of the cluster's member list (and the
+ * values) alone: not of K, n, the other clusters, the grid, or the load path (16-byte loads when D % 4 == 0 and x is
+ * 16-byte aligned, element loads otherwise).  No atomics; a cluster without members gets +0.0.
+ * edm_cluster_block: EDM_CLUSTER_BLOCK as the library was built (host logic only): the caller cuts its chunk tables with
+ *   this value, so a library built with another chunk length stays consistent with its callers.
+ * edm_f32_cluster_sums_partial: x float32 [n][D] row-contiguous, 4-byte aligned; members int32 [n]: the rows of cluster 0
+ *   ascending, then cluster 1, ...; starts int32 [K+1]: cluster k owns members[starts[k] .. starts[k+1]); chunk_first int32
+ *   [K+1]: cluster k owns the chunks chunk_first[k] .. chunk_first[k+1], ceil(its members / EDM_CLUSTER_BLOCK) of them;
+ *   chunk_cluster int32 [n_chunks]; d2 fp64 [n] or null.  Writes partial fp64 [n_chunks][D] and, with d2, partial_d2 fp64
+ *   [n_chunks]: the whole workspace is n_chunks (D + 1) <= (n / EDM_CLUSTER_BLOCK + K)(D + 1) doubles.  The tables are
+ *   the caller's responsibility (every member a row number in [0, n)).
+ * edm_f32_cluster_sums_finish: sums fp64 [K][D] and, when partial_d2 and d2sums are given, d2sums fp64 [K]; every element
+ *   written.
+ * Limits, status -1 otherwise: 1 <= n <= 2^31 - 64, 1 <= D <= 32768, 1 <= K <= 2^20, 1 <= n_chunks <= n /
+ * EDM_CLUSTER_BLOCK + K. */
+#ifndef EDM_CLUSTER_BLOCK
+#define EDM_CLUSTER_BLOCK 64
+#endif
+int edm_cluster_block(void);
+int edm_f32_cluster_sums_partial(const void* x, const int* members, const int* starts, const int* chunk_first,
+                                 const int* chunk_cluster, const double* d2, long n, int D, int K, long n_chunks,
+                                 double* partial, double* partial_d2, edm_stream_t stream);
+int edm_f32_cluster_sums_finish(const double* partial, const double* partial_d2, const int* chunk_first, int D, int K,
+                                double* sums, double* d2sums, edm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,7 @@ alias package re-exports these names so reference configs (``_target_: tinyedm.E
 __version__ = "0.1.0"
 
 from . import _runtime_env  # noqa: F401  (first: sets HIP runtime flags before anything can initialise the GPU)
+from .cluster import KMeans, mode_report
 from .edm import EDM, Diffuser
 from .ema import EMA, EMAOptimizer, FusedAdam, sigma_rel_to_gamma
 from .features import FeatureExtractor
@@ -17,9 +18,9 @@ from .solvers import (AdaptiveSolver, DeterministicSolver, GaussianBlur, LinearD
                       ParallelSolver, ParallelStats, StochasticSolver, Trajectory)
 from .trainer import LightningModule, Trainer
 from .vjp import input_vjp
-from . import config, networks, ops
+from . import cluster, config, networks, ops
 
-__all__ = ["EDM", "Diffuser", "DeterministicSolver", "StochasticSolver", "MultistepSolver", "AdaptiveSolver", "ParallelSolver", "ParallelStats", "Trajectory", "Schedule", "optimize_schedule", "LinearDegradation", "GaussianBlur", "input_vjp", "IdealDenoiser", "FeatureExtractor", "ManifoldMetrics", "DistributionDistance", "FeatureStats", "frechet_distance", "kid", "kid_from_sums",
+__all__ = ["EDM", "Diffuser", "DeterministicSolver", "StochasticSolver", "MultistepSolver", "AdaptiveSolver", "ParallelSolver", "ParallelStats", "Trajectory", "Schedule", "optimize_schedule", "LinearDegradation", "GaussianBlur", "input_vjp", "IdealDenoiser", "FeatureExtractor", "ManifoldMetrics", "KMeans", "mode_report", "DistributionDistance", "FeatureStats", "frechet_distance", "kid", "kid_from_sums",
            "subset_indices", "WeightedMeanSquaredError", "Denoiser", "Linear", "Conv2d",
            "Embedding", "DenoiserWrapper", "EMA", "EMAOptimizer", "FusedAdam", "Trainer", "LightningModule",
-           "sigma_rel_to_gamma", "manual_seed", "config", "networks", "ops"]
+           "sigma_rel_to_gamma", "manual_seed", "cluster", "config", "networks", "ops"]

@@ -234,6 +234,10 @@ SIGNATURES = {
     "edm_f32_pool_features": [P, P, I, I, I, L, I, P],
     # schedule.hip
     "edm_pair_step_errors": [P, P, P, I, I, L, I, P, P],
+    # kmeans.hip
+    "edm_cluster_block": [],
+    "edm_f32_cluster_sums_partial": [P, P, P, P, P, P, L, I, I, L, P, P, P],
+    "edm_f32_cluster_sums_finish": [P, P, P, I, I, P, P, P],
 }
 # include/tinyedm_hip_diag.h: tools-only entry points, bound on demand by call()
 DIAG_SIGNATURES = {
@@ -251,7 +255,7 @@ _NO_STATUS = {"edm_lowrank_wgrad_workspace", "edm_lowrank_supported", "edm_lowra
               "edm_wgrad3_apply_table_bytes",
               "edm_conv_wgrad_1x1_group_table_bytes", "edm_wgrad_finish_multi_table_bytes", "edm_attention_qkv_supported",
               "edm_attention_long_supported", "edm_conv_in_dgrad_pack_cols",
-              "edm_u8_knn_splits", "edm_moments_splits", "edm_sample_chunks", "edm_f32_knn_splits"}
+              "edm_u8_knn_splits", "edm_moments_splits", "edm_sample_chunks", "edm_f32_knn_splits", "edm_cluster_block"}
 
 _lib = None
 

@@ -14,6 +14,7 @@ reference's predict-time dataset (datamodules/random_datamodule.py:6-18: N(0,1) 
 from __future__ import annotations
 
 import gzip
+import json
 import os
 import pickle
 import struct
@@ -164,6 +165,27 @@ def read_mnist(data_dir: str, train: bool):
     return x, y
 
 
+def read_label_file(path, n: int, num_classes: int) -> np.ndarray:
+    """A label file as int64 [n]: a JSON list of integers in sample order (what `tinyedm.cluster --labels_out` writes) or an
+    .npy integer array; exactly n entries, every one in [0, num_classes)."""
+    path = str(path)
+    if path.endswith(".npy"):
+        a = np.load(path, allow_pickle=False)
+        if a.ndim != 1 or a.dtype.kind not in "iu":
+            raise ValueError(f"{path}: expected a 1-d integer array, got {a.dtype} {a.shape}")
+    else:
+        with open(path) as f:
+            v = json.load(f)
+        if not isinstance(v, list) or not all(isinstance(i, int) and not isinstance(i, bool) for i in v):
+            raise ValueError(f"{path}: expected a JSON list of integers")
+        a = np.asarray(v, dtype=np.int64).reshape(-1)
+    if a.shape[0] != n:
+        raise ValueError(f"{path}: holds {a.shape[0]} labels, the split has {n} samples")
+    if n and (int(a.min()) < 0 or int(a.max()) >= num_classes):
+        raise ValueError(f"{path}: labels must lie in [0, {num_classes}), got {int(a.min())} .. {int(a.max())}")
+    return a.astype(np.int64)
+
+
 def _rank_world(rank=None, world=None):
     """this process's (rank, world size): explicit arguments, else torch.distributed, else the launcher's env"""
     if rank is not None and world is not None:
@@ -244,16 +266,30 @@ class AbstractDataModule:
     ``augment_prob`` / ``augment_ops`` (extensions of the image datamodules): non-leaking augmentation of the TRAIN loader,
     each op applied per sample with probability augment_prob; its batches are then (x, y, augment_labels (B, 6)).
     ``augment_warp_ops`` (default none): the continuous ops of the same pipe -- zoom, rotate, stretch, shift -- applied after
-    the exact ones with the same probability; the batches then carry 13 labels (``Embedding(augment_dim=13)``)."""
+    the exact ones with the same probability; the batches then carry 13 labels (``Embedding(augment_dim=13)``).
+
+    ``labels_path`` / ``val_labels_path`` / ``label_classes`` (extension, default off): label files (read_label_file) that
+    replace the datasets' own labels -- pseudo-labels such as the k-means clusters of `tinyedm.cluster`.  One file per
+    split (the validation file also serves the test loader, which is the same split), and num_classes becomes
+    label_classes.  All three go together: a conditional net validated on foreign labels reports a meaningless val_loss."""
 
     AUGMENT_OPS = ("xflip", "yflip", "translate", "rot90")
     AUGMENT_WARP_OPS = ("zoom", "rotate", "stretch", "shift")
     AUGMENT_WARP_SIZES = (2, 64)        # the resampling kernel's range of image sides
 
     def __init__(self, data_dir, batch_size: int, num_workers: int = 0, device: str | None = None, seed: int = 42,
-                 augment_prob: float = 0.0, augment_ops=AUGMENT_OPS, augment_warp_ops=()):
+                 augment_prob: float = 0.0, augment_ops=AUGMENT_OPS, augment_warp_ops=(), labels_path=None,
+                 val_labels_path=None, label_classes=None):
         self.data_dir, self.batch_size, self.num_workers = data_dir, batch_size, num_workers
         self.device, self.seed = device, seed
+        given = [labels_path is not None, val_labels_path is not None, label_classes is not None]
+        if any(given) and not all(given):
+            raise ValueError("labels_path, val_labels_path and label_classes go together: the training labels, the "
+                             "validation labels and the number of classes they index")
+        if label_classes is not None and (isinstance(label_classes, bool) or not isinstance(label_classes, int)
+                                          or label_classes < 1):
+            raise ValueError(f"label_classes must be an integer >= 1, got {label_classes!r}")
+        self.labels_path, self.val_labels_path, self.label_classes = labels_path, val_labels_path, label_classes
         self.augment_prob, self.augment_ops = float(augment_prob), tuple(augment_ops)
         if not 0.0 <= self.augment_prob <= 1.0:
             raise ValueError(f"augment_prob must be in [0, 1], got {augment_prob}")
@@ -272,6 +308,12 @@ class AbstractDataModule:
 
     def prepare_data(self):
         pass
+
+    def _split(self, x, y, train: bool):
+        """a split as read from disk -> resident; with labels_path its labels come from the split's label file"""
+        if self.labels_path is not None:
+            y = read_label_file(self.labels_path if train else self.val_labels_path, x.shape[0], self.label_classes)
+        return self._resident(x, y)
 
     def _resident(self, x, y):
         if self.augment_prob > 0 and "rot90" in self.augment_ops and x.shape[-2] != x.shape[-1]:
@@ -312,8 +354,10 @@ class CIFAR10DataModule(AbstractDataModule):
 
     def __init__(self, data_dir: str = "datasets/cifar", image_size: int = 32, batch_size: int = 16, num_workers: int = 16,
                  device: str | None = None, seed: int = 42, augment_prob: float = 0.0,
-                 augment_ops=AbstractDataModule.AUGMENT_OPS, augment_warp_ops=()):
-        super().__init__(data_dir, batch_size, num_workers, device, seed, augment_prob, augment_ops, augment_warp_ops)
+                 augment_ops=AbstractDataModule.AUGMENT_OPS, augment_warp_ops=(), labels_path=None, val_labels_path=None,
+                 label_classes=None):
+        super().__init__(data_dir, batch_size, num_workers, device, seed, augment_prob, augment_ops, augment_warp_ops,
+                         labels_path, val_labels_path, label_classes)
         if image_size != 32:
             raise ValueError("CIFAR10DataModule: only the native image_size 32 is supported")
         self.img_size, self.flip = image_size, True
@@ -323,14 +367,14 @@ class CIFAR10DataModule(AbstractDataModule):
 
     def setup(self, stage=None):
         if stage == "fit" or stage is None:
-            self.train_dataset = self._resident(*read_cifar10(self.data_dir, True))
-            self.val_dataset = self._resident(*read_cifar10(self.data_dir, False))
+            self.train_dataset = self._split(*read_cifar10(self.data_dir, True), True)
+            self.val_dataset = self._split(*read_cifar10(self.data_dir, False), False)
         if stage == "test":
-            self.test_dataset = self._resident(*read_cifar10(self.data_dir, False))
+            self.test_dataset = self._split(*read_cifar10(self.data_dir, False), False)
 
     @property
     def num_classes(self) -> int:
-        return 10
+        return 10 if self.label_classes is None else self.label_classes
 
 
 class MNISTDataModule(AbstractDataModule):
@@ -339,8 +383,10 @@ class MNISTDataModule(AbstractDataModule):
 
     def __init__(self, batch_size: int, num_workers: int = 0, image_size: int = 28, data_dir: str = "datasets/mnist",
                  device: str | None = None, seed: int = 42, augment_prob: float = 0.0,
-                 augment_ops=AbstractDataModule.AUGMENT_OPS, augment_warp_ops=()):
-        super().__init__(data_dir, batch_size, num_workers, device, seed, augment_prob, augment_ops, augment_warp_ops)
+                 augment_ops=AbstractDataModule.AUGMENT_OPS, augment_warp_ops=(), labels_path=None, val_labels_path=None,
+                 label_classes=None):
+        super().__init__(data_dir, batch_size, num_workers, device, seed, augment_prob, augment_ops, augment_warp_ops,
+                         labels_path, val_labels_path, label_classes)
         if image_size != 28:
             raise ValueError("MNISTDataModule: only the native image_size 28 is supported")
 
@@ -349,14 +395,14 @@ class MNISTDataModule(AbstractDataModule):
 
     def setup(self, stage=None):
         if stage == "fit" or stage is None:
-            self.train_dataset = self._resident(*read_mnist(self.data_dir, True))
-            self.val_dataset = self._resident(*read_mnist(self.data_dir, False))
+            self.train_dataset = self._split(*read_mnist(self.data_dir, True), True)
+            self.val_dataset = self._split(*read_mnist(self.data_dir, False), False)
         if stage == "test":
-            self.test_dataset = self._resident(*read_mnist(self.data_dir, False))
+            self.test_dataset = self._split(*read_mnist(self.data_dir, False), False)
 
     @property
     def num_classes(self) -> int:
-        return 10
+        return 10 if self.label_classes is None else self.label_classes
 
 
 class _LatentLoader:

@@ -3972,6 +3972,83 @@ def f32_pool_features(x, out=None, offset=0):
     return out
 
 
+# ------------------------------------------------------------------ feature clustering (csrc/kmeans.hip)
+CLUSTER_MAX_K = 2 ** 20
+
+
+def cluster_block() -> int:
+    """EDM_CLUSTER_BLOCK as the loaded library was built: rows per chunk of a cluster's member list (the chunk tables are
+    cut with the library's own value, so a library built with another chunk length gets tables that fit it)"""
+    return int(_lib.call("edm_cluster_block"))
+
+
+def _cluster_index(labels, K, counts):
+    """the inverted index of int64 labels [n] in [0, K) -> (members int32 [n], starts int32 [K + 1], chunk_first int32
+    [K + 1], chunk_cluster int32 [chunks]): cluster k's rows in ascending row number (a stable sort), cut into chunks of
+    cluster_block() rows.  counts: the bincount of the labels as a numpy int64 [K] array; the tables are made from it on
+    the host (K entries), so nothing here waits for the device."""
+    dev, block = labels.device, cluster_block()
+    members = torch.sort(labels, stable=True).indices.to(torch.int32)
+    per = (counts + (block - 1)) // block
+    starts, first = np.zeros(K + 1, np.int64), np.zeros(K + 1, np.int64)
+    np.cumsum(counts, out=starts[1:])
+    np.cumsum(per, out=first[1:])
+    chunk_cluster = np.repeat(np.arange(K, dtype=np.int32), per)
+    up = lambda a: torch.from_numpy(a.astype(np.int32)).to(dev)       # noqa: E731
+    return members, up(starts), up(first), up(chunk_cluster)
+
+
+def f32_cluster_sums(x, labels, K, d2=None, *, counts=None):
+    """Per-cluster sums of the rows of x (float32 [n, ...], taken as [n, D]) -> (sums fp64 [K, D], counts int64 [K], d2sums
+    fp64 [K] or None): sums[k] = the fp64 column sums of the rows with labels == k, each float32 widened as it is loaded,
+    and d2sums[k] = the sum of d2 (fp64 [n] or None) over the same rows.  labels: int64 [n] on the device, any order, every
+    entry in [0, K).  The addition order is a function of a cluster's member list alone (ascending row number, chunks of
+    cluster_block() rows added in order: include/tinyedm_hip.h), so the same arguments give the same bits and the sums of
+    a cluster do not depend on K or on the other clusters.  No atomics and no fp64 copy of the set: the workspace is at
+    most (n / cluster_block() + K)(D + 1) doubles.  An empty cluster gives +0.0 and a count of 0.  The input must be finite
+    (the callers that take a set in check it once).
+    The call waits for the device three times (the least and the largest label, then the counts, from which the chunk
+    tables are made on the host).  counts: the bincount of the labels as a numpy int64 [K] array, from a caller that made
+    the labels itself and holds it already (cluster.lloyd_step): the labels are then taken as valid and the call reads
+    nothing back.  Counts that do not belong to the labels give wrong sums, never an access outside the set."""
+    x2 = _fknn_rows(x, "x")
+    n, D = x2.shape
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= CLUSTER_MAX_K:
+        raise ValueError(f"f32_cluster_sums: K must be an integer in [1, {CLUSTER_MAX_K}], got {K!r}")
+    if not 1 <= D <= KNN_MAX_D or n > FKNN_MAX_R:
+        raise ValueError(f"f32_cluster_sums: expected at most 2^31 - 64 rows of 1 to {KNN_MAX_D} elements, got {tuple(x2.shape)}")
+    dev = x.device
+    if counts is None:
+        _row_index(labels, K, "labels", dev, 1)
+    else:
+        if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or labels.dim() != 1:
+            raise ValueError("labels: expected an int64 tensor of 1 dimension")
+        _chk_eval(labels, torch.int64, "labels", None, dev)
+        if not (isinstance(counts, np.ndarray) and counts.dtype == np.int64 and counts.shape == (K,)
+                and int(counts.min()) >= 0 and int(counts.sum()) == n):
+            raise ValueError(f"counts: expected a numpy int64 [{K}] array of non-negative counts that add up to {n}")
+    if labels.shape[0] != n:
+        raise ValueError(f"labels: expected one label per row ({n}), got {labels.shape[0]}")
+    if d2 is not None:
+        _chk_eval(d2, torch.float64, "d2", (n,), dev)
+    if counts is None:
+        counts_dev = torch.bincount(labels, minlength=K)
+        counts = counts_dev.cpu().numpy()
+    else:
+        counts_dev = torch.from_numpy(counts).to(dev)
+    members, starts, first, chunk_cluster = _cluster_index(labels, K, counts)
+    chunks = chunk_cluster.shape[0]
+    partial = torch.empty(chunks, D, dtype=torch.float64, device=dev)
+    partial_d2 = None if d2 is None else torch.empty(chunks, dtype=torch.float64, device=dev)
+    sums = torch.empty(K, D, dtype=torch.float64, device=dev)
+    d2sums = None if d2 is None else torch.empty(K, dtype=torch.float64, device=dev)
+    with _prof("f32_cluster_sums", float(n) * D, 4.0 * n * D + 16.0 * chunks * D + 8.0 * K * D):
+        _lib.call("edm_f32_cluster_sums_partial", _p(x2), _p(members), _p(starts), _p(first), _p(chunk_cluster), _p(d2), n, D,
+                  K, chunks, _p(partial), _p(partial_d2), _stream())
+        _lib.call("edm_f32_cluster_sums_finish", _p(partial), _p(partial_d2), _p(first), D, K, _p(sums), _p(d2sums), _stream())
+    return sums, counts_dev, d2sums
+
+
 # ------------------------------------------------------------------ optimised sampling schedules (csrc/schedule.hip)
 SCHEDULE_MAX_GRID = 256         # EDM_SCHEDULE_MAX_GRID: nodes of the teacher grid edm_pair_step_errors takes
 
