@@ -1124,6 +1124,47 @@ int edm_f32_cluster_sums_partial(const void* x, const int* members, const int* s
 int edm_f32_cluster_sums_finish(const double* partial, const double* partial_d2, const int* chunk_first, int D, int K,
                                 double* sums, double* d2sums, edm_stream_t stream);
 
+/* ---------------------------------------------------------------- paired image quality (csrc/quality.hip) */
+/* SSIM and the squared error of image i against image i (Wang, Bovik, Sheikh, Simoncelli 2004; the reference has no call
+ * site for it).  a, b: n images of C channels, H x W, both uint8 (is_u8) or both float32 in pixel units; element (i, c, y,
+ * x) of a sits at a + i strides_a[0] + c strides_a[1] + y strides_a[2] + x strides_a[3] (HOST arrays of 4 element strides,
+ * >= 0), so uint8 NHWC and float32 NCHW go through one kernel without a copy.  window: DEVICE fp64 [win], the 1-D taps as
+ * the host built them (the same bits as the reference uses); win odd, 3 <= win <= 15, win <= min(H, W).  data_range L:
+ * C1 = (0.01 L)^2, C2 = (0.03 L)^2.  Per image and channel, in fp64 throughout: the five separably filtered maps mu_a,
+ * mu_b, E[a^2], E[b^2], E[ab] over the VALID region (window centres at least (win - 1) / 2 from every edge, no padding),
+ *   S = (2 mu_a mu_b + C1)(2 cov + C2) / ((mu_a^2 + mu_b^2 + C1)(var_a + var_b + C2))     (biased variances),
+ * ssim fp64 [n][C] = the mean of S; sse fp64 [n][C] = sum (a - b)^2 over the counted pixels (uint8: an exact integer below
+ * 2^53); counts int32 [n][2] = (counted pixels, counted window centres).  region: uint8 [n][H][W], or [1][H][W] with
+ * region_shared, or null = everything counted; non-zero = counted.  sse runs over counted pixels, the mean over valid
+ * centres that are themselves counted (the windows still read every pixel); no counted centre: counts[i][1] = 0 and NaN.
+ * The order.  The valid region is cut into tiles of 16 x 32 centres from its corner (edm_pair_ssim_tiles of them, a
+ * function of (H, W, win)).  In a tile, thread t of 256 adds its centres t, t + 256 (row-major in the tile) in ascending
+ * order, then a halving tree over the threads; the tiles are added in row-major tile order.  A tile owns the pixels of
+ * its 16 x 32 block (the last tile row / column also the halo behind it) for sse, same order.  The bits of row i depend
+ * on that image pair, the shape, the window and the region row alone: not on n, the row's place or the strides.  No
+ * atomics; every output element is one ordinary store.  partial: workspace fp64 [n C tiles][4].
+ * Limits, status -1 otherwise: H W < 2^31, n C tiles < 2^31 (launched in chunks of 2^23 workgroups, which changes no bit).
+ * edm_pair_ssim_tiles: the tiles of one plane (host logic only); 0 for a window the library refuses. */
+long edm_pair_ssim_tiles(int H, int W, int win);
+int edm_pair_ssim(const void* a, const void* b, int is_u8, long n, int C, int H, int W, const long* strides_a,
+                  const long* strides_b, const double* window, int win, double data_range, const unsigned char* region,
+                  int region_shared, double* partial, double* ssim, double* sse, int* counts, edm_stream_t stream);
+/* The LPIPS form of a distance between two sets of activations (Zhang et al. 2018, without its learned linear layers and
+ * with the project's own denoiser in the place of VGG / AlexNet: NOT LPIPS; the reference has no call site for it).
+ * a, b fp32 [B][HW][C] contiguous (NHWC maps of one tap).  Row b of out starts at out + b * out_stride (doubles) and only
+ * its element `column` is written:
+ *   out[b][column] = (1 / HW) sum_p sum_c (a_pc / (|a_p| + 1e-10) - b_pc / (|b_p| + 1e-10))^2       in fp64,
+ * in the two-pass form per pixel (the norms, then the squared differences of the scaled values, x * (1 / (|x| + 1e-10)),
+ * each product rounded before the subtraction), never 2 - 2 cos: identical inputs give exactly +0.0; an all-zero pixel vector gives 0 / 1e-10 = 0.
+ * The order, a function of (HW, C) alone.  One wave per pixel: lane l adds the channels of its quads l, l + 64, l + 128
+ * in ascending order, then the xor butterfly (32, 16, .. 1).  Wave w of 8 adds the pixels w, w + 8, ... in ascending
+ * order; the 8 wave totals are added in ascending order and divided by HW once.  Row b depends on neither B, its place
+ * nor the load path (16-byte loads when C % 4 == 0 and a, b are 16-byte aligned, element loads otherwise).  No atomics.
+ * Limits, status -1 otherwise: 1 <= C <= 768 (a pixel row of each map stays in one wave's registers), 0 <= column <
+ * out_stride. */
+int edm_f32_pair_feature_distance(const float* a, const float* b, double* out, int B, int HW, int C, long out_stride,
+                                  int column, edm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

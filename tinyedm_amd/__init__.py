@@ -5,6 +5,7 @@ __version__ = "0.1.0"
 
 from . import _runtime_env  # noqa: F401  (first: sets HIP runtime flags before anything can initialise the GPU)
 from .cluster import KMeans, mode_report
+from .compare import PairedQuality
 from .edm import EDM, Diffuser
 from .ema import EMA, EMAOptimizer, FusedAdam, sigma_rel_to_gamma
 from .features import FeatureExtractor
@@ -20,7 +21,7 @@ from .trainer import LightningModule, Trainer
 from .vjp import input_vjp
 from . import cluster, config, networks, ops
 
-__all__ = ["EDM", "Diffuser", "DeterministicSolver", "StochasticSolver", "MultistepSolver", "AdaptiveSolver", "ParallelSolver", "ParallelStats", "Trajectory", "Schedule", "optimize_schedule", "LinearDegradation", "GaussianBlur", "input_vjp", "IdealDenoiser", "FeatureExtractor", "ManifoldMetrics", "KMeans", "mode_report", "DistributionDistance", "FeatureStats", "frechet_distance", "kid", "kid_from_sums",
+__all__ = ["EDM", "Diffuser", "DeterministicSolver", "StochasticSolver", "MultistepSolver", "AdaptiveSolver", "ParallelSolver", "ParallelStats", "Trajectory", "Schedule", "optimize_schedule", "LinearDegradation", "GaussianBlur", "input_vjp", "IdealDenoiser", "FeatureExtractor", "PairedQuality", "ManifoldMetrics", "KMeans", "mode_report", "DistributionDistance", "FeatureStats", "frechet_distance", "kid", "kid_from_sums",
            "subset_indices", "WeightedMeanSquaredError", "Denoiser", "Linear", "Conv2d",
            "Embedding", "DenoiserWrapper", "EMA", "EMAOptimizer", "FusedAdam", "Trainer", "LightningModule",
            "sigma_rel_to_gamma", "manual_seed", "cluster", "config", "networks", "ops"]

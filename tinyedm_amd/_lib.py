@@ -238,6 +238,10 @@ SIGNATURES = {
     "edm_cluster_block": [],
     "edm_f32_cluster_sums_partial": [P, P, P, P, P, P, L, I, I, L, P, P, P],
     "edm_f32_cluster_sums_finish": [P, P, P, I, I, P, P, P],
+    # quality.hip
+    "edm_pair_ssim_tiles": [I, I, I],
+    "edm_pair_ssim": [P, P, I, L, I, I, I, P, P, P, I, D, P, I, P, P, P, P, P],
+    "edm_f32_pair_feature_distance": [P, P, P, I, I, I, L, I, P],
 }
 # include/tinyedm_hip_diag.h: tools-only entry points, bound on demand by call()
 DIAG_SIGNATURES = {
@@ -247,7 +251,7 @@ DIAG_SIGNATURES = {
     "edm_wgrad3_plan_ksplit": [P, I, P],
     "edm_v6_persistent_launches": [],
 }
-_RET = {"edm_last_error": ctypes.c_char_p, "edm_lowrank_wgrad_workspace": ctypes.c_long, "edm_v6_persistent_launches": ctypes.c_long, "edm_wgrad3_workspace": ctypes.c_long, "edm_wgrad3_table_bytes": ctypes.c_long,
+_RET = {"edm_last_error": ctypes.c_char_p, "edm_pair_ssim_tiles": ctypes.c_long, "edm_lowrank_wgrad_workspace": ctypes.c_long, "edm_v6_persistent_launches": ctypes.c_long, "edm_wgrad3_workspace": ctypes.c_long, "edm_wgrad3_table_bytes": ctypes.c_long,
         "edm_wgrad3_apply_table_bytes": ctypes.c_long,
         "edm_skip_gate_wgrad_multi_table_bytes": ctypes.c_long, "edm_skip_gate_fwd_multi_table_bytes": ctypes.c_long, "edm_skip_gate_bwd_multi_table_bytes": ctypes.c_long,
         "edm_conv_wgrad_1x1_group_table_bytes": ctypes.c_long, "edm_wgrad_finish_multi_table_bytes": ctypes.c_long}
@@ -255,7 +259,7 @@ _NO_STATUS = {"edm_lowrank_wgrad_workspace", "edm_lowrank_supported", "edm_lowra
               "edm_wgrad3_apply_table_bytes",
               "edm_conv_wgrad_1x1_group_table_bytes", "edm_wgrad_finish_multi_table_bytes", "edm_attention_qkv_supported",
               "edm_attention_long_supported", "edm_conv_in_dgrad_pack_cols",
-              "edm_u8_knn_splits", "edm_moments_splits", "edm_sample_chunks", "edm_f32_knn_splits", "edm_cluster_block"}
+              "edm_u8_knn_splits", "edm_moments_splits", "edm_sample_chunks", "edm_f32_knn_splits", "edm_cluster_block", "edm_pair_ssim_tiles"}
 
 _lib = None
 

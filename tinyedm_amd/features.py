@@ -125,35 +125,76 @@ class FeatureExtractor:
         already in network range, on the GPU (uint8 images are moved there).  ids: n distinct integers in [0, 2**32)
         that name the images' noise streams (default 0 .. n - 1)."""
         from . import ops
-        from .callbacks import _eval_dtype
-        u8, f32, labels, ids_dev = self._images(images, labels, ids)
-        src = u8 if u8 is not None else f32
-        n, dev = src.shape[0], src.device
-        out = torch.empty(n, self.dim, dtype=torch.float32, device=dev)
+        out = dev = None
+        for a, b, (maps,), n in self._tapped(images, labels=labels, ids=ids):
+            if out is None:
+                dev = maps[self.taps[0]].device
+                out = torch.empty(n, self.dim, dtype=torch.float32, device=dev)
+            col = 0
+            for t, width in zip(self.taps, self.widths):
+                ops.f32_pool_features(maps[t], out[a:b], col)
+                col += width
+        if out is None:
+            raise ValueError("features: no images")
+        ops.check_health(dev, "FeatureExtractor.extract")
+        return out
+
+    def tapped_maps(self, *image_sets, labels=None, ids=None):
+        """The tapped activations batch by batch: yields (a, b, maps), maps a tuple with one dict {tap: fp32 NHWC map of
+        the images a .. b - 1} per image set, in the order given.  Every set is an `images` of extract() with the same
+        count and shape; image i of every set is noised with the SAME stream (seed, ids[i]) and shares labels[i], so
+        sets that are to be compared image by image (compare.PairedQuality) meet the same noise.  The maps of a batch are
+        the caller's.  Eval mode, network_dtype and no_grad are set for the work of one batch and put back before it is
+        yielded: between batches, and if the generator is abandoned, the model and the grad mode are as the caller
+        left them."""
+        for a, b, maps, _ in self._tapped(*image_sets, labels=labels, ids=ids):
+            yield a, b, maps
+
+    def _tapped(self, *image_sets, labels=None, ids=None):
+        """tapped_maps with the image count as a fourth item"""
+        from . import ops
+        if not image_sets:
+            raise ValueError("features: no images")
+        sets = []
+        for images in image_sets:
+            u8, f32, lab, ids_dev = self._images(images, labels, ids)
+            sets.append((u8, f32))
+            src = u8 if u8 is not None else f32
+            first = sets[0][0] if sets[0][0] is not None else sets[0][1]
+            if src.shape != first.shape or src.dtype != first.dtype or src.device != first.device:
+                raise ValueError(f"features: the image sets differ: {src.dtype} {tuple(src.shape)} on {src.device} against "
+                                 f"{first.dtype} {tuple(first.shape)} on {first.device}")
+        labels = lab
+        n, dev = first.shape[0], first.device
         level = torch.zeros(n, dtype=torch.int32, device=dev)
         sig_dev = torch.tensor([self.sigma], dtype=torch.float32, device=dev)
         rec = ops.churn_record(self.seed, 0, dev)
-        model = self.model
+        for a in range(0, n, self.batch_size):
+            b = min(n, a + self.batch_size)
+            yield a, b, self._batch_maps(sets, a, b, labels, ids_dev, level, sig_dev, rec), n
+
+    def _batch_maps(self, sets, a, b, labels, ids_dev, level, sig_dev, rec) -> tuple:
+        """the maps of images a .. b - 1 of every set; the model's modes are changed here and put back here"""
+        from . import ops
+        from .callbacks import _eval_dtype
+        model, dev = self.model, level.device
         was_training = model.training
         model.eval()
         try:
-            with _eval_dtype(model, self.network_dtype):
-                for a in range(0, n, self.batch_size):
-                    b = min(n, a + self.batch_size)
+            with torch.no_grad(), _eval_dtype(model, self.network_dtype):
+                out = []
+                for u8, f32 in sets:
                     clean = f32[a:b] if u8 is None else ops.u8_gather_normalize(u8, torch.arange(a, b, device=dev), 0.5, 0.5)
                     noisy, sigma = ops.eval_diffuse(clean, ids_dev[a:b], level[a:b], sig_dev, rec, check_levels=False)
                     maps = model.forward_taps(noisy, sigma, None if labels is None else labels[a:b], self.taps)
-                    col = 0
                     for t, width in zip(self.taps, self.widths):
                         if maps[t].shape[-1] != width:
                             raise ValueError(f"features: tap {t} gave {maps[t].shape[-1]} channels, expected {width}")
-                        ops.f32_pool_features(maps[t], out[a:b], col)
-                        col += width
+                    out.append(maps)
+                return tuple(out)
         finally:
             if was_training:
                 model.train()
-        ops.check_health(dev, "FeatureExtractor.extract")
-        return out
 
 
 # ---------------------------------------------------------------------------------------------------- the probes

@@ -113,6 +113,11 @@ sampler produced the class it was asked for.  Without the flag nothing changes.
 `--sigma_table schedule.json` samples on the table that `python -m tinyedm.schedule` optimised for `--num_steps` (a file
 without that N is refused, naming the N it has) instead of the Karras table; it combines with `--solver heun`, `dpmpp`
 and `picard`, `--S_churn` and the guidance flags, and is an error with `--solver adaptive`, which has no table.
+`--quality_report FILE.json` (with `--init_dir` and a task that keeps a ground truth: `--mask_box`, `--restore_*`,
+`--dps_scale`, `--start_step`) scores every output against its init image through compare.PairedQuality, per image: MSE,
+PSNR and SSIM (Wang et al. 2004; 11 taps, or the largest odd window the image holds), for restoration also those of the
+degraded A+ y, for `--mask_box` inside the box only.  `--quality_perceptual` adds the denoiser-feature distance with the
+sampling checkpoint as its own extractor (NOT LPIPS: tinyedm_amd/compare.py).  `--restore_report` stays as it is.
 Multi-GPU = replicas only: under `python -m torch.distributed.run --nproc-per-node N` every rank samples
 its own contiguous index range with its own noise seed and writes `<global index>.png`; there is no collective.
 """
@@ -318,6 +323,31 @@ def _check_restoration(init_dir, restore_scale, restore_gray, save_degraded, res
     return True
 
 
+def _check_quality(quality_report, quality_perceptual, init_dir, start_step, mask_box, invert_to, likelihood_to,
+                   restoring, image_size) -> None:
+    """--quality_report / --quality_perceptual: the choices that need nothing loaded"""
+    if quality_report is None:
+        if quality_perceptual:
+            raise ValueError("generate: --quality_perceptual adds a column to --quality_report: give --quality_report FILE")
+        return
+    if init_dir is None:
+        raise ValueError("generate: --quality_report needs --init_dir (the originals the outputs are scored against)")
+    for flag, on in (("--invert_to", invert_to is not None), ("--likelihood_to", likelihood_to is not None)):
+        if on:
+            raise ValueError(f"generate: --quality_report and {flag} are exclusive: {flag} writes no images")
+    if not (restoring or mask_box is not None or start_step > 0):
+        raise ValueError("generate: --quality_report needs a task that keeps a ground truth: --mask_box, --restore_scale / "
+                         "--restore_gray, --dps_scale or --start_step")
+    if image_size < 3:
+        raise ValueError(f"generate: --quality_report needs images of at least 3 x 3 pixels, got --image_size {image_size}")
+    if mask_box is not None:
+        from .compare import default_win_size, region_from_box
+        try:
+            region_from_box(mask_box, image_size, image_size, default_win_size(image_size))
+        except ValueError as e:
+            raise ValueError(f"generate: --quality_report scores inside --mask_box: {e}") from None
+
+
 def _psnr(x, ref, mean, std) -> torch.Tensor:
     """per-image PSNR in dB of normalised fp32 images against ``ref`` in pixel units [0, 1] (the writer's
     x * std * 2 + mean, clamped): [B] fp32 on x's device"""
@@ -342,7 +372,8 @@ def load_images(init_dir, mean, std, image_size, channels) -> torch.Tensor:
 def _validate(*, solver, S_churn, init_dir, start_step, num_steps, mask_box, invert_to, likelihood_to, network_dtype,
               num_probes, dequantize, image_size, dps_scale, blur_std, blur_radius, measurement_noise, restore_scale,
               restore_gray, save_degraded, restore_report, labels_to, guided, guidance_interval=None, rtol=None, atol=None,
-              max_iterations=None, solver_report=None, window=None, solver_order=2, sigma_table=None) -> tuple:
+              max_iterations=None, solver_report=None, window=None, solver_order=2, sigma_table=None, quality_report=None,
+              quality_perceptual=False) -> tuple:
     """every choice that needs nothing loaded, checked once and in one order for generate() and the command line; returns
     (posterior, restoring): whether the run samples with DPS, and whether it restores (DDNM or DPS)"""
     _check_solver(solver, S_churn)
@@ -363,6 +394,8 @@ def _validate(*, solver, S_churn, init_dir, start_step, num_steps, mask_box, inv
     _check_labels_to(labels_to, init_dir)
     if start_step >= num_steps:
         raise ValueError(f"generate: --start_step must be below --num_steps = {num_steps}, got {start_step}")
+    _check_quality(quality_report, quality_perceptual, init_dir, start_step, mask_box, invert_to, likelihood_to, restoring,
+                   image_size)
     return posterior, restoring
 
 
@@ -375,6 +408,50 @@ def _rank_path(path, rank, world) -> str:
 def _write_json(path, obj) -> None:
     with open(path, "w") as f:
         json.dump(obj, f)
+
+
+class _Collect:
+    """--quality_report: keeps what a task hands to its image writers (fp32, on the device), by name"""
+
+    def __init__(self):
+        self.kept = {}
+
+    def add(self, name, x) -> None:
+        self.kept.setdefault(name, []).append(x.detach().float().clone())
+
+    def write_on_batch_end(self, trainer, pl_module, prediction, batch_indices, batch, batch_idx, dataloader_idx) -> None:
+        self.add("output", prediction)          # (a Trainer.predict callback, beside the PreditionWriter)
+
+    def get(self, name):
+        return torch.cat(self.kept[name]) if name in self.kept else None
+
+
+def _write_quality(path, collect, references, model, perceptual, mean, std, mask_box, image_size, first, seed,
+                   network_dtype, where) -> None:
+    """--quality_report: every kept set against the init images through compare.PairedQuality"""
+    from .compare import PairedQuality, default_win_size, region_from_box, report_rows
+    win = default_win_size(image_size)
+    region = None if mask_box is None else region_from_box(mask_box, image_size, image_size, win)
+    dtype = network_dtype if network_dtype in ("f32x3", "f32") else "f32x3"     # (the taps have no bf16 form)
+    pq = PairedQuality(model if perceptual else None, win_size=win, mean=mean, std=std, seed=seed, network_dtype=dtype)
+    settings = {"data_range": 1.0, "window": pq.window_name, "win_size": win, "win_sigma": pq.win_sigma,
+                "region_box": None if mask_box is None else [int(v) for v in mask_box], "perceptual": bool(perceptual),
+                "first_index": first, "num_images": 0}
+    if perceptual:
+        settings.update(sigma=pq.extractor.sigma, taps=list(pq.extractor.taps), seed=seed, network_dtype=dtype)
+    report = {"settings": settings}
+    for name, key in (("output", "restored"), ("degraded", "degraded")):
+        x = collect.get(name)
+        if x is None:
+            continue
+        ref = references[:x.shape[0]].to(x.device)
+        indices = list(range(first, first + x.shape[0]))
+        scores = pq.score(x, ref, region=region, ids=indices)
+        settings["num_images"] = x.shape[0]
+        report[key] = {"summary": scores["summary"], "images": report_rows(scores, indices)}
+    with open(path, "w") as f:
+        json.dump(report, f, indent=1)
+    print(f"[rank {where[0]}] wrote the paired quality of images {where[1]} to {path}", flush=True)
 
 
 def _run_invert(model, datamodule, invert_to, graph, end_step, num_steps, where) -> None:
@@ -434,7 +511,7 @@ def _rms_residual(measurement_noise, dps_scale):
 
 
 def _run_restore(model, datamodule, op, solve_kw, noise, rank_seed, back, stat, start_step, writers, mean, std, where,
-                 what, output_dir, restore_report, report) -> None:
+                 what, output_dir, restore_report, report, collect=None) -> None:
     """restoration by DDNM or DPS: measure each ground-truth image with ``op`` (plus noise * N(0, 1) from rank_seed), solve
     with ``solve_kw`` from ``back(meas)``, the measurement on the image grid, and write both through ``writers``.
     ``stat`` = (add, fields) accumulates the residual A x - y; the JSON is fields(), the PSNRs, then ``report``"""
@@ -454,6 +531,9 @@ def _run_restore(model, datamodule, op, solve_kw, noise, rank_seed, back, stat, 
         psnr_deg.append(_psnr(deg, img, mean, std).cpu())
         for w, pred in zip(writers, (out, deg)):
             w.write_on_batch_end(None, model, pred, None, None, bi, 0)
+        if collect is not None:
+            collect.add("output", out)
+            collect.add("degraded", deg)
     if restore_report is not None:
         _write_json(restore_report, {**fields(), "psnr_restored": float(torch.cat(psnr_out).mean()) if psnr_out else None,
                                      "psnr_degraded": float(torch.cat(psnr_deg).mean()) if psnr_deg else None, **report})
@@ -484,10 +564,10 @@ def _solver_report(stats, solver, first) -> dict:
             "num_images": len(accepted)}
 
 
-def _run_sample(model, datamodule, writer, n_local, where, output_dir, labels_to, labels, num_samples) -> None:
+def _run_sample(model, datamodule, writer, n_local, where, output_dir, labels_to, labels, num_samples, collect=None) -> None:
     """plain sampling through Trainer.predict; ``labels()`` (unless None) gives what --labels_to records"""
     from .trainer import Trainer
-    trainer = Trainer(accelerator="gpu", strategy="auto", callbacks=[writer])
+    trainer = Trainer(accelerator="gpu", strategy="auto", callbacks=[writer] + ([] if collect is None else [collect]))
     if n_local > 0:
         trainer.predict(model, datamodule=datamodule, return_predictions=False, ckpt_path=None, distributed=False)   # generate.py:45-47
     print(f"[rank {where[0]}] wrote images {where[1]} to {output_dir}", flush=True)
@@ -504,7 +584,7 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
              num_probes=1, dequantize=False, restore_scale=1, restore_gray=False, save_degraded=None,
              restore_report=None, labels_to=None, dps_scale=None, blur_std=None, blur_radius=2,
              measurement_noise=0.0, rtol=None, atol=None, max_iterations=None, solver_report=None, window=None,
-             sigma_table=None) -> None:
+             sigma_table=None, quality_report=None, quality_perceptual=False) -> None:
     from . import _runtime_env
     from .callbacks import PreditionWriter
     from .datamodules import RandomNoiseDataModule
@@ -520,7 +600,7 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
         save_degraded=save_degraded, restore_report=restore_report, labels_to=labels_to,
         guided=guide is not None or guide_ckpt_path is not None, guidance_interval=guidance_interval, rtol=rtol, atol=atol,
         max_iterations=max_iterations, solver_report=solver_report, window=window, solver_order=solver_order,
-        sigma_table=sigma_table)
+        sigma_table=sigma_table, quality_report=quality_report, quality_perceptual=quality_perceptual)
     if sigma_table is not None:     # (before anything is loaded: a file without this N is refused, naming the N it has)
         from .schedule import Schedule
         sigma_table = Schedule.load(sigma_table, num_steps).sigmas
@@ -602,6 +682,7 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
                                        seed=rank_seed, images=images, mask=mask)
     where = (rank, f"{first}..{first + n_local - 1}")       # for the line each task prints at its end
     writer = functools.partial(PreditionWriter, write_interval="batch", mean=mean, std=std, first_index=first)
+    collect = None if quality_report is None else _Collect()
     if invert_to is not None:
         _run_invert(model, datamodule, _rank_path(invert_to, rank, world), graph, start_step, num_steps, where)
     elif likelihood_to is not None:
@@ -626,11 +707,15 @@ def generate(ckpt_path, load_ema, output_dir, num_samples, image_size, num_class
                      None if restore_report is None else _rank_path(restore_report, rank, world),
                      {"restore_scale": restore_scale, "restore_gray": bool(restore_gray), **blur_fields, "num_steps": num_steps,
                       "start_step": start_step, "seed": seed, "network_dtype": network_dtype, "first_index": first,
-                      "num_images": n_local})
+                      "num_images": n_local}, collect)
     else:
         labels = None if labels_to is None or rank != 0 else functools.partial(
             _drawn_labels, batch_size, num_workers, image_size, num_samples, num_classes, C, seed, world)
-        _run_sample(model, datamodule, writer(output_dir), n_local, where, output_dir, labels_to, labels, num_samples)
+        _run_sample(model, datamodule, writer(output_dir), n_local, where, output_dir, labels_to, labels, num_samples,
+                    collect)
+    if collect is not None and n_local > 0:
+        _write_quality(_rank_path(quality_report, rank, world), collect, images, model, quality_perceptual, mean, std,
+                       mask_box, image_size, first, seed, network_dtype, where)
     if solver_report is not None:
         report = _picard_report if solver == "picard" else _solver_report
         _write_json(_rank_path(solver_report, rank, world), report(adaptive_stats, model.solver, first))
@@ -743,6 +828,12 @@ def main(argv=None):
     parser.add_argument("--sigma_table", type=str, default=None, metavar="schedule.json",
                         help="sample on the table of this file for --num_steps (python -m tinyedm.schedule writes it) "
                              "instead of the Karras table; --solver heun, dpmpp or picard")
+    parser.add_argument("--quality_report", type=str, default=None, metavar="FILE.json",
+                        help="with --init_dir and --mask_box, --restore_*, --dps_scale or --start_step: write per image the "
+                             "MSE, PSNR and SSIM of every output (restoration: also of A+ y) against its init image; "
+                             "--mask_box: inside the box")
+    parser.add_argument("--quality_perceptual", action="store_true",
+                        help="--quality_report: add the denoiser-feature distance, the sampling checkpoint as its extractor")
     args = parser.parse_args(argv)
     _check_solver(args.solver, args.S_churn)        # a ValueError, not a usage error: raised before _validate meets it
     try:
@@ -787,7 +878,8 @@ def main(argv=None):
              restore_report=args.restore_report, labels_to=args.labels_to, dps_scale=args.dps_scale,
              blur_std=args.blur_std, blur_radius=args.blur_radius, measurement_noise=args.measurement_noise,
              rtol=args.rtol, atol=args.atol, max_iterations=args.max_iterations, solver_report=args.solver_report,
-             window=args.window, sigma_table=args.sigma_table)
+             window=args.window, sigma_table=args.sigma_table, quality_report=args.quality_report,
+             quality_perceptual=args.quality_perceptual)
 
 
 if __name__ == "__main__":

@@ -4079,3 +4079,120 @@ def pair_step_errors(X, S, tau, order=2):
     with _prof("pair_step_errors", 6.0 * pairs * K, 4.0 * (X.numel() + S.numel()) + 8.0 * d2.numel()):
         _lib.call("edm_pair_step_errors", _p(X), _p(S), _p(tau), B, G, K, int(order), _p(d2), _stream())
     return d2
+
+
+# ------------------------------------------------------------------ paired image quality (csrc/quality.hip)
+SSIM_MAX_WIN = 15               # the widest window edm_pair_ssim takes
+FEATURE_DISTANCE_MAX_C = 768    # channels of a pixel row edm_f32_pair_feature_distance keeps in one wave's registers
+
+
+def _ssim_window(window):
+    """the host-built fp64 tap table -> a numpy fp64 [win] array (checked)"""
+    if isinstance(window, torch.Tensor):
+        if window.is_cuda:
+            raise ValueError("pair_ssim: window is the HOST-built tap table (numpy or a CPU tensor), not a device tensor")
+        window = window.numpy()
+    w = np.asarray(window)
+    if w.dtype != np.float64 or w.ndim != 1:
+        raise ValueError(f"pair_ssim: window must be a 1-d fp64 table, got {w.dtype} {w.shape}")
+    win = w.shape[0]
+    if win % 2 == 0 or not 3 <= win <= SSIM_MAX_WIN:
+        raise ValueError(f"pair_ssim: the window must have an odd number of taps in [3, {SSIM_MAX_WIN}], got {win}")
+    if not np.isfinite(w).all():
+        raise ValueError("pair_ssim: window holds non-finite taps")
+    return np.ascontiguousarray(w)
+
+
+def pair_ssim(a, b, window, data_range, region=None):
+    """SSIM and the squared error of image i of a against image i of b -> (ssim fp64 [n, C], sse fp64 [n, C], counts int32
+    [n, 2]).  a, b: the same shape and dtype, uint8 [n, H, W, C] (the PNG layout) or float32 [n, C, H, W] in pixel units,
+    any non-negative strides (the kernel takes element strides: no copy to a common layout).  window: the fp64 1-D tap
+    table built on the host (compare.gaussian_window / uniform_window), odd, 3 <= win <= 15, win <= min(H, W).
+    data_range L: C1 = (0.01 L)^2, C2 = (0.03 L)^2; uint8 takes 255.  Everything is fp64 over the valid region (no
+    padding), biased variances.  sse = sum (a - b)^2 over the counted pixels (uint8: an exact integer).  region: uint8
+    [n or 1, H, W], non-zero = counted: sse over counted pixels, the SSIM mean over valid centres that are themselves
+    counted; counts = (counted pixels, counted centres); no counted centre gives NaN and a count of 0.  The bits of row i
+    depend on that pair, the shape, the window and the region row alone (include/tinyedm_hip.h)."""
+    for t, name in ((a, "a"), (b, "b")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise ValueError(f"{name}: expected a CUDA/HIP tensor -- tinyedm_amd has no CPU path")
+    if a.dtype != b.dtype or a.shape != b.shape or a.device != b.device:
+        raise ValueError(f"pair_ssim: a and b must agree in dtype, shape and device, got {a.dtype} {tuple(a.shape)} on "
+                         f"{a.device} and {b.dtype} {tuple(b.shape)} on {b.device}")
+    if a.dtype not in (torch.uint8, f32) or a.dim() != 4 or a.numel() == 0:
+        raise ValueError(f"pair_ssim: expected non-empty uint8 [n, H, W, C] or float32 [n, C, H, W] images, got {a.dtype} "
+                         f"{tuple(a.shape)}")
+    is_u8 = a.dtype == torch.uint8
+    if is_u8:
+        n, H, W, C = a.shape
+        order = (0, 3, 1, 2)
+    else:
+        n, C, H, W = a.shape
+        order = (0, 1, 2, 3)
+    w = _ssim_window(window)
+    win = w.shape[0]
+    if win > min(H, W):
+        raise ValueError(f"pair_ssim: a window of {win} taps does not fit {H} x {W} images")
+    try:
+        L = float(data_range)
+    except (TypeError, ValueError):
+        raise ValueError(f"pair_ssim: data_range must be a number, got {data_range!r}") from None
+    if not (math.isfinite(L) and L > 0.0):
+        raise ValueError(f"pair_ssim: data_range must be finite and > 0, got {data_range}")
+    if is_u8 and L != 255.0:
+        raise ValueError(f"pair_ssim: uint8 images have data_range 255, got {data_range}")
+    sa, sb = [a.stride(k) for k in order], [b.stride(k) for k in order]
+    if min(sa) < 0 or min(sb) < 0:
+        raise ValueError("pair_ssim: negative strides")
+    dev = a.device
+    shared = 0
+    if region is not None:
+        _chk_eval(region, torch.uint8, "region", None, dev)
+        if region.dim() != 3 or region.shape[0] not in (1, n) or tuple(region.shape[1:]) != (H, W):
+            raise ValueError(f"region: expected uint8 [{n} or 1, {H}, {W}], got {tuple(region.shape)}")
+        shared = int(region.shape[0] == 1 and n > 1)
+    tiles = int(_lib.call("edm_pair_ssim_tiles", H, W, win))
+    if tiles < 1 or H * W >= 2 ** 31 or n * C * tiles >= 2 ** 31:
+        raise ValueError(f"pair_ssim: {n} x {C} planes of {H} x {W} exceed the library's limits")
+    wdev = torch.from_numpy(w).to(dev)
+    partial = torch.empty(n * C * tiles, 4, dtype=torch.float64, device=dev)
+    ssim = torch.empty(n, C, dtype=torch.float64, device=dev)
+    sse = torch.empty(n, C, dtype=torch.float64, device=dev)
+    counts = torch.empty(n, 2, dtype=torch.int32, device=dev)
+    with _prof("pair_ssim", 20.0 * win * n * C * H * W, 2.0 * a.element_size() * n * C * H * W):
+        _lib.call("edm_pair_ssim", _p(a), _p(b), int(is_u8), n, C, H, W, (ctypes.c_long * 4)(*sa), (ctypes.c_long * 4)(*sb),
+                  _p(wdev), win, L, _p(region), shared, _p(partial), _p(ssim), _p(sse), _p(counts), _stream())
+    return ssim, sse, counts
+
+
+def f32_pair_feature_distance(a, b, out=None, column=0):
+    """The LPIPS form of a distance between two sets of fp32 NHWC maps (B,H,W,C) of one tap -> fp64:
+    d[b] = (1/HW) sum_p sum_c (a_pc / (|a_p| + 1e-10) - b_pc / (|b_p| + 1e-10))^2, two passes per pixel (the norms, then
+    the squared differences of the scaled values), summed in fp64 in an order fixed by (HW, C): row b has the same bits
+    whatever the batch, identical inputs give exactly 0.0, an all-zero pixel stays finite.  out=None allocates and
+    returns fp64 (B,); otherwise out is a contiguous fp64 (B, T) tensor, only column `column` is written and out is
+    returned, so several taps sit side by side.  1 <= C <= FEATURE_DISTANCE_MAX_C."""
+    try:
+        B, H, W, C = _nhwc32(a, "a")
+        _nhwc32(b, "b")
+    except (TypeError, RuntimeError) as e:
+        raise ValueError(str(e)) from None
+    if a.numel() == 0 or a.shape != b.shape or a.device != b.device:
+        raise ValueError(f"f32_pair_feature_distance: expected two non-empty (B,H,W,C) maps of one shape on one device, got "
+                         f"{tuple(a.shape)} and {tuple(b.shape)}")
+    if C > FEATURE_DISTANCE_MAX_C:
+        raise ValueError(f"f32_pair_feature_distance: at most {FEATURE_DISTANCE_MAX_C} channels, got {C}")
+    if isinstance(column, bool) or not isinstance(column, int) or column < 0:
+        raise ValueError(f"f32_pair_feature_distance: column must be an integer >= 0, got {column!r}")
+    if out is None:
+        if column:
+            raise ValueError("f32_pair_feature_distance: a column needs the out tensor it points into")
+        res = torch.empty(B, 1, device=a.device, dtype=torch.float64)
+    else:
+        _chk_eval(out, torch.float64, "out", None, a.device)
+        if out.dim() != 2 or out.shape[0] != B or column >= out.shape[1]:
+            raise ValueError(f"out: expected ({B}, T) with T > column = {column}, got {tuple(out.shape)}")
+        res = out
+    with _prof("f32_pair_feature_distance", 8.0 * a.numel(), 8.0 * a.numel()):
+        _lib.call("edm_f32_pair_feature_distance", _p(a), _p(b), _p(res), B, H * W, C, res.shape[1], column, _stream())
+    return res.view(B) if out is None else out
